@@ -18,11 +18,20 @@ normalisation summaries and the per-shard top-k lists.
 value = sum over ranks of the postings of all queries (include + exclude list
 lengths) / max-over-ranks wall time of the K timed steps.
 
-After the headline the default run measures the other BASELINE configs as
-extra legs on the same GPUs: C3 (1B postings, 3-term AND + 1
-exclude, split over the N ranks: strong scaling), C4 (4096 concurrent 2-4 term
-queries over the C3 index) and C5 (the custom and /date RankingProfiles over the
-per-GPU 625M-posting slice of the 5B corpus).  `--legs none` skips them.
+A plain run does only what the headline needs: it builds the index, runs every
+distinct batch once with statistics (the postings each step is credited with),
+warms up, times the K steps and prints the line.  `--dump-outputs DIR` also
+writes what the last timed step returned to its caller (DIR/<name>.npy).
+
+`--full` adds everything else, each outside the timed steps: the same region
+with identical batches, the isolated pass behind the per-kernel and roofline
+figures, the parity sample against the oracle, single-query latency, the CPU
+baselines, the detail record (profiles/run/, or --detail-dir) and the other
+BASELINE configs as extra legs on the same GPUs: C3 (1B postings,
+3-term AND + 1 exclude, split over the N ranks: strong scaling), C4 (4096
+concurrent 2-4 term queries over the C3 index) and C5 (the custom and /date
+RankingProfiles over the per-GPU 625M-posting slice of the 5B corpus).
+`--legs none` skips the legs.
 """
 
 import argparse
@@ -48,6 +57,14 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run what a plain run leaves out: identical-batch region, "
+                         "isolated pass (per-kernel and roofline figures), parity sample, latency, CPU "
+                         "baselines, the extra legs and the detail record (the options below tune these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (hits and counts of its batch) as DIR/<name>.npy")
+    ap.add_argument("--detail-dir", default=os.path.join(ROOT, "profiles", "run"),
+                    help="(--full) where the full record bench_detail_src<source hash>.json is written")
     ap.add_argument("--config", default="C2")
     ap.add_argument("--nq", type=int, default=1000)
     ap.add_argument("--k", type=int, default=100)
@@ -432,6 +449,10 @@ class Runner:
             bi = i_last % D
             if bi not in out:
                 out[bi] = (bytes(memoryview(bufs[s][0]).cast("B")), list(bufs[s][1]))
+        # what the last timed step handed its caller: its slot's buffers, its batch
+        s_last = (steps - 1) % depth
+        last = {"batch": (steps - 1) % D, "hits": bytes(memoryview(bufs[s_last][0]).cast("B")),
+                "nout": list(bufs[s_last][1])} if steps > 0 else None
         timed["stats_in_timed_region"] = timed_stats
         timed["cgroup_cpu_stat"] = throttle
         ident = None
@@ -459,7 +480,8 @@ class Runner:
             iso["batches"] = 1
             iso["isolated_runs_t_kernels_us"] = [round(r["t_kernels_ns"] / 1e3, 1) for r in runs]
         return {"dt": dt, "steps": steps, "total_post": total_post, "timed": timed, "iso": iso, "bufs": bufs,
-                "arrs": arrs, "keep": keep, "timed_out": out, "batches": batches, "D": D, "identical": ident,
+                "arrs": arrs, "keep": keep, "timed_out": out, "last_out": last, "batches": batches, "D": D,
+                "identical": ident,
                 "per_batch_postings": [pb["postings_in"] for pb in per_batch]}
 
 
@@ -687,21 +709,26 @@ def run(args, rank, world, local):
     elif args.profile == "date":
         prof = RankingProfile.date()
     shard_transport = transport_summary(R.transports()) if world > 1 else None
-    M = R.measure(bats, idx.hashes, prof, args.k, args.steps, args.warmup, args.inflight)
+    M = R.measure(bats, idx.hashes, prof, args.k, args.steps, args.warmup, args.inflight,
+                  isolated=args.full, identical=args.full)
     value = M["total_post"] / M["dt"]
     ms_per_step = M["dt"] / args.steps * 1e3
     iso, timed = M["iso"], M["timed"]
-    pmc = load_pmc(args.config) if world == 1 and args.shard_of == 1 else None
-    roof, kern = roofline_block(iso, timed, args.steps, ms_per_step, pmc)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, M, args.k)
+    roof = kern = None
+    if args.full:
+        pmc = load_pmc(args.config) if world == 1 and args.shard_of == 1 else None
+        roof, kern = roofline_block(iso, timed, args.steps, ms_per_step, pmc)
 
     # parity of this very workload and single-query latency (outside the timed region)
     parity = lat = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         parity, lat = check_and_latency(R, M, idx.hashes, idx, prof, args.k, 0 if args.no_cpu else args.check,
                                         args.latency, args.config, threads=host_cores()[0])
 
     cpu = cpu1 = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         nthr, aff, why = host_cores()
         cpu = cpu_baseline(idx, qs, NOW_MS, args.k, args.cpu_budget, nthr, prof, args.config)
         cpu["cores_why"] = why
@@ -715,7 +742,7 @@ def run(args, rank, world, local):
     legs = {}
     if args.legs == "auto":
         args.legs = "C3,C4,C5" if world == 1 else "none"
-    if args.legs and args.legs != "none" and args.shard_of == 1:
+    if args.full and args.legs and args.legs != "none" and args.shard_of == 1:
         for leg in [x.strip() for x in args.legs.split(",") if x.strip()]:
             try:
                 legs.update(run_leg(R, leg, args, rank, world))
@@ -737,7 +764,6 @@ def run(args, rank, world, local):
         else:
             corpus_s = (f"{base.n_postings / 1e6:.0f}M postings ({base.n_urls / 1e6:.0f}M URLs x "
                         f"{base.n_terms} words) per GPU")
-        nbi = max(1, iso["batches"])
         out = {
             "metric": "postings joined+ranked/sec (node)",
             "value": value, "unit": "postings/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -770,7 +796,7 @@ def run(args, rank, world, local):
             "inflight": args.inflight,
             # per batch, from the library's own HIP events (isolated pass): join+probe kernels,
             # normalisation (reduce..combine), scoring (score..emit), all kernels; host = call to results
-            "phase_ms": phase_ms(iso),
+            "phase_ms": phase_ms(iso) if iso else None,
             "url_dictionary_build_s": round(t_dict, 3),
             "legs": legs or None,
             # world > 1: how the shards' collectives travelled (yrwi_shard_info of every rank)
@@ -778,34 +804,77 @@ def run(args, rank, world, local):
         }
         ident = source_identity()
         out["build"] = ident
-        detail = write_detail(out, ident)
+        detail = write_detail(out, ident, args.detail_dir) if args.full else None
         print(json.dumps(compact_line(out, detail)), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
 
 
-def write_detail(out, ident):
+def write_detail(out, ident, where):
     """The full record (every per-kernel block, the path model, the identical-batch
-    run, per-batch data) goes to profiles/bench_detail_src<source hash>.json and, when a
-    gpurun_out/ directory can be made, a copy there (what a GPU call brings back)."""
-    # named by the hash of libyrwi's sources: the committed detail of a build's own
-    # full run carries the same name as any later run of that build (the driver's)
-    name = f"bench_detail_src{ident['src']}.json"
-    rel = os.path.join("profiles", name)
-    for d in (os.path.join(ROOT, "profiles"), os.path.join(ROOT, "gpurun_out")):
-        try:
-            os.makedirs(d, exist_ok=True)
-            with open(os.path.join(d, name), "w") as f:
-                json.dump(out, f, indent=1)
-        except OSError as e:
-            log(f"detail not written to {d}: {e!r}")
-    return rel
+    run, per-batch data) goes to <where>/bench_detail_src<source hash>.json."""
+    # named by the hash of libyrwi's sources: a build's record keeps one name over its
+    # runs (the copy committed under profiles/ with a build's final run carries it too)
+    path = os.path.join(where, f"bench_detail_src{ident['src']}.json")
+    try:
+        os.makedirs(where, exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+    except OSError as e:
+        log(f"detail not written to {where}: {e!r}")
+        return None
+    rel = os.path.relpath(path, ROOT)
+    return path if rel.startswith("..") else rel
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(where, M, k):
+    """What the last timed step returned to its caller, as float arrays (DIR/<name>.npy;
+    every value is an integer a float64 / float32 holds exactly):
+      nout.npy      float64 [Q]        hits returned for each query
+      score.npy     float64 [Q, k]     yrwi_hit.score, rank order (0 past nout)
+      tiebreak.npy  float64 [Q, k]     yrwi_hit.tiebreak
+      urlhash.npy   float32 [Q, k, 12] yrwi_hit.urlhash, one byte per element
+      query.npy     float64 [Q]        which queries of the batch the rows are
+      step.npy      float64 [2]        the distinct batch the step ran, queries in it
+    Q is every query of the batch, or a fixed seeded sample of them (ascending)
+    when all would pass 64 MB."""
+    import ctypes
+    import numpy as np
+    from yacy_search_server_amd._lib import CHit
+    last = M["last_out"]
+    nq = len(last["nout"])
+    dt = np.dtype([("urlhash", np.uint8, 12), ("tiebreak", "<i4"), ("score", "<i8")])
+    assert dt.itemsize == ctypes.sizeof(CHit)
+    hits = np.frombuffer(last["hits"], dtype=dt, count=nq * k).reshape(nq, k)
+    nout = np.asarray(last["nout"], dtype=np.int64)
+    per_query = 8 + 8 + k * (8 + 8 + 12 * 4)
+    sel = np.arange(nq)
+    if nq * per_query + 16 > DUMP_MAX_BYTES:
+        sel = np.sort(np.random.default_rng(0x59525749).choice(nq, (DUMP_MAX_BYTES - 16) // per_query, replace=False))
+    live = np.arange(k)[None, :] < nout[sel, None]  # rows past nout are not results
+    score = np.where(live, hits["score"][sel], 0)
+    if np.abs(score).max(initial=0) >= 1 << 53:
+        log("dump-outputs: a score passes 2^53, score.npy rounds it")
+    os.makedirs(where, exist_ok=True)
+    for name, a in (("nout", nout[sel].astype(np.float64)),
+                    ("score", score.astype(np.float64)),
+                    ("tiebreak", np.where(live, hits["tiebreak"][sel], 0).astype(np.float64)),
+                    ("urlhash", np.where(live[:, :, None], hits["urlhash"][sel], 0).astype(np.float32)),
+                    ("query", sel.astype(np.float64)),
+                    ("step", np.asarray([last["batch"], nq], dtype=np.float64))):
+        np.save(os.path.join(where, name + ".npy"), a)
+    log(f"outputs of the last timed step (batch {last['batch']}, {len(sel)} of {nq} queries) written to {where}")
 
 
 def _short_roof(r):
     keep = ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "hbm_frac", "alg_bytes_per_launch",
             "credited_bytes_per_launch", "mean_launch_us", "rocprof_mean_launch_us", "frac_rocprof")
+    if not r:
+        return None
     o = {k: r.get(k) for k in keep if k in r}
     if r.get("profile"):
         o["profile"] = r["profile"]
@@ -862,8 +931,8 @@ def compact_line(out, detail):
     line["roofline_kernels"] = _short_kernels(out.get("roofline_kernels"))
     line["phase_ms"] = out.get("phase_ms")
     line["build"] = out.get("build")
-    # the full record, written on the box that ran this (the driver's copy stays there;
-    # everything the line's figures rest on is in the line itself)
+    # the full record (--full), written where this ran; everything the line's figures
+    # rest on is in the line itself
     line["detail"] = detail
     return line
 

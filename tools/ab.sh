@@ -4,7 +4,7 @@
 #   bash tools/ab.sh name1=path1.so name2=path2.so ...   (path "cur" = the in-tree build)
 set -e
 mkdir -p gpurun_out/ab
-ARGS=${AB_ARGS:---steps 20 --warmup 5 --no-cpu --latency 0}
+ARGS="--full ${AB_ARGS:---steps 20 --warmup 5 --no-cpu --latency 0}"
 for i in $(seq 1 ${ROUNDS:-2}); do
   for nv in "$@"; do
     n=${nv%%=*}; p=${nv#*=}

@@ -1,7 +1,9 @@
-# Round check at HEAD (run through gpurun from the repo root): the whole GPU suite,
-# then the driver's bench command.  Output in gpurun_out/final/.
+# Round check at HEAD (run from the repo root on the GPU box): the whole GPU suite,
+# then the full bench (headline, legs, CPU baseline).  Output in $OUT (default
+# bench_out/final).
 set -o pipefail
-mkdir -p gpurun_out/final
+OUT=${OUT:-bench_out/final}
+mkdir -p $OUT
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread \
-  > gpurun_out/final/t.log 2>&1 || exit $?
-timeout -k 10 1000 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/final/b.json 2> gpurun_out/final/b.err || exit $?
+  > $OUT/t.log 2>&1 || exit $?
+timeout -k 10 1000 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/b.json 2> $OUT/b.err || exit $?

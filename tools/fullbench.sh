@@ -1,4 +1,6 @@
-# The driver's round-end bench command exactly (default legs, CPU baseline), under a time limit.
+# The full bench (headline, default legs, CPU baseline) under a time limit.  Output in
+# $OUT (default bench_out/full).
 set -o pipefail
-mkdir -p gpurun_out/full
-timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/full/bench.json 2> gpurun_out/full/bench.err || exit $?
+OUT=${OUT:-bench_out/full}
+mkdir -p $OUT
+timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err || exit $?

@@ -5,7 +5,7 @@
 set -o pipefail
 mkdir -p gpurun_out/legab
 LEGS=${LEGS:-C5}
-ARGS=${LEG_ARGS:-"--steps 5 --warmup 2 --no-cpu --latency 0 --check 0 --leg-check 4 --leg-latency 0"}
+ARGS="--full "${LEG_ARGS:-"--steps 5 --warmup 2 --no-cpu --latency 0 --check 0 --leg-check 4 --leg-latency 0"}
 root=$(pwd)
 for i in 1 2; do
   for d in cur $DIRS; do
