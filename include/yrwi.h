@@ -228,6 +228,42 @@ int yrwi_list_size(yrwi_ctx* ctx, const uint8_t term[12], int64_t* n);
  * (its url-hash shard when sharded), ascending by url hash.  *n = the list size
  * (0: no list); YRWI_E_ARG when cap < *n (nothing copied). */
 int yrwi_get_list(yrwi_ctx* ctx, const uint8_t term[12], uint8_t* rows40, int64_t cap, int64_t* n);
+/* ---- index updates on the device (yrwi_update.hip): the caller keeps no host copy of a
+ *      list and sends only the change.  Both calls wait for the batches in flight, as
+ *      yrwi_put_list does, and take the rows they are given: a sharded context does not
+ *      filter them to its url-hash range (the caller sends each shard its own). ---- */
+enum {
+  YRWI_ADD_REPLACE = 0, /* RowSet.put, what IndexCell.add(termHash, entry) does: the last candidate stays */
+  YRWI_ADD_KEEP = 1,    /* RowSet.mergeEnum, the heap loader's rule: the first candidate stays */
+  YRWI_ADD_RECENT = 2   /* ReferenceContainer.putAllRecent: a later candidate takes the place unless its
+                           lastModified (column a, bytes 12-13) is strictly smaller */
+};
+typedef struct yrwi_update_stats {
+  int64_t terms;          /* lists created, changed or emptied by the call */
+  int64_t new_terms, emptied_terms;
+  int64_t added;          /* batch postings whose url was new to their list */
+  int64_t replaced;       /* batch postings that took the place of an existing row */
+  int64_t dropped;        /* batch postings that lost (to an existing row or another batch row) */
+  int64_t removed;        /* postings removed (yrwi_remove_postings) */
+  int32_t launches;       /* kernel launches, device-library calls, copies and memsets the call enqueued:
+                             a function of the batch's bytes, never of the number of terms touched */
+  int32_t syncs;          /* host waits on the device the call made (staging growth on a lane's first
+                             large batch not counted); independent of the terms touched */
+} yrwi_update_stats;
+/* IndexCell.add in bulk: posting i is rows40 + 40 i, for the list of term terms12 + 12 i, in any
+ * order.  For each (term, url hash) the candidates are the list's row, if it has one, and then the
+ * batch's rows of that pair in batch order; `policy` says which one stays.  Lists stay strictly
+ * ascending by url hash; a term without a list gets one.  added + replaced + dropped == n.  Atomic:
+ * on YRWI_E_HASH (term or url hash), YRWI_E_NULL_LANGUAGE, YRWI_E_LIMIT (a list would pass
+ * 53,687,091 rows) or YRWI_E_NOMEM nothing has changed.  st may be NULL. */
+int yrwi_add_postings(yrwi_ctx* ctx, const uint8_t* terms12, const uint8_t* rows40, int64_t n, int policy,
+                      yrwi_update_stats* st);
+/* IndexCell.remove(termHash, urlHashes) for each of nterms terms; nterms == 0: every list of the
+ * context (Segment.removeAllUrlReferences without the document's words).  Duplicate urls and terms
+ * count once, unknown terms and absent urls are ignored; a list left empty disappears as after
+ * yrwi_put_list(n = 0).  st->removed = rows removed.  st may be NULL. */
+int yrwi_remove_postings(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uint8_t* urls12,
+                         int64_t nurls, yrwi_update_stats* st);
 /* Brings the url dictionary (url hash -> order-preserving 32-bit url id, the
  * join key in HBM) up to date now instead of at the next query.  The first
  * build sorts every key; later put_list / removal / load_heaps changes are

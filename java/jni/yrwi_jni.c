@@ -48,6 +48,53 @@ JNIEXPORT jint JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_putList(JNIEnv* env, jc
   return rc;
 }
 
+/* ---- index updates on the device (yrwi_add_postings / yrwi_remove_postings) ---- */
+/* yrwi_update_stats as long[9]: terms, new_terms, emptied_terms, added, replaced, dropped, removed,
+ * launches, syncs; NULL when rc != 0 */
+static jlongArray update_stats(JNIEnv* env, int rc, const yrwi_update_stats* st) {
+  if (rc != 0) return NULL;
+  const jlong v[9] = {st->terms, st->new_terms, st->emptied_terms, st->added, st->replaced,
+                      st->dropped, st->removed, st->launches, st->syncs};
+  jlongArray res = (*env)->NewLongArray(env, 9);
+  if (res) (*env)->SetLongArrayRegion(env, res, 0, 9, v);
+  return res;
+}
+
+JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_addPostings(JNIEnv* env, jclass c, jlong ctx,
+                                                                          jbyteArray terms, jbyteArray rows, jint n,
+                                                                          jint policy) {
+  /* both arrays are copied out of the Java heap: the call synchronises with the GPU */
+  uint8_t* t = copy_in(env, terms, (int64_t)n * 12);
+  if (!t) return NULL;
+  uint8_t* r = copy_in(env, rows, (int64_t)n * 40);
+  if (!r) {
+    free(t);
+    return NULL;
+  }
+  yrwi_update_stats st;
+  int rc = yrwi_add_postings((yrwi_ctx*)(intptr_t)ctx, t, r, n, policy, &st);
+  free(t);
+  free(r);
+  return update_stats(env, rc, &st);
+}
+
+JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_removePostings(JNIEnv* env, jclass c, jlong ctx,
+                                                                             jbyteArray terms, jint nterms,
+                                                                             jbyteArray urls, jint nurls) {
+  uint8_t* t = copy_in(env, terms, (int64_t)nterms * 12);
+  if (!t) return NULL;
+  uint8_t* u = copy_in(env, urls, (int64_t)nurls * 12);
+  if (!u) {
+    free(t);
+    return NULL;
+  }
+  yrwi_update_stats st;
+  int rc = yrwi_remove_postings((yrwi_ctx*)(intptr_t)ctx, t, nterms, u, nurls, &st);
+  free(t);
+  free(u);
+  return update_stats(env, rc, &st);
+}
+
 JNIEXPORT jbyteArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_joinExclude(JNIEnv* env, jclass c, jlong ctx,
                                                                           jbyteArray incl, jint nincl, jbyteArray excl,
                                                                           jint nexcl, jint maxd, jlong now) {

@@ -98,6 +98,31 @@ public final class GpuRWI implements AutoCloseable {
         check(putList(this.ctx, termHash, chunkcache, n, 1));
     }
 
+    /** Policies of addPostings (YRWI_ADD_*): which of a (term, url) pair's candidates stays. */
+    public static final int ADD_REPLACE = 0;  // RowSet.put: IndexCell.add(termHash, entry), ReferenceContainerCache.add
+    public static final int ADD_KEEP = 1;     // RowSet.mergeEnum: IndexCell.add(container) merged below what is stored
+    public static final int ADD_RECENT = 2;   // ReferenceContainer.putAllRecent (DHT transfers)
+
+    /** IndexCell.add in bulk (yrwi_add_postings): posting i is rows[40 i, 40 i + 40) for the list of the
+     *  term hash terms[12 i, 12 i + 12), in any order; only the batch crosses to the device.  Returns
+     *  {terms, newTerms, emptiedTerms, added, replaced, dropped, removed, launches, syncs}. */
+    public synchronized long[] addPostings(final byte[] terms, final byte[] rows, final int n, final int policy) {
+        final long[] st = addPostings(this.ctx, terms, rows, n, policy);
+        if (st == null) throw new IllegalStateException("yrwi_add_postings failed");
+        return st;
+    }
+
+    /** IndexCell.remove(termHash, urlHashes) for every term of `terms`; terms == null or empty: every
+     *  list (Segment.removeAllUrlReferences without the document's words).  Returns the statistics
+     *  of addPostings (removed = rows removed). */
+    public synchronized long[] removePostings(final byte[][] terms, final byte[][] urls) {
+        final int nterms = terms == null ? 0 : terms.length;
+        final long[] st = removePostings(this.ctx, nterms == 0 ? new byte[0] : flatten(terms), nterms,
+                                         flatten(urls), urls.length);
+        if (st == null) throw new IllegalStateException("yrwi_remove_postings failed");
+        return st;
+    }
+
     /** Index.size(termHash) of each term on the GPU index (yrwi_list_size; 0: no list). */
     public synchronized long[] listSizes(final byte[][] terms) {
         return listSizes(this.ctx, flatten(terms), terms.length);
@@ -333,6 +358,8 @@ public final class GpuRWI implements AutoCloseable {
     private static native long open(int device);
     private static native void close(long ctx);
     private static native int putList(long ctx, byte[] term, byte[] rows, int n, int sorted);
+    private static native long[] addPostings(long ctx, byte[] terms, byte[] rows, int n, int policy);
+    private static native long[] removePostings(long ctx, byte[] terms, int nterms, byte[] urls, int nurls);
     private static native byte[] joinExclude(long ctx, byte[] incl, int nincl, byte[] excl, int nexcl,
                                              int maxDistance, long nowMillis);
     private static native long[] normalizeScore(long ctx, byte[] rows, int m, int[] profile32, String language,

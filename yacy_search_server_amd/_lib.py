@@ -120,6 +120,14 @@ class CLoadStats(ctypes.Structure):
                                               "dropped_terms")]
 
 
+class CUpdateStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("terms", "new_terms", "emptied_terms", "added", "replaced", "dropped",
+                                              "removed")] + [("launches", ctypes.c_int32), ("syncs", ctypes.c_int32)]
+
+
+ADD_POLICIES = {"replace": 0, "keep": 1, "recent": 2}
+
+
 # every symbol include/yrwi.h declares, with its ctypes signature
 _VP = ctypes.c_void_p
 SIGNATURES = {
@@ -134,6 +142,10 @@ SIGNATURES = {
     "yrwi_last_error": (ctypes.c_char_p, [_VP]),
     "yrwi_shard_info": (ctypes.c_int, [_VP, ctypes.POINTER(CTransportInfo)]),
     "yrwi_put_list": (ctypes.c_int, [_VP, ctypes.c_char_p, _VP, ctypes.c_int64, ctypes.c_int]),
+    "yrwi_add_postings": (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int64, ctypes.c_int,
+                                         ctypes.POINTER(CUpdateStats)]),
+    "yrwi_remove_postings": (ctypes.c_int, [_VP, _VP, ctypes.c_int32, _VP, ctypes.c_int64,
+                                            ctypes.POINTER(CUpdateStats)]),
     "yrwi_build_url_ids": (ctypes.c_int, [_VP]),
     "yrwi_list_size": (ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]),
     "yrwi_get_list": (ctypes.c_int, [_VP, ctypes.c_char_p, _VP, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),

@@ -615,7 +615,9 @@ int ensure_url_ids(CtxBase* ctx);
 void measure_scratch(CtxBase* ctx);
 // dense host ids in every index record (after ensure_url_ids; no batch in flight)
 int ensure_host_ids(CtxBase* ctx);
-// the list of `term` was added / replaced (added = true) or removed: url ids are due
+// the list of `term` was added / replaced (added = true) or removed: url ids are due.  old_n is
+// charged to dict_churn: the postings whose keys may have left the dictionary's lists (put_list:
+// the whole old list; yrwi_update.hip: the postings really removed, 0 for an add)
 void index_changed(CtxBase* ctx, const KeyT& term, int64_t old_n, bool added);
 // brings the url ids up to date, then counts inconsistencies (0: every id names its key)
 int check_url_ids(CtxBase* ctx, int64_t* bad);

@@ -1,0 +1,637 @@
+// yrwi_update.hip -- index updates on the device: postings added and urls removed in bulk
+// (IndexCell.add(termHash, entry) / add(container) / remove(termHash, urlHashes),
+// Segment.removeAllUrlReferences).
+//
+// yrwi_add_postings: the batch is uploaded through the lane's pinned staging and keyed by
+// k_validate; the host maps every row's term to a job (one per touched list); the device
+// sorts the batch by (job, 72-bit url key, arrival index) with two stable radix sorts (low
+// 64 key bits, then job | top 8 key bits); k_upd_pick lets the head of every run of equal
+// (job, url) pick the run's winner under the policy, take its lower bound in the job's list
+// and settle it against an existing row; one scan over the batch rows numbers the new keys;
+// one read-back brings the per-job counts and the validation bits; the new lists come from
+// index memory in one round; k_upd_old places the old rows of the changed lists (flattened
+// over a prefix table) and k_upd_new the surviving batch rows.  Nothing is launched or
+// waited for per term.
+//
+// yrwi_remove_postings: k_rm_count looks every key of the named lists up in the sorted,
+// deduplicated url set and counts the hits per list (read back once); only the lists that
+// lose rows are flagged, scanned and compacted (k_rm_flag, one scan, k_rm_place).
+//
+// A changed list is a new list in index memory (the old copy is dead until repack_index,
+// reached through ensure_url_ids) and goes through index_changed like a replaced list.
+
+#include <hipcub/hipcub.hpp>
+
+#include "yrwi_host.h"
+
+using namespace yrwi;
+
+namespace {
+
+struct UpdJob {  // one touched list and the job's rows in the sorted batch
+  const uint64_t* akhi;
+  const uint8_t* aklo;
+  const uint8_t* arows;
+  int64_t an;
+  uint64_t* okhi;
+  uint8_t* oklo;
+  uint8_t* orows;
+  int64_t boff, bn;
+};
+
+struct RmJob {
+  const uint64_t* khi;
+  const uint8_t* klo;
+  const uint8_t* rows;
+  int64_t n;
+  uint64_t* okhi;
+  uint8_t* oklo;
+  uint8_t* orows;
+};
+
+__device__ __forceinline__ bool key_lt(uint64_t ah, uint32_t al, uint64_t bh, uint32_t bl) {
+  return ah < bh || (ah == bh && al < bl);
+}
+
+__device__ __forceinline__ int64_t lb_key(const uint64_t* __restrict__ kh, const uint8_t* __restrict__ kl, int64_t lo,
+                                          int64_t hi, uint64_t h, uint32_t l) {
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (key_lt(kh[mid], kl[mid], h, l)) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// last segment whose offset is <= i
+__device__ __forceinline__ int seg_of(const int64_t* __restrict__ off, int nseg, int64_t i) {
+  int lo = 0, hi = nseg - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ void copy_row(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src) {
+  const uint64_t* s = reinterpret_cast<const uint64_t*>(src);  // rows are 8-byte aligned (40 B, 256 B bases)
+  uint64_t* d = reinterpret_cast<uint64_t*>(dst);
+#pragma unroll
+  for (int i = 0; i < 5; i++) d[i] = s[i];
+}
+
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, int lane) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, lane, 64);
+  const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), lane, 64);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// Every lane of the wave holds one row to move (dstp null: none).  The wave's 64 rows are
+// 320 8-byte words: in each of 5 rounds lane l moves word 64 k + l, so neighbouring lanes
+// read neighbouring words of neighbouring rows (full 128-B lines where the rows are
+// consecutive, as the old rows of a list are).  Called by every thread of the block.
+__device__ __forceinline__ void wave_move_rows(const uint8_t* srcp, uint8_t* dstp) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t s = (uint64_t)srcp, d = (uint64_t)dstp;
+#pragma unroll
+  for (int k = 0; k < 5; k++) {
+    const int w = k * 64 + lane;
+    const int r = w / 5, word = w - r * 5;
+    const uint64_t sp = shfl64(s, r), dp = shfl64(d, r);
+    if (dp) *reinterpret_cast<uint64_t*>(dp + word * 8) = *reinterpret_cast<const uint64_t*>(sp + word * 8);
+  }
+}
+
+// lastModified: the row's `a` cell (bytes 12-13, big endian)
+__device__ __forceinline__ uint32_t row_lm(const uint8_t* __restrict__ r) { return ((uint32_t)r[12] << 8) | r[13]; }
+
+// ---------------------------------------------------------------- add: sort keys
+__global__ void k_upd_key_a(const uint64_t* __restrict__ khi, const uint8_t* __restrict__ klo, int64_t n,
+                            uint64_t* __restrict__ ka, uint32_t* __restrict__ idx) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  ka[i] = (khi[i] << 8) | (uint64_t)klo[i];
+  idx[i] = (uint32_t)i;
+}
+
+__global__ void k_upd_key_b(const uint64_t* __restrict__ khi, const int32_t* __restrict__ job,
+                            const uint32_t* __restrict__ idx, int64_t n, uint64_t* __restrict__ kb) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t p = idx[i];
+  kb[i] = ((uint64_t)(uint32_t)job[p] << 8) | (khi[p] >> 56);
+}
+
+__global__ void k_upd_gather(const uint64_t* __restrict__ khi, const uint8_t* __restrict__ klo,
+                             const int32_t* __restrict__ job, const uint32_t* __restrict__ perm, int64_t n,
+                             uint64_t* __restrict__ skh, uint8_t* __restrict__ skl, int32_t* __restrict__ sjob) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n) return;
+  const uint32_t p = perm[s];
+  skh[s] = khi[p];
+  skl[s] = klo[p];
+  sjob[s] = job[p];
+}
+
+// The head of every run of equal (job, url key) -- the run is in arrival order -- picks the
+// run's winner: REPLACE the last, KEEP the first, RECENT the last of the largest
+// lastModified; then settles it against the list's row of that key, if there is one.
+// ins = the winner brings a new key, rep = it takes an existing row's place.  The head walks its
+// run alone: a run is as long as one (term, url) pair repeats in the batch, 1 in a crawl's batch.
+__global__ void k_upd_pick(const UpdJob* __restrict__ jobs, const uint8_t* __restrict__ rows,
+                           const uint32_t* __restrict__ perm, const uint64_t* __restrict__ skh,
+                           const uint8_t* __restrict__ skl, const int32_t* __restrict__ sjob, int64_t n, int policy,
+                           int32_t* __restrict__ ins, uint8_t* __restrict__ rep, int64_t* __restrict__ lbA,
+                           uint32_t* __restrict__ src, unsigned long long* __restrict__ jcnt) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n) return;
+  const int32_t j = sjob[s];
+  const uint64_t h = skh[s];
+  const uint32_t l = skl[s];
+  if (s > 0 && sjob[s - 1] == j && skh[s - 1] == h && (uint32_t)skl[s - 1] == l) {
+    ins[s] = 0;
+    rep[s] = 0;
+    return;
+  }
+  int64_t w = s;
+  uint32_t lmw = 0;
+  if (policy == YRWI_ADD_RECENT) lmw = row_lm(rows + (int64_t)perm[s] * YRWI_ROW_BYTES);
+  if (policy != YRWI_ADD_KEEP) {
+    for (int64_t e = s + 1; e < n && sjob[e] == j && skh[e] == h && (uint32_t)skl[e] == l; e++) {
+      if (policy == YRWI_ADD_REPLACE) {
+        w = e;
+      } else {
+        const uint32_t lme = row_lm(rows + (int64_t)perm[e] * YRWI_ROW_BYTES);
+        if (lme >= lmw) {
+          w = e;
+          lmw = lme;
+        }
+      }
+    }
+  }
+  const UpdJob J = jobs[j];
+  const int64_t p = lb_key(J.akhi, J.aklo, 0, J.an, h, l);
+  const bool exists = p < J.an && J.akhi[p] == h && (uint32_t)J.aklo[p] == l;
+  int i = 0, r = 0;
+  if (!exists) i = 1;
+  else if (policy == YRWI_ADD_REPLACE) r = 1;
+  else if (policy == YRWI_ADD_RECENT) r = lmw >= row_lm(J.arows + p * YRWI_ROW_BYTES);
+  ins[s] = i;
+  rep[s] = (uint8_t)r;
+  lbA[s] = p;
+  src[s] = perm[w];
+  if (i) atomicAdd(&jcnt[2 * (int64_t)j], 1ull);
+  if (r) atomicAdd(&jcnt[2 * (int64_t)j + 1], 1ull);
+}
+
+// Old rows of the changed lists, flattened over aoff: row k of its list goes to k + (new
+// keys of the job below its key), unless a batch row takes its place.
+__global__ __launch_bounds__(256) void k_upd_old(const UpdJob* __restrict__ jobs, const int32_t* __restrict__ cj,
+                                                 const int64_t* __restrict__ aoff, int ncj, int64_t total,
+                                                 const uint64_t* __restrict__ skh, const uint8_t* __restrict__ skl,
+                                                 const int64_t* __restrict__ insx, const uint8_t* __restrict__ rep) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint8_t* srcp = nullptr;
+  uint8_t* dstp = nullptr;
+  if (i < total) {
+    const int c = seg_of(aoff, ncj, i);
+    const UpdJob J = jobs[cj[c]];
+    const int64_t k = i - aoff[c];
+    const uint64_t h = J.akhi[k];
+    const uint32_t l = J.aklo[k];
+    const int64_t bend = J.boff + J.bn;
+    const int64_t lb = lb_key(skh, skl, J.boff, bend, h, l);  // the head of the key's run, if the batch has it
+    const bool taken = lb < bend && skh[lb] == h && (uint32_t)skl[lb] == l && rep[lb];
+    if (!taken) {
+      const int64_t pos = k + (insx[lb] - insx[J.boff]);
+      J.okhi[pos] = h;
+      J.oklo[pos] = (uint8_t)l;
+      srcp = J.arows + k * YRWI_ROW_BYTES;
+      dstp = J.orows + pos * YRWI_ROW_BYTES;
+    }
+  }
+  wave_move_rows(srcp, dstp);
+}
+
+// Surviving batch rows: lower bound in the old list + new keys of the job before it.
+__global__ void k_upd_new(const UpdJob* __restrict__ jobs, const uint8_t* __restrict__ rows, int64_t n,
+                          const uint64_t* __restrict__ skh, const uint8_t* __restrict__ skl,
+                          const int32_t* __restrict__ sjob, const int32_t* __restrict__ ins,
+                          const uint8_t* __restrict__ rep, const int64_t* __restrict__ insx,
+                          const int64_t* __restrict__ lbA, const uint32_t* __restrict__ src) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n || !(ins[s] || rep[s])) return;
+  const UpdJob J = jobs[sjob[s]];
+  const int64_t pos = lbA[s] + (insx[s] - insx[J.boff]);
+  J.okhi[pos] = skh[s];
+  J.oklo[pos] = skl[s];
+  copy_row(J.orows + pos * YRWI_ROW_BYTES, rows + (int64_t)src[s] * YRWI_ROW_BYTES);
+}
+
+// ---------------------------------------------------------------- remove
+__device__ __forceinline__ bool in_set(const uint64_t* __restrict__ ukh, const uint8_t* __restrict__ ukl, int64_t nu,
+                                       uint64_t h, uint32_t l) {
+  const int64_t p = lb_key(ukh, ukl, 0, nu, h, l);
+  return p < nu && ukh[p] == h && (uint32_t)ukl[p] == l;
+}
+
+__global__ void k_rm_count(const RmJob* __restrict__ jobs, const int64_t* __restrict__ off, int nj, int64_t total,
+                           const uint64_t* __restrict__ ukh, const uint8_t* __restrict__ ukl, int64_t nu,
+                           unsigned long long* __restrict__ jrem) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int c = seg_of(off, nj, i);
+  const int64_t k = i - off[c];
+  if (in_set(ukh, ukl, nu, jobs[c].khi[k], jobs[c].klo[k])) atomicAdd(&jrem[c], 1ull);
+}
+
+__global__ void k_rm_flag(const RmJob* __restrict__ jobs, const int64_t* __restrict__ off, int nj, int64_t total,
+                          const uint64_t* __restrict__ ukh, const uint8_t* __restrict__ ukl, int64_t nu,
+                          int32_t* __restrict__ keep) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int c = seg_of(off, nj, i);
+  const int64_t k = i - off[c];
+  keep[i] = in_set(ukh, ukl, nu, jobs[c].khi[k], jobs[c].klo[k]) ? 0 : 1;
+}
+
+__global__ __launch_bounds__(256) void k_rm_place(const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                                  int nj, int64_t total, const int32_t* __restrict__ keep,
+                                                  const int64_t* __restrict__ kx) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint8_t* srcp = nullptr;
+  uint8_t* dstp = nullptr;
+  if (i < total && keep[i]) {
+    const int c = seg_of(off, nj, i);
+    const RmJob J = jobs[c];
+    const int64_t k = i - off[c];
+    const int64_t pos = kx[i] - kx[off[c]];
+    J.okhi[pos] = J.khi[k];
+    J.oklo[pos] = J.klo[k];
+    srcp = J.rows + k * YRWI_ROW_BYTES;
+    dstp = J.orows + pos * YRWI_ROW_BYTES;
+  }
+  wave_move_rows(srcp, dstp);
+}
+
+unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// what the call enqueued (kernels, device-library calls, copies, memsets) and waited for
+struct Tally {
+  int32_t launches = 0, syncs = 0;
+};
+
+// n host rows -> d_rows through the lane's pinned staging, two pieces in turn; the stage
+// keeps `extra` bytes after the pieces for the call's table uploads (upload())
+int stage_rows(yrwi_ctx* ctx, Lane* L, const uint8_t* rows, size_t total, uint8_t* d_rows, size_t extra, Tally* T) {
+  const size_t piece = std::min((size_t)16 << 20, al256(total));
+  uint8_t* stg = stage_reserve(L, &L->stage, 2 * piece + extra, true);
+  if (!stg) return ctx->take(L, YRWI_E_HIP);
+  hipEvent_t done[2] = {L->event(), L->event()};
+  bool used[2] = {false, false};
+  for (size_t off = 0, k = 0; off < total; off += piece, k ^= 1) {
+    const size_t m = std::min(piece, total - off);
+    if (used[k]) {
+      HIPCHK(ctx, hipEventSynchronize(done[k]));
+      T->syncs++;
+    }
+    std::memcpy(stg + k * piece, rows + off, m);
+    HIPCHK(ctx, hipMemcpyAsync(d_rows + off, stg + k * piece, m, hipMemcpyHostToDevice, L->stream));
+    HIPCHK(ctx, hipEventRecord(done[k], L->stream));
+    used[k] = true;
+    T->launches++;
+  }
+  L->stage.used = 2 * piece;
+  return 0;
+}
+
+void put_stats(yrwi_update_stats* st, const yrwi_update_stats& S, const Tally& T) {
+  if (!st) return;
+  *st = S;
+  st->launches = T.launches;
+  st->syncs = T.syncs;
+}
+
+}  // namespace
+
+extern "C" int yrwi_add_postings(yrwi_ctx* ctx, const uint8_t* terms12, const uint8_t* rows40, int64_t n, int policy,
+                                 yrwi_update_stats* st) {
+  if (!ctx || n < 0 || (n > 0 && (!terms12 || !rows40))) return YRWI_E_ARG;
+  if (policy != YRWI_ADD_REPLACE && policy != YRWI_ADD_KEEP && policy != YRWI_ADD_RECENT)
+    return ctx->fail(YRWI_E_ARG, "unknown add policy");
+  if (n >= (int64_t)INT32_MAX) return ctx->fail(YRWI_E_ARG, "2^31 - 1 or more postings in one batch");
+  yrwi_update_stats S;
+  std::memset(&S, 0, sizeof(S));
+  Tally T;
+  if (st) std::memset(st, 0, sizeof(*st));
+  // ---- grouping: every row's term -> its job (host, O(n))
+  std::unordered_map<KeyT, int32_t, KeyHash> jobof;
+  std::vector<KeyT> jkey;
+  std::vector<int32_t> job((size_t)n);
+  std::vector<int64_t> bcnt;
+  for (int64_t i = 0; i < n; i++) {
+    KeyT tk;
+    if (!key_of(terms12 + i * 12, &tk)) return ctx->fail(YRWI_E_HASH, "term hash is not well-formed Base64");
+    auto ins = jobof.emplace(tk, (int32_t)jkey.size());
+    if (ins.second) {
+      jkey.push_back(tk);
+      bcnt.push_back(0);
+    }
+    job[(size_t)i] = ins.first->second;
+    bcnt[(size_t)ins.first->second]++;
+  }
+  hipSetDevice(ctx->device);
+  drain(ctx);  // in-flight batches read the list table
+  if (n == 0) return 0;
+  Lane* L = ctx->lanes[0];
+  if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
+  T.syncs++;
+  const int nj = (int)jkey.size();
+  std::vector<UpdJob> jobs((size_t)nj);
+  std::vector<const ListRec*> old((size_t)nj, nullptr);
+  for (int j = 0; j < nj; j++) {
+    UpdJob& J = jobs[(size_t)j];
+    std::memset(&J, 0, sizeof(J));
+    auto it = ctx->lists.find(jkey[(size_t)j]);
+    if (it != ctx->lists.end() && it->second.n > 0) {
+      old[(size_t)j] = &it->second;
+      J.akhi = it->second.khi;
+      J.aklo = it->second.klo;
+      J.arows = it->second.rows;
+      J.an = it->second.n;
+    }
+    J.boff = j ? jobs[(size_t)j - 1].boff + jobs[(size_t)j - 1].bn : 0;
+    J.bn = bcnt[(size_t)j];
+  }
+  // ---- scratch (lane arena)
+  uint8_t* d_rows = L->arena.alloc((size_t)n * 40);
+  uint64_t* khi = arena_alloc<uint64_t>(L, n);
+  uint8_t* klo = arena_alloc<uint8_t>(L, n);
+  int32_t* d_job = arena_alloc<int32_t>(L, n);
+  uint64_t* ka = arena_alloc<uint64_t>(L, n);
+  uint64_t* kb = arena_alloc<uint64_t>(L, n);
+  uint32_t* ia = arena_alloc<uint32_t>(L, n);
+  uint32_t* ib = arena_alloc<uint32_t>(L, n);
+  uint64_t* skh = arena_alloc<uint64_t>(L, n);
+  uint8_t* skl = arena_alloc<uint8_t>(L, n);
+  int32_t* sjob = arena_alloc<int32_t>(L, n);
+  int32_t* ins = arena_alloc<int32_t>(L, n + 1);
+  int64_t* insx = arena_alloc<int64_t>(L, n + 1);
+  uint8_t* rep = arena_alloc<uint8_t>(L, n);
+  int64_t* lbA = arena_alloc<int64_t>(L, n);
+  uint32_t* src = arena_alloc<uint32_t>(L, n);
+  UpdJob* d_jobs = arena_alloc<UpdJob>(L, nj);
+  int32_t* d_cj = arena_alloc<int32_t>(L, nj);
+  int64_t* d_aoff = arena_alloc<int64_t>(L, nj);
+  int64_t* res = arena_alloc<int64_t>(L, 1 + 2 * (int64_t)nj);  // validation bits, then (new, replacing) per job
+  if (!d_rows || !khi || !klo || !d_job || !ka || !kb || !ia || !ib || !skh || !skl || !sjob || !ins || !insx ||
+      !rep || !lbA || !src || !d_jobs || !d_cj || !d_aoff || !res)
+    return ctx->fail(YRWI_E_NOMEM, "device allocation (add_postings)");
+  int jbits = 1;
+  while (((int64_t)1 << jbits) < nj) jbits++;
+  const int ni = (int)n;
+  size_t t1 = 0, t2 = 0, t3 = 0;
+  HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, t1, ka, kb, ia, ib, ni, 0, 64, L->stream));
+  HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, t2, kb, ka, ib, ia, ni, 0, 8 + jbits, L->stream));
+  HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t3, ins, insx, ni + 1, L->stream));
+  const size_t tmpb = std::max(t1, std::max(t2, t3));
+  void* tmp = L->arena.alloc(tmpb);
+  if (!tmp) return ctx->fail(YRWI_E_NOMEM, "device allocation (add_postings sort)");
+  // ---- upload, key and validate (the sortedness bit means nothing for a batch)
+  const size_t extra = al256((size_t)n * 4) + 2 * al256((size_t)nj * sizeof(UpdJob)) + al256((size_t)nj * 4) +
+                       al256((size_t)nj * 8) + 4096;
+  if (int rc = stage_rows(ctx, L, rows40, (size_t)n * 40, d_rows, extra, &T)) return rc;
+  if (int rc = upload(L, d_job, job, d_jobs, jobs)) return ctx->take(L, rc);
+  HIPCHK(ctx, hipMemsetAsync(res, 0, (size_t)(1 + 2 * (int64_t)nj) * 8, L->stream));
+  HIPCHK(ctx, hipMemsetAsync(ins + n, 0, 4, L->stream));
+  T.launches += 3;
+  if (launch_validate_rows(d_rows, n, khi, klo, reinterpret_cast<int32_t*>(res), L->stream))
+    return ctx->fail(YRWI_E_HIP, "validate launch");
+  // ---- sort by (job, url key, arrival)
+  hipLaunchKernelGGL(k_upd_key_a, dim3(blocks(n)), dim3(256), 0, L->stream, khi, klo, n, ka, ia);
+  HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairs(tmp, t1, ka, kb, ia, ib, ni, 0, 64, L->stream));
+  hipLaunchKernelGGL(k_upd_key_b, dim3(blocks(n)), dim3(256), 0, L->stream, khi, d_job, ib, n, kb);
+  HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairs(tmp, t2, kb, ka, ib, ia, ni, 0, 8 + jbits, L->stream));
+  const uint32_t* perm = ia;
+  hipLaunchKernelGGL(k_upd_gather, dim3(blocks(n)), dim3(256), 0, L->stream, khi, klo, d_job, perm, n, skh, skl, sjob);
+  // ---- winners, lower bounds, one scan, one read-back
+  hipLaunchKernelGGL(k_upd_pick, dim3(blocks(n)), dim3(256), 0, L->stream, d_jobs, d_rows, perm, skh, skl, sjob, n,
+                     policy, ins, rep, lbA, src, reinterpret_cast<unsigned long long*>(res + 1));
+  HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(tmp, t3, ins, insx, ni + 1, L->stream));
+  HIPCHK(ctx, hipGetLastError());
+  T.launches += 8;
+  const int64_t* hres =
+      reinterpret_cast<const int64_t*>(readback(L, &L->down_stage, res, 1 + 2 * (int64_t)nj, 8, 8));
+  if (!hres) return ctx->take(L, YRWI_E_HIP);
+  T.launches++;
+  HIPCHK(ctx, lane_sync(L));
+  T.syncs++;
+  const int32_t herr = (int32_t)hres[0];
+  if (herr & 1) return ctx->fail(YRWI_E_HASH, "url hash is not well-formed Base64");
+  if (herr & 2) return ctx->fail(YRWI_E_NULL_LANGUAGE, "row with empty language cell (reference NPE)");
+  // ---- one allocation round from index memory
+  std::vector<int32_t> cj;
+  std::vector<int64_t> aoff;
+  int64_t atotal = 0;
+  for (int j = 0; j < nj; j++) {
+    const int64_t add = hres[1 + 2 * j], rp = hres[2 + 2 * j];
+    S.added += add;
+    S.replaced += rp;
+    if (jobs[(size_t)j].an + add > MAX_LIST)
+      return ctx->fail(YRWI_E_LIMIT, "list longer than 53,687,091 rows (RowSet.importRowSet)");
+    if (add + rp == 0) continue;
+    cj.push_back(j);
+    aoff.push_back(atotal);
+    atotal += jobs[(size_t)j].an;
+  }
+  S.dropped = n - S.added - S.replaced;
+  if (cj.empty()) {  // every posting lost to an existing row
+    put_stats(st, S, T);
+    return 0;
+  }
+  for (int32_t j : cj) {
+    UpdJob& J = jobs[(size_t)j];
+    const size_t nn = (size_t)(J.an + hres[1 + 2 * j]);
+    J.orows = ctx->index_mem.alloc(nn * 40);
+    J.okhi = reinterpret_cast<uint64_t*>(ctx->index_mem.alloc(nn * 8));
+    J.oklo = ctx->index_mem.alloc(nn);
+    if (!J.orows || !J.okhi || !J.oklo) return ctx->fail(YRWI_E_NOMEM, "device index allocation failed");
+  }
+  // ---- place the old rows, then the batch's
+  if (int rc = upload(L, d_jobs, jobs, d_cj, cj, d_aoff, aoff)) return ctx->take(L, rc);
+  T.launches++;
+  if (atotal > 0) {
+    hipLaunchKernelGGL(k_upd_old, dim3(blocks(atotal)), dim3(256), 0, L->stream, d_jobs, d_cj, d_aoff, (int)cj.size(),
+                       atotal, skh, skl, insx, rep);
+    T.launches++;
+  }
+  hipLaunchKernelGGL(k_upd_new, dim3(blocks(n)), dim3(256), 0, L->stream, d_jobs, d_rows, n, skh, skl, sjob, ins, rep,
+                     insx, lbA, src);
+  T.launches++;
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, lane_sync(L));
+  T.syncs++;
+  // ---- bookkeeping: a pure add charges no dictionary churn (no key left a list)
+  for (int32_t j : cj) {
+    const UpdJob& J = jobs[(size_t)j];
+    ListRec R;
+    R.khi = J.okhi;
+    R.klo = J.oklo;
+    R.rows = J.orows;
+    R.n = J.an + hres[1 + 2 * j];
+    ctx->npostings += R.n - J.an;
+    if (!old[(size_t)j]) S.new_terms++;
+    ctx->lists[jkey[(size_t)j]] = R;
+    index_changed(ctx, jkey[(size_t)j], 0, true);
+    S.terms++;
+  }
+  put_stats(st, S, T);
+  return 0;
+}
+
+extern "C" int yrwi_remove_postings(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uint8_t* urls12,
+                                    int64_t nurls, yrwi_update_stats* st) {
+  if (!ctx || nterms < 0 || nurls < 0 || (nterms > 0 && !terms12) || (nurls > 0 && !urls12)) return YRWI_E_ARG;
+  yrwi_update_stats S;
+  std::memset(&S, 0, sizeof(S));
+  Tally T;
+  if (st) std::memset(st, 0, sizeof(*st));
+  // ---- the url set, sorted and deduplicated; the named lists, each once
+  std::vector<KeyT> uk((size_t)nurls);
+  for (int64_t i = 0; i < nurls; i++)
+    if (!key_of(urls12 + i * 12, &uk[(size_t)i])) return ctx->fail(YRWI_E_HASH, "url hash is not well-formed Base64");
+  std::sort(uk.begin(), uk.end());
+  uk.erase(std::unique(uk.begin(), uk.end()), uk.end());
+  std::vector<KeyT> tks;
+  {
+    std::unordered_set<KeyT, KeyHash> seen;
+    for (int32_t i = 0; i < nterms; i++) {
+      KeyT tk;
+      if (!key_of(terms12 + (size_t)i * 12, &tk)) return ctx->fail(YRWI_E_HASH, "term hash is not well-formed Base64");
+      if (seen.insert(tk).second) tks.push_back(tk);
+    }
+  }
+  hipSetDevice(ctx->device);
+  drain(ctx);
+  std::vector<KeyT> jkey;
+  std::vector<RmJob> jobs;
+  std::vector<int64_t> off;
+  int64_t total = 0;
+  auto take = [&](const KeyT& tk, const ListRec& R) {
+    if (R.n == 0) return;
+    jkey.push_back(tk);
+    jobs.push_back(RmJob{R.khi, R.klo, R.rows, R.n, nullptr, nullptr, nullptr});
+    off.push_back(total);
+    total += R.n;
+  };
+  if (nterms == 0) {
+    for (auto& kv : ctx->lists) take(kv.first, kv.second);
+  } else {
+    for (const KeyT& tk : tks) {
+      auto it = ctx->lists.find(tk);
+      if (it != ctx->lists.end()) take(tk, it->second);
+    }
+  }
+  if (uk.empty() || jobs.empty()) return 0;
+  Lane* L = ctx->lanes[0];
+  if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
+  T.syncs++;
+  const int nj = (int)jobs.size();
+  const int64_t nu = (int64_t)uk.size();
+  std::vector<uint64_t> h_ukh((size_t)nu);
+  std::vector<uint8_t> h_ukl((size_t)nu);
+  for (int64_t i = 0; i < nu; i++) {
+    h_ukh[(size_t)i] = uk[(size_t)i].hi;
+    h_ukl[(size_t)i] = (uint8_t)uk[(size_t)i].lo;
+  }
+  uint64_t* ukh = arena_alloc<uint64_t>(L, nu);
+  uint8_t* ukl = arena_alloc<uint8_t>(L, nu);
+  RmJob* d_jobs = arena_alloc<RmJob>(L, nj);
+  int64_t* d_off = arena_alloc<int64_t>(L, nj);
+  unsigned long long* jrem = arena_alloc<unsigned long long>(L, nj);
+  if (!ukh || !ukl || !d_jobs || !d_off || !jrem) return ctx->fail(YRWI_E_NOMEM, "device allocation (remove_postings)");
+  // ---- one marking pass over the named lists' keys, the per-list counts read back once
+  if (int rc = upload(L, ukh, h_ukh, ukl, h_ukl, d_jobs, jobs, d_off, off)) return ctx->take(L, rc);
+  HIPCHK(ctx, hipMemsetAsync(jrem, 0, (size_t)nj * 8, L->stream));
+  hipLaunchKernelGGL(k_rm_count, dim3(blocks(total)), dim3(256), 0, L->stream, d_jobs, d_off, nj, total, ukh, ukl, nu,
+                     jrem);
+  HIPCHK(ctx, hipGetLastError());
+  const int64_t* hrem = reinterpret_cast<const int64_t*>(readback(L, &L->down_stage, jrem, nj, 8, 8));
+  if (!hrem) return ctx->take(L, YRWI_E_HIP);
+  T.launches += 4;
+  HIPCHK(ctx, lane_sync(L));
+  T.syncs++;
+  // ---- compaction of only the lists that lost rows (an emptied list needs none)
+  std::vector<int> lose;
+  std::vector<RmJob> cjobs;
+  std::vector<int64_t> coff;
+  std::vector<int64_t> rem((size_t)nj);
+  int64_t ctotal = 0;
+  for (int j = 0; j < nj; j++) {
+    rem[(size_t)j] = hrem[j];  // (the pinned landing buffer is reused below)
+    if (rem[(size_t)j] == 0) continue;
+    lose.push_back(j);
+    if (rem[(size_t)j] == jobs[(size_t)j].n) continue;
+    RmJob J = jobs[(size_t)j];
+    const size_t nn = (size_t)(J.n - rem[(size_t)j]);
+    J.orows = ctx->index_mem.alloc(nn * 40);
+    J.okhi = reinterpret_cast<uint64_t*>(ctx->index_mem.alloc(nn * 8));
+    J.oklo = ctx->index_mem.alloc(nn);
+    if (!J.orows || !J.okhi || !J.oklo) return ctx->fail(YRWI_E_NOMEM, "device index allocation failed");
+    jobs[(size_t)j] = J;
+    cjobs.push_back(J);
+    coff.push_back(ctotal);
+    ctotal += J.n;
+  }
+  if (lose.empty()) {
+    put_stats(st, S, T);
+    return 0;
+  }
+  if (!cjobs.empty()) {
+    if (ctotal > (int64_t)INT32_MAX - 1) return ctx->fail(YRWI_E_LIMIT, "more than 2^31 postings in the lists to compact");
+    const int ncj = (int)cjobs.size();
+    RmJob* d_cjobs = arena_alloc<RmJob>(L, ncj);
+    int64_t* d_coff = arena_alloc<int64_t>(L, ncj);
+    int32_t* keep = arena_alloc<int32_t>(L, ctotal + 1);
+    int64_t* kx = arena_alloc<int64_t>(L, ctotal + 1);
+    size_t tb = 0;
+    HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, keep, kx, (int)(ctotal + 1), L->stream));
+    void* tmp = L->arena.alloc(tb);
+    if (!d_cjobs || !d_coff || !keep || !kx || !tmp)
+      return ctx->fail(YRWI_E_NOMEM, "device allocation (remove_postings compaction)");
+    if (int rc = upload(L, d_cjobs, cjobs, d_coff, coff)) return ctx->take(L, rc);
+    HIPCHK(ctx, hipMemsetAsync(keep + ctotal, 0, 4, L->stream));
+    hipLaunchKernelGGL(k_rm_flag, dim3(blocks(ctotal)), dim3(256), 0, L->stream, d_cjobs, d_coff, ncj, ctotal, ukh, ukl,
+                       nu, keep);
+    HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(tmp, tb, keep, kx, (int)(ctotal + 1), L->stream));
+    hipLaunchKernelGGL(k_rm_place, dim3(blocks(ctotal)), dim3(256), 0, L->stream, d_cjobs, d_coff, ncj, ctotal, keep,
+                       kx);
+    HIPCHK(ctx, hipGetLastError());
+    T.launches += 5;
+    HIPCHK(ctx, lane_sync(L));
+    T.syncs++;
+  }
+  // ---- bookkeeping: the removed postings are the dictionary churn
+  for (int j : lose) {
+    const RmJob& J = jobs[(size_t)j];
+    auto it = ctx->lists.find(jkey[(size_t)j]);
+    S.removed += rem[(size_t)j];
+    S.terms++;
+    ctx->npostings -= rem[(size_t)j];
+    if (rem[(size_t)j] == J.n) {  // as yrwi_put_list(n = 0) leaves things
+      index_changed(ctx, jkey[(size_t)j], J.n, false);
+      ctx->lists.erase(it);
+      S.emptied_terms++;
+    } else {
+      ListRec R;
+      R.khi = J.okhi;
+      R.klo = J.oklo;
+      R.rows = J.orows;
+      R.n = J.n - rem[(size_t)j];
+      it->second = R;
+      index_changed(ctx, jkey[(size_t)j], rem[(size_t)j], true);
+    }
+  }
+  put_stats(st, S, T);
+  return 0;
+}

@@ -302,6 +302,38 @@ class RWIIndex:
         rows = np.ascontiguousarray(rows, dtype=np.uint8).reshape(-1, 40)
         _check(self._h, _lib.lib().yrwi_put_list(self._h, bytes(term), rows.ctypes.data, len(rows), 1 if sorted else 0))
 
+    def add_postings(self, terms: Sequence[bytes], rows: np.ndarray, policy: str = "replace") -> dict:
+        """IndexCell.add in bulk (yrwi_add_postings): posting i, rows[i], goes into the list of
+        terms[i]; only the batch crosses to the device.  policy: "replace" (RowSet.put: the
+        newest of a (term, url) pair stays), "keep" (RowSet.mergeEnum: the first stays) or
+        "recent" (ReferenceContainer.putAllRecent: the newest unless its lastModified is
+        smaller).  Returns the call's yrwi_update_stats as a dict."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint8).reshape(-1, 40)
+        if isinstance(terms, np.ndarray):
+            tb = np.ascontiguousarray(terms, dtype=np.uint8).reshape(-1, 12)
+        else:
+            tb = np.frombuffer(_hashes(terms), dtype=np.uint8).reshape(-1, 12)
+        if len(tb) != len(rows):
+            raise ValueError("one term hash per posting")
+        st = _lib.CUpdateStats()
+        _check(self._h, _lib.lib().yrwi_add_postings(self._h, tb.ctypes.data, rows.ctypes.data, len(rows),
+                                                     _lib.ADD_POLICIES[policy], ctypes.byref(st)))
+        return {f: getattr(st, f) for f, _ in _lib.CUpdateStats._fields_}
+
+    def remove_postings(self, urls: Sequence[bytes], terms: Optional[Sequence[bytes]] = None) -> dict:
+        """IndexCell.remove(termHash, urlHashes) for every term of `terms`, or with terms=None
+        Segment.removeAllUrlReferences over every list (yrwi_remove_postings).  Returns the
+        call's yrwi_update_stats as a dict ("removed": rows removed)."""
+        ub = np.frombuffer(_hashes(urls), dtype=np.uint8)
+        tb = np.frombuffer(_hashes(terms or ()), dtype=np.uint8)
+        if terms is not None and len(terms) == 0:
+            return {f: 0 for f, _ in _lib.CUpdateStats._fields_}  # no term named: nothing to do
+        st = _lib.CUpdateStats()
+        _check(self._h, _lib.lib().yrwi_remove_postings(self._h, tb.ctypes.data if len(tb) else None, len(tb) // 12,
+                                                        ub.ctypes.data if len(ub) else None, len(ub) // 12,
+                                                        ctypes.byref(st)))
+        return {f: getattr(st, f) for f, _ in _lib.CUpdateStats._fields_}
+
     def load_heaps(self, paths: Sequence[str], order_by_name: bool = False) -> "_lib.CLoadStats":
         """Load YaCy BLOB heap files (IndexCell's ReferenceContainerArray) into the index;
         lists already present act as the RAM cache (the files' rows win)."""
