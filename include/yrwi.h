@@ -43,7 +43,8 @@ enum {
                                 ASCII.getBytes(null) (WordReferenceVars.java:315, ReferenceOrder.java:260) */
   YRWI_E_UNSUPPORTED = -8,
   YRWI_E_LIMIT = -9,         /* list longer than 53,687,091 rows (RowSet.java:90-92) */
-  YRWI_E_CAPACITY = -10      /* search event tables full (max_postings given to yrwi_event_open too small) */
+  YRWI_E_CAPACITY = -10,     /* search event tables full (max_postings given to yrwi_event_open too small) */
+  YRWI_E_IO = -11            /* file could not be created, written or renamed */
 };
 
 typedef struct yrwi_ctx yrwi_ctx;
@@ -330,6 +331,47 @@ typedef struct yrwi_load_stats {
 } yrwi_load_stats;
 int yrwi_load_heaps(yrwi_ctx* ctx, const char* const* paths, int32_t npaths, int32_t flags,
                     yrwi_load_stats* st);
+
+/* Two cells of the 14-byte export header that yrwi_dump_heap writes are UNVERIFIED against the
+ * reference source (written from memory; no reader here or, per SURVEY.md §8f.1, in the reference
+ * depends on either):
+ *   - orderkey: the two bytes "Be", Base64Order.enhancedCoder.signature();
+ *   - lastread / lastwrote: whole days from 2000-01-01T00:00:00Z to the call's time. */
+#define YRWI_DUMP_ORDERKEY0 'B'
+#define YRWI_DUMP_ORDERKEY1 'e'
+#define YRWI_DUMP_EPOCH_MS 946684800000LL /* 2000-01-01T00:00:00Z in ms since 1970 */
+typedef struct yrwi_dump_stats {
+  int64_t terms, postings;  /* records written, rows in them */
+  int64_t bytes;            /* file size */
+  int64_t windows;          /* windows of the file image packed on the device */
+  int32_t launches;         /* kernel launches, copies and memsets enqueued: a function of bytes and the
+                               window size, never of the number of terms */
+  int32_t syncs;            /* host waits on the device: a function of the number of windows only */
+  int64_t t_pack_ns;        /* device time of the pack kernels (HIP events) */
+  int64_t t_total_ns;
+} yrwi_dump_stats;
+/* ReferenceContainerCache.dump / the FlushThread dump of IndexCell (IndexCell.java:131-166) through
+ * HeapWriter.add (HeapWriter.java:114-124) and RowCollection.exportCollection (:209-224): writes the
+ * context's lists to one BLOB heap file that yrwi_load_heaps (and a stock HeapReader) reads back.
+ * nterms == 0: every list; otherwise the named lists (duplicates count once, unknown terms are
+ * ignored; an ill-formed term: YRWI_E_HASH, nothing written).  The file is the concatenation, in
+ * Base64Order of the term hashes, of one record per non-empty list:
+ *   [int32 BE reclen = 12 + 14 + 40 n][12-B term hash][export header][n rows of 40 B as stored],
+ * export header = size n (int32 BE), lastread and lastwrote (int16 BE: days from 2000-01-01 to
+ * now_ms; now_ms == 0: now), orderkey "Be", orderbound n (int32 BE).  No lists or an empty
+ * selection: a 0-byte file.  The .idx / .gap companions are not written (HeapReader rebuilds its
+ * index by scanning the file).  The bytes go to <path>.prt, renamed onto `path` after the last
+ * byte is written and flushed; on any failure the temporary file is removed and an existing
+ * `path` is untouched (file errors: YRWI_E_IO, strerror text in yrwi_last_error).
+ * The file image is packed on the device in windows of YRWI_DUMP_WINDOW bytes (environment, read
+ * per call, rounded down to a multiple of 256, at least 256, at most 1 GiB; default 32 MiB); extra
+ * device memory is two windows and the job table, whatever the index size.  The call waits for the
+ * batches in flight, as yrwi_get_list does, and changes nothing in the context.  A sharded context
+ * writes the lists it holds, i.e. its url-hash range of every term: no collective is involved,
+ * the shards' files cover disjoint url ranges and loaded together give the whole index.
+ * st may be NULL. */
+int yrwi_dump_heap(yrwi_ctx* ctx, const char* path, const uint8_t* terms12, int32_t nterms,
+                   int64_t now_ms, yrwi_dump_stats* st);
 
 /* ---- query hot path ---- */
 /* TermSearch + joinExcludeContainers + normalizeWith + cardinal + rwiStack top-k

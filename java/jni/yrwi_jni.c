@@ -265,6 +265,30 @@ JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_loadHeaps(JNIEnv*
   return res;
 }
 
+/* The IndexCell dump (FlushThread, IndexCell.java:131-166): yrwi_dump_heap; terms: nterms * 12
+ * bytes (nterms == 0: every list); returns the stats as long[8] {terms, postings, bytes, windows,
+ * launches, syncs, t_pack_ns, t_total_ns}, NULL when the call failed. */
+JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_dumpHeap(JNIEnv* env, jclass c, jlong ctx,
+                                                                       jstring path, jbyteArray terms, jint nterms,
+                                                                       jlong nowMs) {
+  uint8_t* t = copy_in(env, terms, (int64_t)nterms * 12);
+  if (!t) return NULL;
+  const char* p = (*env)->GetStringUTFChars(env, path, NULL);
+  if (!p) {
+    free(t);
+    return NULL;
+  }
+  yrwi_dump_stats st;
+  int rc = yrwi_dump_heap((yrwi_ctx*)(intptr_t)ctx, p, t, nterms, nowMs, &st);
+  (*env)->ReleaseStringUTFChars(env, path, p);
+  free(t);
+  if (rc != 0) return NULL;
+  const jlong v[8] = {st.terms, st.postings, st.bytes, st.windows, st.launches, st.syncs, st.t_pack_ns, st.t_total_ns};
+  jlongArray res = (*env)->NewLongArray(env, 8);
+  if (res) (*env)->SetLongArrayRegion(env, res, 0, 8, v);
+  return res;
+}
+
 /* SearchEvent.addRWIs constraints + pullOneRWI(skipDoubleDom): query with a yrwi_filter.
  * constraint: 4 Bitfield bytes or null; site / altSite: 6-byte host hashes or null;
  * siteExcludes: n*6 bytes; urlHashes: n*12 bytes; flagCount: int[32] out or null. */

@@ -12,6 +12,7 @@
 //   search/query/SearchEvent.java:612-631      -> GpuRWI.query(...) (whole local RWI path)
 //   search/query/SearchEvent.java:736-806,1297 -> GpuRWI.queryFiltered(...) (constraints, doubledom)
 //   kelondro/rwi/IndexCell.java:353-386        -> GpuRWI.loadHeaps(...) (BLOB heaps into HBM)
+//   kelondro/rwi/IndexCell.java:131-166        -> GpuRWI.dumpHeap(...) (the FlushThread dump: HBM into a BLOB heap)
 //
 // Java level: 1.8, YaCy's own (build.properties javacSource/javacTarget, pom.xml
 // maven.compiler.source/target).  No API newer than Java 8 is used here or in the
@@ -194,6 +195,20 @@ public final class GpuRWI implements AutoCloseable {
         return loadHeaps(this.ctx, heapFiles, orderByFileName ? 1 : 0);
     }
 
+    /** The FlushThread dump of IndexCell (IndexCell.java:131-166 through HeapWriter.add and
+     *  RowCollection.exportCollection; yrwi_dump_heap): the lists of `terms`, or with terms == null or
+     *  empty every list, written to one BLOB heap file in term-hash order; the file appears under
+     *  `path` only when complete (written to path + ".prt", then renamed).  Name it
+     *  prefix.yyyyMMddHHmmssSSS.blob for ArrayStack and loadHeaps(..., orderByFileName).  nowMs: the
+     *  time for the export header's day cells (0: now).  Returns {terms, postings, bytes, windows,
+     *  launches, syncs, packNanos, totalNanos}. */
+    public synchronized long[] dumpHeap(final String path, final byte[][] terms, final long nowMs) {
+        final int nterms = terms == null ? 0 : terms.length;
+        final long[] st = dumpHeap(this.ctx, path, nterms == 0 ? new byte[0] : flatten(terms), nterms, nowMs);
+        if (st == null) throw new IllegalStateException("yrwi_dump_heap failed");
+        return st;
+    }
+
     /** query(...) under SearchEvent.addRWIs constraints (SearchEvent.java:736-806) and,
      *  with skipDoubleDom, in pullOneRWI order (:1297-1394).  flagCount (int[32] or null)
      *  receives SearchEvent.flagcount. */
@@ -371,6 +386,7 @@ public final class GpuRWI implements AutoCloseable {
     private static native byte[] query(long ctx, byte[] incl, int nincl, byte[] excl, int nexcl, int maxDistance,
                                        int k, int[] profile32, String language, long nowMillis, long[] stats);
     private static native long[] loadHeaps(long ctx, String[] paths, int byName);
+    private static native long[] dumpHeap(long ctx, String path, byte[] terms, int nterms, long nowMs);
     private static native byte[] queryFiltered(long ctx, byte[] incl, int nincl, byte[] excl, int nexcl,
                                                int maxDistance, int k, int[] profile32, String language,
                                                long nowMillis, byte[] constraint, boolean allOf, int contentdom,

@@ -25,8 +25,9 @@ PROFILE_FIELDS = [
 ERRORS = {
     -1: "YRWI_E_ARG", -2: "YRWI_E_HASH", -3: "YRWI_E_UNSORTED", -4: "YRWI_E_HIP",
     -5: "YRWI_E_NOMEM", -6: "YRWI_E_RCCL", -7: "YRWI_E_NULL_LANGUAGE", -8: "YRWI_E_UNSUPPORTED",
-    -9: "YRWI_E_LIMIT",
+    -9: "YRWI_E_LIMIT", -10: "YRWI_E_CAPACITY", -11: "YRWI_E_IO",
 }
+E_IO = -11
 
 
 class CProfile(ctypes.Structure):
@@ -128,6 +129,15 @@ class CUpdateStats(ctypes.Structure):
 ADD_POLICIES = {"replace": 0, "keep": 1, "recent": 2}
 
 
+DUMP_WINDOW_DEFAULT = 32 << 20  # yrwi_dump_heap's window without YRWI_DUMP_WINDOW (bytes)
+
+
+class CDumpStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("terms", "postings", "bytes", "windows")] + \
+        [("launches", ctypes.c_int32), ("syncs", ctypes.c_int32), ("t_pack_ns", ctypes.c_int64),
+         ("t_total_ns", ctypes.c_int64)]
+
+
 # every symbol include/yrwi.h declares, with its ctypes signature
 _VP = ctypes.c_void_p
 SIGNATURES = {
@@ -166,6 +176,8 @@ SIGNATURES = {
     "yrwi_host_free": (ctypes.c_int, [_VP, _VP]),
     "yrwi_load_heaps": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32, ctypes.c_int32,
                                        ctypes.POINTER(CLoadStats)]),
+    "yrwi_dump_heap": (ctypes.c_int, [_VP, ctypes.c_char_p, _VP, ctypes.c_int32, ctypes.c_int64,
+                                      ctypes.POINTER(CDumpStats)]),
     "yrwi_score_nodes": (ctypes.c_int, [_VP, ctypes.POINTER(CNode), ctypes.c_int64, ctypes.POINTER(CProfile),
                                         ctypes.c_char_p, ctypes.c_int32, _VP]),
     "yrwi_event_open": (ctypes.c_int, [_VP, ctypes.POINTER(CProfile), ctypes.c_char_p, ctypes.c_int64,

@@ -394,6 +394,8 @@ extern "C" void yrwi_close(yrwi_ctx* ctx) {
   ctx->devx = nullptr;
   for (auto& b : ctx->ev_pool) hipFree(b.second);
   ctx->ev_pool.clear();
+  if (ctx->dump_dev) hipFree(ctx->dump_dev);
+  if (ctx->dump_host) hipHostFree(ctx->dump_host);
   if (ctx->host_key) hipFree(ctx->host_key);
   ctx->index_mem.release();
   if (ctx->uid_all) hipFree(ctx->uid_all);

@@ -446,6 +446,11 @@ struct CtxBase {
   std::recursive_mutex api_mu;
   std::mutex ev_pool_mu;
   std::vector<std::pair<size_t, void*>> ev_pool;
+  // yrwi_dump_heap (yrwi_dump.hip): two device and two pinned windows of dump_cap bytes each,
+  // allocated on the first dump and kept
+  uint8_t* dump_dev = nullptr;
+  uint8_t* dump_host = nullptr;
+  size_t dump_cap = 0;
 
   int fail(int code, const std::string& m) {
     err = m;

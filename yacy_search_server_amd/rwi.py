@@ -20,6 +20,7 @@ All posting work runs in libyrwi's HIP kernels; this module only marshals.
 from __future__ import annotations
 
 import ctypes
+import os
 from dataclasses import dataclass, field
 from typing import Iterable, List, Optional, Sequence, Tuple
 
@@ -342,6 +343,22 @@ class RWIIndex:
         _check(self._h, _lib.lib().yrwi_load_heaps(self._h, arr, len(paths), 1 if order_by_name else 0,
                                                    ctypes.byref(st)))
         return st
+
+    def dump_heap(self, path: str, terms: Optional[Sequence[bytes]] = None, now_ms: int = 0) -> dict:
+        """The IndexCell dump (yrwi_dump_heap): the lists of `terms`, or with terms=None every
+        list, written to one BLOB heap file at `path` in term-hash order, as load_heaps reads
+        it.  The file image is packed on the device window by window (YRWI_DUMP_WINDOW bytes);
+        the context is unchanged.  Returns the call's yrwi_dump_stats as a dict."""
+        st = _lib.CDumpStats()
+        if terms is not None and len(terms) == 0:  # no term named (nterms == 0 would mean every list)
+            with open(os.fspath(path) + ".prt", "wb"):
+                pass
+            os.replace(os.fspath(path) + ".prt", path)
+            return {f: 0 for f, _ in _lib.CDumpStats._fields_}
+        tb =np.frombuffer(_hashes(terms or ()), dtype=np.uint8)
+        _check(self._h, _lib.lib().yrwi_dump_heap(self._h, os.fsencode(path), tb.ctypes.data if len(tb) else None,
+                                                  len(tb) // 12, now_ms, ctypes.byref(st)))
+        return {f: getattr(st, f) for f, _ in _lib.CDumpStats._fields_}
 
     def build_url_ids(self) -> None:
         """Bring the url dictionary up to date now (else the next query does)."""
