@@ -396,6 +396,33 @@ int yrwi_query_batch_submit(yrwi_ctx* ctx, const yrwi_query_desc* q, int32_t nq,
                             yrwi_hit* out, int32_t* nout, yrwi_stats* st, int64_t* ticket);
 int yrwi_query_batch_wait(yrwi_ctx* ctx, int64_t ticket);
 
+/* The query path with the joined posting of every hit (SearchEvent.rwiStack holds the
+ * WordReferenceVars of the joined posting, which pullOneRWI hands to Fulltext.getMetadata,
+ * SearchEvent.java:1297-1394): out and nout are exactly what yrwi_query / yrwi_query_batch /
+ * yrwi_query_batch_submit return for the same batch, and rows40_out (nq * kmax * 40 bytes; one
+ * query: k rows) receives the 40-byte row of hit i of query q at rows40_out + (q * kmax + i) * 40,
+ * i < nout[q]; the bytes past a query's nout[q] rows are unspecified.  The row is the one
+ * yrwi_term_search writes for the hit's url under the same descriptor: one include term, the
+ * list's row as stored (typeofword, reserve and freshUntil included); two or more, the joined
+ * record as toRowEntry re-encodes it (typeofword and reserve 0, freshUntil from the query's
+ * now_ms).  Filters, the doubledom pull order, urlselection, max_distance and exclusions decide
+ * which hits there are and their order, never a row's bytes.  rows40_out == NULL: the call is
+ * its counterpart without rows.  The rows go where the hits go: straight into rows40_out when it
+ * came from yrwi_host_alloc and is 8-byte aligned, else through the lane's landing buffer; like
+ * out it must stay valid until yrwi_query_batch_wait returns (submit).
+ * Sharded contexts (yrwi_open_shard): every rank ends with the same hits; a rank writes the rows
+ * of the hits whose url hash lies in its own range -- the first character's index c with
+ * c >> (6 - log2(world)) == rank (Distribution.java:153-158) -- and 40 zero bytes for the hits
+ * another rank owns.  No collective is added: the ranks' rows are disjoint and together give the
+ * row of every hit. */
+int yrwi_query_rows(yrwi_ctx* ctx, const yrwi_query_desc* q, yrwi_hit* out, uint8_t* rows40_out, int32_t* nout,
+                    yrwi_stats* st);
+int yrwi_query_batch_rows(yrwi_ctx* ctx, const yrwi_query_desc* q, int32_t nq, int32_t kmax, yrwi_hit* out,
+                          uint8_t* rows40_out, int32_t* nout, yrwi_stats* st);
+/* collected with yrwi_query_batch_wait */
+int yrwi_query_batch_rows_submit(yrwi_ctx* ctx, const yrwi_query_desc* q, int32_t nq, int32_t kmax, yrwi_hit* out,
+                                 uint8_t* rows40_out, int32_t* nout, yrwi_stats* st, int64_t* ticket);
+
 /* Pinned host memory for result buffers: hits written into such a buffer come
  * straight from the GPU (no staging copy).  Free with yrwi_host_free. */
 int yrwi_host_alloc(yrwi_ctx* ctx, size_t bytes, void** p);

@@ -292,11 +292,12 @@ JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_dumpHeap(JNIEnv* 
 /* SearchEvent.addRWIs constraints + pullOneRWI(skipDoubleDom): query with a yrwi_filter.
  * constraint: 4 Bitfield bytes or null; site / altSite: 6-byte host hashes or null;
  * siteExcludes: n*6 bytes; urlHashes: n*12 bytes; flagCount: int[32] out or null. */
-JNIEXPORT jbyteArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_queryFiltered(
-    JNIEnv* env, jclass c, jlong ctx, jbyteArray incl, jint nincl, jbyteArray excl, jint nexcl, jint maxd, jint k,
+/* rows_out != NULL: yrwi_query_rows, *rows_out = the hits' 40-byte rows (n * 40 bytes, hit order) */
+static jbyteArray query_filtered(
+    JNIEnv* env, jlong ctx, jbyteArray incl, jint nincl, jbyteArray excl, jint nexcl, jint maxd, jint k,
     jintArray prof, jstring lang, jlong now, jbyteArray constraint, jboolean allOf, jint contentdom,
     jboolean strictDom, jstring modLang, jbyteArray site, jbyteArray altSite, jbyteArray siteExcludes,
-    jbyteArray urlHashes, jboolean skipDoubleDom, jintArray flagCount) {
+    jbyteArray urlHashes, jboolean skipDoubleDom, jintArray flagCount, jbyteArray* rows_out) {
   yrwi_profile p;
   to_profile(env, prof, &p);
   yrwi_filter f;
@@ -331,8 +332,10 @@ JNIEXPORT jbyteArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_queryFiltered(
   q.max_distance = maxd; q.k = k; q.profile = &p; q.now_ms = now; q.filter = &f;
   strncpy(q.language, l, sizeof(q.language) - 1);
   yrwi_hit* hits = (yrwi_hit*)malloc(sizeof(yrwi_hit) * (size_t)(k > 0 ? k : 1));
+  uint8_t* rows = rows_out ? (uint8_t*)malloc((size_t)YRWI_ROW_BYTES * (size_t)(k > 0 ? k : 1)) : NULL;
   int32_t n = 0;
-  int rc = yrwi_query((yrwi_ctx*)(intptr_t)ctx, &q, hits, &n, NULL);
+  int rc = !hits || (rows_out && !rows) ? YRWI_E_NOMEM
+                                        : yrwi_query_rows((yrwi_ctx*)(intptr_t)ctx, &q, hits, rows, &n, NULL);
   (*env)->ReleaseByteArrayElements(env, incl, ib, JNI_ABORT);
   (*env)->ReleaseByteArrayElements(env, excl, eb, JNI_ABORT);
   if (sx) (*env)->ReleaseByteArrayElements(env, siteExcludes, sx, JNI_ABORT);
@@ -342,9 +345,44 @@ JNIEXPORT jbyteArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_queryFiltered(
   if (rc == 0) {
     if (flagCount) (*env)->SetIntArrayRegion(env, flagCount, 0, 32, (const jint*)fc);
     res = (*env)->NewByteArray(env, (jsize)(n * (jint)sizeof(yrwi_hit)));
-    (*env)->SetByteArrayRegion(env, res, 0, (jsize)(n * (jint)sizeof(yrwi_hit)), (const jbyte*)hits);
+    if (res) (*env)->SetByteArrayRegion(env, res, 0, (jsize)(n * (jint)sizeof(yrwi_hit)), (const jbyte*)hits);
+    if (res && rows_out) {
+      *rows_out = (*env)->NewByteArray(env, (jsize)(n * YRWI_ROW_BYTES));
+      if (*rows_out) (*env)->SetByteArrayRegion(env, *rows_out, 0, (jsize)(n * YRWI_ROW_BYTES), (const jbyte*)rows);
+      else res = NULL;
+    }
   }
   free(hits);
+  free(rows);
+  return res;
+}
+
+JNIEXPORT jbyteArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_queryFiltered(
+    JNIEnv* env, jclass c, jlong ctx, jbyteArray incl, jint nincl, jbyteArray excl, jint nexcl, jint maxd, jint k,
+    jintArray prof, jstring lang, jlong now, jbyteArray constraint, jboolean allOf, jint contentdom,
+    jboolean strictDom, jstring modLang, jbyteArray site, jbyteArray altSite, jbyteArray siteExcludes,
+    jbyteArray urlHashes, jboolean skipDoubleDom, jintArray flagCount) {
+  return query_filtered(env, ctx, incl, nincl, excl, nexcl, maxd, k, prof, lang, now, constraint, allOf, contentdom,
+                        strictDom, modLang, site, altSite, siteExcludes, urlHashes, skipDoubleDom, flagCount, NULL);
+}
+
+/* queryFiltered with the joined posting of every hit (yrwi_query_rows): byte[2][] = {the hits
+ * (n * 24 bytes), their 40-byte WordReferenceRow rows (n * 40 bytes, hit order)}; NULL on failure. */
+JNIEXPORT jobjectArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_queryRows(
+    JNIEnv* env, jclass c, jlong ctx, jbyteArray incl, jint nincl, jbyteArray excl, jint nexcl, jint maxd, jint k,
+    jintArray prof, jstring lang, jlong now, jbyteArray constraint, jboolean allOf, jint contentdom,
+    jboolean strictDom, jstring modLang, jbyteArray site, jbyteArray altSite, jbyteArray siteExcludes,
+    jbyteArray urlHashes, jboolean skipDoubleDom, jintArray flagCount) {
+  jbyteArray rows = NULL;
+  jbyteArray hits = query_filtered(env, ctx, incl, nincl, excl, nexcl, maxd, k, prof, lang, now, constraint, allOf,
+                                   contentdom, strictDom, modLang, site, altSite, siteExcludes, urlHashes,
+                                   skipDoubleDom, flagCount, &rows);
+  if (!hits || !rows) return NULL;
+  jclass bytes = (*env)->FindClass(env, "[B");
+  jobjectArray res = bytes ? (*env)->NewObjectArray(env, 2, bytes, NULL) : NULL;
+  if (!res) return NULL;
+  (*env)->SetObjectArrayElement(env, res, 0, hits);
+  (*env)->SetObjectArrayElement(env, res, 1, rows);
   return res;
 }
 

@@ -11,6 +11,7 @@
 //   search/ranking/ReferenceOrder.java:70,223  -> GpuRWI.eventOrder(...) (GpuReferenceOrder: one event per SearchEvent)
 //   search/query/SearchEvent.java:612-631      -> GpuRWI.query(...) (whole local RWI path)
 //   search/query/SearchEvent.java:736-806,1297 -> GpuRWI.queryFiltered(...) (constraints, doubledom)
+//   search/query/SearchEvent.java:612-631,1297 -> GpuRWI.queryRows(...) (the hits with their joined postings: rwiStack elements)
 //   kelondro/rwi/IndexCell.java:353-386        -> GpuRWI.loadHeaps(...) (BLOB heaps into HBM)
 //   kelondro/rwi/IndexCell.java:131-166        -> GpuRWI.dumpHeap(...) (the FlushThread dump: HBM into a BLOB heap)
 //
@@ -224,6 +225,46 @@ public final class GpuRWI implements AutoCloseable {
                              flattenN(urlhashes, 12), skipDoubleDom, flagCount);
     }
 
+    /** The hits of queryFiltered(...) together with the joined posting of every hit
+     *  (yrwi_query_rows): what SearchEvent.rwiStack holds and pullOneRWI hands to
+     *  Fulltext.getMetadata (SearchEvent.java:1297-1394).  rows: one 40-byte WordReferenceRow
+     *  per hit, in hit order -- the row TermSearch.joined() holds for the hit's url (one
+     *  include word: the stored row; more: the joined posting as toRowEntry writes it). */
+    public static final class HitsWithRows {
+        public final byte[] hits;   // n * 24 bytes, as query()
+        public final byte[] rows;   // n * 40 bytes
+        HitsWithRows(final byte[] hits, final byte[] rows) {
+            this.hits = hits;
+            this.rows = rows;
+        }
+        public int size() {
+            return this.hits.length / 24;
+        }
+        /** the 40 bytes of hit i's posting (new WordReferenceRow(urlEntryRow.newEntry(row(i)))) */
+        public byte[] row(final int i) {
+            final byte[] r = new byte[40];
+            System.arraycopy(this.rows, 40 * i, r, 0, 40);
+            return r;
+        }
+    }
+
+    /** queryFiltered(...) returning the hits plus their rows in one call; the filter arguments
+     *  may all be null / false / -1 (an unconstrained query).  A sharded context returns 40
+     *  zero bytes for a hit whose url hash another rank owns (include/yrwi.h). */
+    public synchronized HitsWithRows queryRows(final byte[][] include, final byte[][] exclude, final int maxDistance,
+                                final int k, final int[] profile32, final String language, final long nowMillis,
+                                final byte[] constraint, final boolean allOfConstraint, final int contentdom,
+                                final boolean strictContentDom, final String modifierLanguage, final byte[] sitehash,
+                                final byte[] altSitehash, final byte[][] siteexcludes, final byte[][] urlhashes,
+                                final boolean skipDoubleDom, final int[] flagCount) {
+        final byte[][] r = queryRows(this.ctx, flatten(include), include.length, flatten(exclude), exclude.length,
+                                     maxDistance, k, profile32, language, nowMillis, constraint, allOfConstraint,
+                                     contentdom, strictContentDom, modifierLanguage, sitehash, altSitehash,
+                                     flattenN(siteexcludes, 6), flattenN(urlhashes, 12), skipDoubleDom, flagCount);
+        if (r == null) throw new IllegalStateException("yrwi_query_rows failed");
+        return new HitsWithRows(r[0], r[1]);
+    }
+
     /** A SearchEvent's rwiStack on the GPU: open once per event, then addRWIs for the
      *  local container and every remote peer's container (Protocol.java:802); the
      *  result is the stack in rwiStack order (24-byte records as query()). */
@@ -393,6 +434,12 @@ public final class GpuRWI implements AutoCloseable {
                                                boolean strictDom, String modifierLanguage, byte[] site,
                                                byte[] altSite, byte[] siteExcludes, byte[] urlHashes,
                                                boolean skipDoubleDom, int[] flagCount);
+    private static native byte[][] queryRows(long ctx, byte[] incl, int nincl, byte[] excl, int nexcl,
+                                             int maxDistance, int k, int[] profile32, String language,
+                                             long nowMillis, byte[] constraint, boolean allOf, int contentdom,
+                                             boolean strictDom, String modifierLanguage, byte[] site,
+                                             byte[] altSite, byte[] siteExcludes, byte[] urlHashes,
+                                             boolean skipDoubleDom, int[] flagCount);
     private static native long eventOpen(long ctx, int[] profile32, String language, long nowMillis, int k,
                                          long maxPostings);
     private static native long eventOpenFiltered(long ctx, int[] profile32, String language, long nowMillis, int k,

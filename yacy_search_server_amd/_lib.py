@@ -172,6 +172,15 @@ SIGNATURES = {
                                                ctypes.POINTER(CHit), ctypes.POINTER(ctypes.c_int32),
                                                ctypes.POINTER(CStats), ctypes.POINTER(ctypes.c_int64)]),
     "yrwi_query_batch_wait": (ctypes.c_int, [_VP, ctypes.c_int64]),
+    # the same three with the 40-byte row of every hit (rows40_out, may be NULL) after `out`
+    "yrwi_query_rows": (ctypes.c_int, [_VP, ctypes.POINTER(CQuery), ctypes.POINTER(CHit), _VP,
+                                       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(CStats)]),
+    "yrwi_query_batch_rows": (ctypes.c_int, [_VP, ctypes.POINTER(CQuery), ctypes.c_int32, ctypes.c_int32,
+                                             ctypes.POINTER(CHit), _VP, ctypes.POINTER(ctypes.c_int32),
+                                             ctypes.POINTER(CStats)]),
+    "yrwi_query_batch_rows_submit": (ctypes.c_int, [_VP, ctypes.POINTER(CQuery), ctypes.c_int32, ctypes.c_int32,
+                                                    ctypes.POINTER(CHit), _VP, ctypes.POINTER(ctypes.c_int32),
+                                                    ctypes.POINTER(CStats), ctypes.POINTER(ctypes.c_int64)]),
     "yrwi_host_alloc": (ctypes.c_int, [_VP, ctypes.c_size_t, ctypes.POINTER(_VP)]),
     "yrwi_host_free": (ctypes.c_int, [_VP, _VP]),
     "yrwi_load_heaps": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32, ctypes.c_int32,

@@ -1711,7 +1711,8 @@ static int exchange_host_counts(Lane* ctx, int nq, int64_t nslots, const std::ve
 
 // Normalise (+ cross-shard exchange), then either score+top-k (hits) or all scores.
 static int run_rank_phase(Lane* ctx, std::vector<Plan>& plans, int32_t kmax, yrwi_hit* h_hits,
-                          int32_t* h_nout, int64_t* h_scores_all, yrwi_stats* st, Timing* tm, bool exchange = true) {
+                          int32_t* h_nout, int64_t* h_scores_all, yrwi_stats* st, Timing* tm, bool exchange = true,
+                          uint8_t* h_rows = nullptr) {
   const int nq = (int)plans.size();
   const int W = exchange ? ctx->world : 1;
   const bool shx = exchange && ctx->sharded;  // the url-hash-shard protocol
@@ -2081,23 +2082,69 @@ static int run_rank_phase(Lane* ctx, std::vector<Plan>& plans, int32_t kmax, yrw
   yrwi_hit* d_hits = nullptr;
   int32_t* d_nout = nullptr;
   const bool direct = ctx->hostreg && ctx->hostreg->contains(h_hits, hb) && ctx->hostreg->contains(h_nout, nb);
+  // the hits' rows (yrwi_query_*_rows) go the same way: into the caller's buffer when it is
+  // pinned and 8-byte aligned (k_hit_rows stores 8-byte words), else behind the hits in the
+  // landing buffer
+  const size_t rb = h_rows ? (size_t)YRWI_ROW_BYTES * (size_t)nq * kmax : 0;
+  const bool rows_direct = h_rows && ctx->hostreg && (reinterpret_cast<uintptr_t>(h_rows) & 7) == 0 &&
+                           ctx->hostreg->contains(h_rows, rb);
+  const size_t land_rows = direct ? 0 : (hb_al + nb + 255) & ~(size_t)255;
   uint8_t* land = nullptr;
+  uint8_t* d_rows = nullptr;
   {
     void* hp = h_hits;
     void* np = h_nout;
-    if (!direct) {
-      land = stage_reserve(ctx, &ctx->out_stage, hb_al + nb, true);
+    void* rp = h_rows;
+    if (!direct || (h_rows && !rows_direct)) {
+      land = stage_reserve(ctx, &ctx->out_stage, h_rows && !rows_direct ? land_rows + rb : hb_al + nb, true);
       if (!land) return YRWI_E_HIP;
+    }
+    if (!direct) {
       hp = land;
       np = land + hb_al;
     }
+    if (h_rows && !rows_direct) rp = land + land_rows;
+    if (h_rows) HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&d_rows), rp, 0));
     // the emit kernels write the pinned destination directly (a DMA copy from a
     // device buffer instead measured 1.17 vs 1.07 ms per C2 step)
     HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&d_hits), hp, 0));
     HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&d_nout), np, 0));
   }
   if (!d_fptr || !d_fcnt) return ctx->fail(YRWI_E_NOMEM, "arena");
-  if (upload(ctx, d_fptr, fptr, d_fcnt, fcnt)) return YRWI_E_HIP;
+  // rows asked for: k_pull (doubledom, sharded) leaves its hits in device memory, where
+  // k_hit_rows reads them, looks their rows up and forwards them to the pinned destination
+  HitRowQ* d_hq = nullptr;
+  yrwi_hit* d_phits = d_hits;
+  int32_t* d_pnout = d_nout;
+  if (!h_rows) {
+    if (upload(ctx, d_fptr, fptr, d_fcnt, fcnt)) return YRWI_E_HIP;
+  } else {
+    std::vector<HitRowQ> hq((size_t)nq);
+    int own_shift = -1;
+    if (shx) {
+      own_shift = 6;
+      for (int w = ctx->world; w > 1; w >>= 1) own_shift--;
+    }
+    for (int qi = 0; qi < nq; qi++) {
+      const Plan& P = plans[(size_t)qi];
+      HitRowQ& H = hq[(size_t)qi];
+      H.rows = P.empty ? nullptr : P.cont.rows;
+      H.now_ms = P.now_ms;
+      H.src = shx || rq[(size_t)qi].doubledom ? HR_HITS : HR_CAND;
+      H.own_shift = own_shift;
+      H.own_rank = ctx->rank;
+      H.pad = 0;
+    }
+    d_hq = arena_alloc<HitRowQ>(ctx, nq);
+    if (!d_hq) return ctx->fail(YRWI_E_NOMEM, "arena");
+    // (the rows' descriptors ride in the candidate lists' copy kernel: no launch of their own)
+    if (upload(ctx, d_fptr, fptr, d_fcnt, fcnt, d_hq, hq)) return YRWI_E_HIP;
+    if (shx || any_dd) {
+      d_phits = arena_alloc<yrwi_hit>(ctx, (int64_t)nq * kmax);
+      d_pnout = arena_alloc<int32_t>(ctx, nq);
+      if (!d_phits || !d_pnout) return ctx->fail(YRWI_E_NOMEM, "arena");
+    }
+  }
   std::vector<int32_t> hD;  // max-distance fold state per query (overflow check)
   const uint8_t* hD_land = nullptr;
   if (!shx) {
@@ -2111,7 +2158,7 @@ static int run_rank_phase(Lane* ctx, std::vector<Plan>& plans, int32_t kmax, yrw
       if (!d_stack || !d_scnt) return ctx->fail(YRWI_E_NOMEM, "arena");
       sp = span_open(ctx, tm);
       if (launch_emit(d_q, nq, d_fptr, d_fcnt, kint, d_stack, d_scnt, 2, ctx->stream) ||
-          launch_pull(d_q, nq, d_stack, d_scnt, kint, 1, kmax, d_hits, d_nout, ctx->stream))
+          launch_pull(d_q, nq, d_stack, d_scnt, kint, 1, kmax, d_phits, d_pnout, ctx->stream))
         return ctx->fail(YRWI_E_HIP, "doubledom launch");
       span_close(ctx, tm, sp);
     }
@@ -2135,12 +2182,18 @@ static int run_rank_phase(Lane* ctx, std::vector<Plan>& plans, int32_t kmax, yrw
     if (ctx->release_after_final) turn_release(ctx);  // the next batch part's collectives may follow now
     sp = span_open(ctx, tm);
     if (launch_gmerge(d_q, d_allh, d_alln, W, nq, kint, d_slot, d_dup, d_stack, d_scnt, ctx->stream) ||
-        launch_pull(d_q, nq, d_stack, d_scnt, kint, 0, kmax, d_hits, d_nout, ctx->stream))
+        launch_pull(d_q, nq, d_stack, d_scnt, kint, 0, kmax, d_phits, d_pnout, ctx->stream))
       return ctx->fail(YRWI_E_HIP, "shard merge launch");
     span_close(ctx, tm, sp);
     hD_land = readback(ctx, &ctx->down_stage, reinterpret_cast<const uint8_t*>(d_norm) + offsetof(NormState, D), nq,
                        4, (int64_t)sizeof(NormState));
     if (!hD_land) return YRWI_E_HIP;
+  }
+  if (h_rows) {
+    sp = span_open(ctx, tm);
+    if (launch_hit_rows(d_q, d_hq, nq, d_fptr, d_fcnt, d_phits, d_pnout, kmax, d_hits, d_nout, d_rows, ctx->stream))
+      return ctx->fail(YRWI_E_HIP, "hit rows launch");
+    span_close(ctx, tm, sp);
   }
   if (tm) { tm->ts = ctx->event(); hipEventRecord(tm->ts, ctx->stream); }
   HIPCHK(ctx, lane_sync(ctx));
@@ -2156,6 +2209,11 @@ static int run_rank_phase(Lane* ctx, std::vector<Plan>& plans, int32_t kmax, yrw
       std::memcpy(h_hits + (size_t)qi * kmax, land + sizeof(yrwi_hit) * (size_t)qi * kmax,
                   sizeof(yrwi_hit) * (size_t)std::max(0, std::min(h_nout[qi], kmax)));
   }
+  if (h_rows && !rows_direct)
+    for (int qi = 0; qi < nq; qi++)
+      std::memcpy(h_rows + (size_t)YRWI_ROW_BYTES * (size_t)qi * kmax,
+                  land + land_rows + (size_t)YRWI_ROW_BYTES * (size_t)qi * kmax,
+                  (size_t)YRWI_ROW_BYTES * (size_t)std::max(0, std::min(h_nout[qi], kmax)));
   return flagcounts_out();
 }
 
@@ -2221,13 +2279,14 @@ void yrwi::measure_scratch(CtxBase* ctx) {
 }
 
 static int run_batch_part_(const yrwi_ctx* ix, Lane* L, const yrwi_query_desc* q, int32_t nq, int32_t kmax,
-                           yrwi_hit* out, int32_t* nout, yrwi_stats* st);
+                           yrwi_hit* out, uint8_t* rows, int32_t* nout, yrwi_stats* st);
 
+// rows: the 40-byte row of every hit (stride kmax rows per query), or nullptr
 static int run_batch_part(const yrwi_ctx* ix, Lane* L, const yrwi_query_desc* q, int32_t nq, int32_t kmax,
-                          yrwi_hit* out, int32_t* nout, yrwi_stats* st) {
+                          yrwi_hit* out, uint8_t* rows, int32_t* nout, yrwi_stats* st) {
   L->enter();
   const int64_t seq = L->seq;  // (passing the turn after the final collective clears L->seq)
-  const int rc = run_batch_part_(ix, L, q, nq, kmax, out, nout, st);
+  const int rc = run_batch_part_(ix, L, q, nq, kmax, out, rows, nout, st);
   // peers waiting on this part's exchanges fail fast; later parts are unaffected
   if (rc && L->hostx) hostx_abort(L->hostx, seq);
   turn_release(L);  // error paths, parts without collectives: the turn still passes in order
@@ -2237,7 +2296,7 @@ static int run_batch_part(const yrwi_ctx* ix, Lane* L, const yrwi_query_desc* q,
 }
 
 static int run_batch_part_(const yrwi_ctx* ix, Lane* L, const yrwi_query_desc* q, int32_t nq, int32_t kmax,
-                           yrwi_hit* out, int32_t* nout, yrwi_stats* st) {
+                           yrwi_hit* out, uint8_t* rows, int32_t* nout, yrwi_stats* st) {
   const int64_t t0 = now_ns();
   const int64_t r0 = t_realloc;
   int64_t tp = 0, tj = 0, tr = 0, w0 = L->wait_ns, wj = 0;
@@ -2286,7 +2345,9 @@ static int run_batch_part_(const yrwi_ctx* ix, Lane* L, const yrwi_query_desc* q
       tm.tj = L->event();
       hipEventRecord(tm.tj, L->stream);
     }
-    rc = run_rank_phase(L, plans, kmax, out + (size_t)g0 * kmax, nout + g0, nullptr, st, tmp);
+    // (a pass's rows leave its arena here, before the next pass reuses it, at its queries' own positions)
+    rc = run_rank_phase(L, plans, kmax, out + (size_t)g0 * kmax, nout + g0, nullptr, st, tmp, true,
+                        rows ? rows + (size_t)YRWI_ROW_BYTES * (size_t)g0 * kmax : nullptr);
     if (rc) return rc;
     tr += now_ns() - tr0;
     if (st) {
@@ -2384,6 +2445,11 @@ static bool wants_authority(const yrwi_query_desc* q, int32_t nq) {
 
 extern "C" int yrwi_query_batch(yrwi_ctx* ctx, const yrwi_query_desc* q, int32_t nq, int32_t kmax, yrwi_hit* out,
                                 int32_t* nout, yrwi_stats* st) {
+  return yrwi_query_batch_rows(ctx, q, nq, kmax, out, nullptr, nout, st);
+}
+
+extern "C" int yrwi_query_batch_rows(yrwi_ctx* ctx, const yrwi_query_desc* q, int32_t nq, int32_t kmax, yrwi_hit* out,
+                                     uint8_t* rows, int32_t* nout, yrwi_stats* st) {
   if (int rc = check_batch_args(ctx, q, nq, kmax, out, nout)) return rc;
   if (nq == 0) {
     if (st) std::memset(st, 0, sizeof(*st));
@@ -2410,7 +2476,8 @@ extern "C" int yrwi_query_batch(yrwi_ctx* ctx, const yrwi_query_desc* q, int32_t
   }
   auto part = [=, &pst](int l) {
     Lane* L = ctx->lanes[(size_t)l];
-    L->rc = run_batch_part(ctx, L, q + cut(l), cut(l + 1) - cut(l), kmax, out + (size_t)cut(l) * kmax, nout + cut(l),
+    L->rc = run_batch_part(ctx, L, q + cut(l), cut(l + 1) - cut(l), kmax, out + (size_t)cut(l) * kmax,
+                           rows ? rows + (size_t)YRWI_ROW_BYTES * (size_t)cut(l) * kmax : nullptr, nout + cut(l),
                            st ? &pst[(size_t)l] : nullptr);
   };
   for (int l = 1; l < nl; l++) ctx->lanes[(size_t)l]->submit([=] { part(l); });
@@ -2464,6 +2531,12 @@ extern "C" int yrwi_query_batch(yrwi_ctx* ctx, const yrwi_query_desc* q, int32_t
 
 extern "C" int yrwi_query_batch_submit(yrwi_ctx* ctx, const yrwi_query_desc* q, int32_t nq, int32_t kmax,
                                        yrwi_hit* out, int32_t* nout, yrwi_stats* st, int64_t* ticket) {
+  return yrwi_query_batch_rows_submit(ctx, q, nq, kmax, out, nullptr, nout, st, ticket);
+}
+
+extern "C" int yrwi_query_batch_rows_submit(yrwi_ctx* ctx, const yrwi_query_desc* q, int32_t nq, int32_t kmax,
+                                            yrwi_hit* out, uint8_t* rows, int32_t* nout, yrwi_stats* st,
+                                            int64_t* ticket) {
   if (int rc = check_batch_args(ctx, q, nq, kmax, out, nout)) return rc;
   if (!ticket) return YRWI_E_ARG;
   hipSetDevice(ctx->device);
@@ -2484,7 +2557,7 @@ extern "C" int yrwi_query_batch_submit(yrwi_ctx* ctx, const yrwi_query_desc* q, 
   L->dcall = 0;
   L->submit([=] {
     if (st) std::memset(st, 0, sizeof(*st));
-    const int rc = nq == 0 ? 0 : run_batch_part(ctx, L, q, nq, kmax, out, nout, st);
+    const int rc = nq == 0 ? 0 : run_batch_part(ctx, L, q, nq, kmax, out, rows, nout, st);
     turn_release(L);  // nq == 0: nothing ran, the turn passes all the same
     {
       std::lock_guard<std::mutex> lk(ctx->st_mu);
@@ -2538,6 +2611,13 @@ extern "C" int yrwi_query(yrwi_ctx* ctx, const yrwi_query_desc* q, yrwi_hit* out
   if (!q) return YRWI_E_ARG;
   int32_t kmax = std::max<int32_t>(1, std::min<int32_t>(q->k, YRWI_MAX_K));
   return yrwi_query_batch(ctx, q, 1, kmax, out, nout, st);
+}
+
+extern "C" int yrwi_query_rows(yrwi_ctx* ctx, const yrwi_query_desc* q, yrwi_hit* out, uint8_t* rows, int32_t* nout,
+                               yrwi_stats* st) {
+  if (!q) return YRWI_E_ARG;
+  int32_t kmax = std::max<int32_t>(1, std::min<int32_t>(q->k, YRWI_MAX_K));
+  return yrwi_query_batch_rows(ctx, q, 1, kmax, out, rows, nout, st);
 }
 
 extern "C" int yrwi_score_nodes(yrwi_ctx* ctx, const yrwi_node* nodes, int64_t n, const yrwi_profile* prof,

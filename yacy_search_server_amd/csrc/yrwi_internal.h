@@ -339,6 +339,19 @@ struct Cand {  // top-k candidate: sort descending on (k1, k2)
   uint64_t k2;  // ((hashCode ^ 2^31) << 32) | ~index
 };
 
+// Rows of the hits (k_hit_rows), per query beside its RankQ (whose feat, uid /
+// ekhi / eklo, dkhi / dklo and n name the container the hits were ranked from).
+enum : int32_t { HR_CAND = 0, HR_HITS = 1 };
+struct HitRowQ {
+  const uint8_t* rows;  // the container's stored 40-byte rows (an index list, or its url selection); nullptr:
+                        // a joined container, its records are re-encoded (J6)
+  int64_t now_ms;       // freshUntil of a re-encoded row
+  int32_t src;          // HR_CAND: the hits are the final candidates; HR_HITS: hits in device memory, looked up by key
+  int32_t own_shift;    // sharded: this rank owns url hashes with (first character index >> own_shift) == own_rank
+  int32_t own_rank;     //   (Distribution.java:153-158); own_shift < 0: one context, every hit is its own
+  int32_t pad;
+};
+
 // host-count exchange between url-hash shards (authority, ReferenceOrder.java:176-216)
 struct HostMsg {
   uint64_t key;  // host hash (url-hash chars 6..11, 36 bits) + 1
@@ -472,6 +485,13 @@ int launch_reduce_i32(const int32_t* all, int world, int64_t n, int32_t* out, in
 // queries, the first kout entries for the others (only_dd: doubledom queries only)
 int launch_pull(const RankQ* d_q, int32_t nq, const yrwi_hit* d_stack, const int32_t* d_scnt, int32_t kint,
                 int only_dd, int32_t kmax, yrwi_hit* d_hits, int32_t* d_nout, void* stream);
+// the 40-byte row of every final hit (row of hit i of query q at d_rows + (q * kmax + i) * 40, 8-byte
+// aligned).  HR_CAND queries: the hits k_emit wrote from d_final.  HR_HITS queries: the hits are
+// d_src_hits[q * kmax + i], i < d_src_cnt[q] (k_pull's output in device memory), and are forwarded
+// to d_hits / d_nout as well
+int launch_hit_rows(const RankQ* d_q, const HitRowQ* d_hq, int32_t nq, const Cand* const* d_final,
+                    const int32_t* const* d_final_cnt, const yrwi_hit* d_src_hits, const int32_t* d_src_cnt,
+                    int32_t kmax, yrwi_hit* d_hits, int32_t* d_nout, uint8_t* d_rows, void* stream);
 // merge of gathered shard stacks allh[world][nq][kint] into stack[nq][kint] (TreeSet in shard order)
 int launch_gmerge(const RankQ* d_q, const yrwi_hit* d_allh, const int32_t* d_alln, int world, int32_t nq, int32_t kint,
                   uint32_t* d_slot, uint8_t* d_dup, yrwi_hit* d_stack, int32_t* d_scnt, void* stream);

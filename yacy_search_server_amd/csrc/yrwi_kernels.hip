@@ -2024,17 +2024,12 @@ __global__ void k_features(const uint8_t* __restrict__ rows, int64_t n, uint64_t
   if (i < n) store_rec(feat, i, rec_of_row(load_row(rows + i * YRWI_ROW_BYTES)));
 }
 
-// joined container -> the 40-byte rows toRowEntry writes (WordReferenceRow ctor
-// :116-161): url hash from the dictionary, freshUntil = lastModified + 2 (today -
+// a joined container's record -> the 40-byte row toRowEntry writes (WordReferenceRow ctor
+// :116-161): url hash from its key, freshUntil = lastModified + 2 (today -
 // lastModified) days, floored at 0; typeofword and reserve 0
-__global__ void k_feat_rows(const uint64_t* __restrict__ feat, const uint32_t* __restrict__ uid,
-                            const uint64_t* __restrict__ dkhi, const uint8_t* __restrict__ dklo, int64_t n,
-                            int64_t now_ms, uint8_t* __restrict__ rows) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const Rec q = load_rec(feat, i);
+__device__ __forceinline__ Row row_of_rec(const Rec& q, uint64_t khi, uint32_t klo, int64_t now_ms) {
   uint8_t h[12];
-  key_chars(dkhi[uid[i]], dklo[uid[i]], h);
+  key_chars(khi, klo, h);
   Row r{};
   for (int j = 0; j < 12; j++) r.set(j, h[j]);
   const uint64_t w0 = q.w[0], w1 = q.w[1], w2 = q.w[2];
@@ -2056,7 +2051,17 @@ __global__ void k_feat_rows(const uint64_t* __restrict__ feat, const uint32_t* _
   r.set(O_T, (uint32_t)(w0 >> 8)); r.set(O_T + 1, (uint32_t)w0);
   r.set(O_R, (uint32_t)w1); r.set(O_O, (uint32_t)(w1 >> 8)); r.set(O_I, (uint32_t)(w1 >> 16));
   r.set(O_K, 0);
-  store_row(rows + i * YRWI_ROW_BYTES, r);
+  return r;
+}
+
+// joined container -> its rows (yrwi_term_search, J6)
+__global__ void k_feat_rows(const uint64_t* __restrict__ feat, const uint32_t* __restrict__ uid,
+                            const uint64_t* __restrict__ dkhi, const uint8_t* __restrict__ dklo, int64_t n,
+                            int64_t now_ms, uint8_t* __restrict__ rows) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Rec q = load_rec(feat, i);
+  store_row(rows + i * YRWI_ROW_BYTES, row_of_rec(q, dkhi[uid[i]], dklo[uid[i]], now_ms));
 }
 
 // ================================================================ ranking
@@ -4375,6 +4380,74 @@ __global__ __launch_bounds__(64) void k_pull(const RankQ* __restrict__ qs, const
   if (threadIdx.x == 0) nout[qi] = m;
 }
 
+// ------------------------------------------------ rows of the hits (yrwi_query_*_rows)
+// The 40-byte row of the joined and excluded container every final hit was ranked
+// from, next to the hit: a single include list's row as it is stored, else the
+// record re-encoded as k_feat_rows does (J6).  One workgroup per query, one hit
+// per thread.  HR_CAND: the hits are the query's final candidates (what k_emit
+// wrote), the element index is the candidate's.  HR_HITS: the hits are in device
+// memory in their final order (k_pull's output: doubledom and sharded batches);
+// the element is found by a binary search of the hit's url key in the container
+// (strictly ascending by url hash), and the hit is forwarded to the caller's
+// buffer.  Sharded: a hit of another rank's url-hash range gets 40 zero bytes.
+__device__ __forceinline__ void hit_key(const yrwi_hit& h, uint64_t& hi, uint32_t& lo) {
+  uint64_t x = 0;
+#pragma unroll
+  for (int j = 0; j < 10; j++) x = (x << 6) | (uint64_t)(ahpla(h.urlhash[j]) & 63);
+  const uint32_t c10 = (uint32_t)ahpla(h.urlhash[10]) & 63, c11 = (uint32_t)ahpla(h.urlhash[11]) & 63;
+  hi = (x << 4) | (c10 >> 2);
+  lo = ((c10 & 3u) << 6) | c11;
+}
+
+__global__ __launch_bounds__(256) void k_hit_rows(const RankQ* __restrict__ qs, const HitRowQ* __restrict__ hq,
+                                                  const Cand* const* __restrict__ fin,
+                                                  const int32_t* const* __restrict__ fin_cnt,
+                                                  const yrwi_hit* __restrict__ src_hits,
+                                                  const int32_t* __restrict__ src_cnt, int32_t kmax,
+                                                  yrwi_hit* __restrict__ hits, int32_t* __restrict__ nout,
+                                                  uint8_t* __restrict__ rows) {
+  const int qi = blockIdx.x;
+  const RankQ& Q = qs[qi];
+  const HitRowQ H = hq[qi];
+  const bool cand = H.src == HR_CAND;
+  const int32_t n = cand ? min(*fin_cnt[qi], min(Q.kout, kmax)) : min(src_cnt[qi], kmax);
+  const Cand* f = fin[qi];
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int64_t o = (int64_t)qi * kmax + i;
+    int64_t e = -1;
+    uint64_t khi = 0;
+    uint32_t klo = 0;
+    if (cand) {
+      e = (int64_t)(~(uint32_t)f[i].k2 & 0x0FFFFFFFu);
+      if (e < Q.n) key_at(Q, e, khi, klo); else e = -1;
+    } else {
+      const yrwi_hit h = src_hits[o];
+      hits[o] = h;
+      const bool mine = H.own_shift < 0 || (ahpla(h.urlhash[0]) >> H.own_shift) == H.own_rank;
+      if (mine) {
+        hit_key(h, khi, klo);
+        int64_t lo = 0, hi = Q.n;  // first element whose key is not below the hit's
+        while (lo < hi) {
+          const int64_t m = (lo + hi) >> 1;
+          uint64_t mh;
+          uint32_t ml;
+          key_at(Q, m, mh, ml);
+          if (mh < khi || (mh == khi && ml < klo)) lo = m + 1; else hi = m;
+        }
+        if (lo < Q.n) {
+          uint64_t mh;
+          uint32_t ml;
+          key_at(Q, lo, mh, ml);
+          if (mh == khi && ml == klo) e = lo;
+        }
+      }
+    }
+    Row r{};
+    if (e >= 0) r = H.rows ? load_row(H.rows + e * YRWI_ROW_BYTES) : row_of_rec(load_rec(Q.feat, e), khi, klo, H.now_ms);
+    store_row(rows + o * YRWI_ROW_BYTES, r);
+  }
+  if (!cand && threadIdx.x == 0) nout[qi] = n;
+}
 
 // all scores of a container (yrwi_normalize_score)
 __global__ __launch_bounds__(256) void k_score_all(const RankQ* __restrict__ qs,
@@ -4884,6 +4957,15 @@ int launch_emit(const RankQ* d_q, int32_t nq, const Cand* const* d_final, const 
                 int32_t kmax, yrwi_hit* d_hits, int32_t* d_nout, int mode, void* st) {
   hipLaunchKernelGGL(k_emit, dim3((unsigned)nq), dim3(256), 0, S(st), d_q, nq, d_final, d_final_cnt, kmax,
                      d_hits, d_nout, mode);
+  return rc(hipGetLastError());
+}
+
+int launch_hit_rows(const RankQ* d_q, const HitRowQ* d_hq, int32_t nq, const Cand* const* d_final,
+                    const int32_t* const* d_final_cnt, const yrwi_hit* d_src_hits, const int32_t* d_src_cnt,
+                    int32_t kmax, yrwi_hit* d_hits, int32_t* d_nout, uint8_t* d_rows, void* st) {
+  if (nq <= 0) return 0;
+  hipLaunchKernelGGL(k_hit_rows, dim3((unsigned)nq), dim3(256), 0, S(st), d_q, d_hq, d_final, d_final_cnt, d_src_hits,
+                     d_src_cnt, kmax, d_hits, d_nout, d_rows);
   return rc(hipGetLastError());
 }
 

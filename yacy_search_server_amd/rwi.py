@@ -101,6 +101,9 @@ class Hit:
     urlhash: bytes
     score: int      # ReferenceOrder.cardinal
     tiebreak: int   # ByteArray.hashCode(urlhash)
+    # the 40-byte row of the joined container the hit was ranked from (searches with rows=True;
+    # a sharded context: 40 zero bytes when another rank owns the url hash), else None
+    row: Optional[bytes] = None
 
 
 class QueryFilter:
@@ -247,6 +250,15 @@ def _check(ctx, rc: int):
         # ctx None: an open failed, and yrwi_last_error(NULL) holds this thread's reason
         msg = _lib.lib().yrwi_last_error(ctx)
         raise YrwiError(rc, (msg or b"").decode(errors="replace"))
+
+
+def _address(buf) -> Optional[int]:
+    """address of a ctypes array / numpy array, an int address as it is, None as NULL"""
+    if buf is None or isinstance(buf, int):
+        return buf
+    if isinstance(buf, np.ndarray):
+        return buf.ctypes.data
+    return ctypes.addressof(buf)
 
 
 def _hashes(hs: Sequence[bytes]) -> bytes:
@@ -536,9 +548,16 @@ class RWIIndex:
     # ---- full query: TermSearch -> normalise -> cardinal -> top-k ----
     def search(self, include: Sequence[bytes], exclude: Sequence[bytes] = (), profile: Optional[RankingProfile] = None,
                language: str = "en", max_distance: int = INTEGER_MAX, now_ms: int = 0, k: int = 100,
-               stats: Optional[CStats] = None, filter: Optional[QueryFilter] = None) -> List[Hit]:
-        return self.search_batch([Query(include, exclude, max_distance, k, profile, language, now_ms, filter)],
-                                 stats=stats)[0]
+               stats: Optional[CStats] = None, filter: Optional[QueryFilter] = None, rows: bool = False) -> List[Hit]:
+        """rows=True: every Hit carries its joined posting's 40-byte row (yrwi_query_rows)."""
+        q = Query(include, exclude, max_distance, k, profile, language, now_ms, filter)
+        if not rows:
+            return self.search_batch([q], stats=stats)[0]
+        arr, keep, hits, nout, kmax = self._marshal([q], None)
+        st = stats if stats is not None else CStats()
+        rbuf = np.zeros((kmax, 40), dtype=np.uint8)
+        _check(self._h, _lib.lib().yrwi_query_rows(self._h, arr, hits, rbuf.ctypes.data, nout, ctypes.byref(st)))
+        return self._unmarshal(1, kmax, hits, nout, rbuf)[0]
 
     def _marshal(self, queries: Sequence[Query], kmax: Optional[int]):
         nq = len(queries)
@@ -574,35 +593,65 @@ class RWIIndex:
         return arr, keep, hits, nout, kmax
 
     @staticmethod
-    def _unmarshal(nq: int, kmax: int, hits, nout) -> List[List[Hit]]:
-        return [[Hit(bytes(hits[i * kmax + j].urlhash), hits[i * kmax + j].score, hits[i * kmax + j].tiebreak)
-                 for j in range(nout[i])] for i in range(nq)]
+    def _unmarshal(nq: int, kmax: int, hits, nout, rows: Optional[np.ndarray] = None) -> List[List[Hit]]:
+        """rows: the (nq * kmax, 40) uint8 rows buffer of a search with rows, or None"""
+        if rows is None:
+            return [[Hit(bytes(hits[i * kmax + j].urlhash), hits[i * kmax + j].score, hits[i * kmax + j].tiebreak)
+                     for j in range(nout[i])] for i in range(nq)]
+        return [[Hit(bytes(hits[i * kmax + j].urlhash), hits[i * kmax + j].score, hits[i * kmax + j].tiebreak,
+                     rows[i * kmax + j].tobytes()) for j in range(nout[i])] for i in range(nq)]
 
     def search_batch(self, queries: Sequence[Query], stats: Optional[CStats] = None,
-                     kmax: Optional[int] = None) -> List[List[Hit]]:
+                     kmax: Optional[int] = None, rows: bool = False) -> List[List[Hit]]:
+        """rows=True: every Hit carries its joined posting's 40-byte row (yrwi_query_batch_rows)."""
         nq = len(queries)
         if nq == 0:
             return []
         arr, keep, hits, nout, kmax = self._marshal(queries, kmax)
         st = stats if stats is not None else CStats()
-        _check(self._h, _lib.lib().yrwi_query_batch(self._h, arr, nq, kmax, hits, nout, ctypes.byref(st)))
-        return self._unmarshal(nq, kmax, hits, nout)
+        if not rows:
+            _check(self._h, _lib.lib().yrwi_query_batch(self._h, arr, nq, kmax, hits, nout, ctypes.byref(st)))
+            return self._unmarshal(nq, kmax, hits, nout)
+        rbuf = np.zeros((nq * kmax, 40), dtype=np.uint8)
+        self.search_batch_rows_raw(arr, nq, kmax, hits, rbuf.ctypes.data, nout, st)
+        return self._unmarshal(nq, kmax, hits, nout, rbuf)
 
-    def submit(self, queries: Sequence[Query], kmax: Optional[int] = None) -> "PendingBatch":
+    def submit(self, queries: Sequence[Query], kmax: Optional[int] = None, rows: bool = False) -> "PendingBatch":
         """Start a batch asynchronously (yrwi_query_batch_submit); .result() waits for it.
-        Batches run on the context's lanes in submission order (ticket t on lane t % lanes)."""
+        Batches run on the context's lanes in submission order (ticket t on lane t % lanes).
+        rows=True: the result's Hits carry their rows (yrwi_query_batch_rows_submit)."""
         nq = len(queries)
         arr, keep, hits, nout, kmax = self._marshal(queries, kmax) if nq else ((CQuery * 1)(), [], (CHit * 1)(),
                                                                                (ctypes.c_int32 * 1)(), 1)
         st = CStats()
-        ticket = self.submit_raw(arr, nq, kmax, hits, nout, st)
-        return PendingBatch(self, ticket, nq, kmax, (arr, keep, hits, nout, st))
+        if not rows:
+            ticket = self.submit_raw(arr, nq, kmax, hits, nout, st)
+            return PendingBatch(self, ticket, nq, kmax, (arr, keep, hits, nout, st))
+        rbuf = np.zeros((max(1, nq) * kmax, 40), dtype=np.uint8)
+        ticket = self.submit_rows_raw(arr, nq, kmax, hits, rbuf.ctypes.data, nout, st)
+        return PendingBatch(self, ticket, nq, kmax, (arr, keep, hits, nout, st), rbuf)
 
     def search_batch_raw(self, cq, nq: int, kmax: int, hits, nout, st) -> None:
         """Zero-marshalling batch call for benchmarks (pre-built ctypes arrays).
         st None: no statistics (yrwi_stats* NULL, no HIP events: the production call)."""
         _check(self._h, _lib.lib().yrwi_query_batch(self._h, cq, nq, kmax, hits, nout,
                                                     ctypes.byref(st) if st is not None else None))
+
+    def search_batch_rows_raw(self, cq, nq: int, kmax: int, hits, rows, nout, st) -> None:
+        """search_batch_raw with the hits' rows (yrwi_query_batch_rows).  rows: a buffer of
+        nq * kmax * 40 bytes -- a ctypes array (host_array(ctypes.c_uint8, n): pinned, written
+        by the GPU directly when 8-byte aligned) or an address; None: no rows."""
+        _check(self._h, _lib.lib().yrwi_query_batch_rows(self._h, cq, nq, kmax, hits, _address(rows), nout,
+                                                         ctypes.byref(st) if st is not None else None))
+
+    def submit_rows_raw(self, cq, nq: int, kmax: int, hits, rows, nout, st) -> int:
+        """submit_raw with the hits' rows (yrwi_query_batch_rows_submit); `rows` as in
+        search_batch_rows_raw, alive until wait(ticket)."""
+        t = ctypes.c_int64()
+        _check(self._h, _lib.lib().yrwi_query_batch_rows_submit(self._h, cq, nq, kmax, hits, _address(rows), nout,
+                                                                ctypes.byref(st) if st is not None else None,
+                                                                ctypes.byref(t)))
+        return t.value
 
     # ---- asynchronous batches (yrwi_query_batch_submit / _wait) ----
     def submit_raw(self, cq, nq: int, kmax: int, hits, nout, st) -> int:
@@ -628,13 +677,14 @@ class RWIIndex:
 class PendingBatch:
     """A submitted batch: its ctypes buffers stay alive until result() collects it."""
 
-    def __init__(self, index: RWIIndex, ticket: int, nq: int, kmax: int, bufs):
+    def __init__(self, index: RWIIndex, ticket: int, nq: int, kmax: int, bufs, rows: Optional[np.ndarray] = None):
         self.index, self.ticket, self.nq, self.kmax, self._bufs = index, ticket, nq, kmax, bufs
+        self._rows = rows  # the rows buffer of submit(rows=True)
 
     def result(self) -> List[List[Hit]]:
         self.index.wait(self.ticket)
         _, _, hits, nout, _ = self._bufs
-        return RWIIndex._unmarshal(self.nq, self.kmax, hits, nout)
+        return RWIIndex._unmarshal(self.nq, self.kmax, hits, nout, self._rows)
 
 
 def unique_id() -> bytes:
