@@ -534,6 +534,55 @@ int yrwi_event_result(yrwi_ctx* ctx, yrwi_event* ev, yrwi_hit* out, int32_t maxn
  * at :1309,1327,1392 is not on the RWI path). */
 int yrwi_event_pull(yrwi_ctx* ctx, yrwi_event* ev, int32_t skip_double_dom, yrwi_hit* out, int32_t maxn,
                     int32_t* nout);
+/* ---- the local container of a search event, straight from the device index ----
+ * RWIProcess.run hands TermSearch's joined container to addRWIs(container, local = true)
+ * (SearchEvent.java:612-631; the sitehost retry at :651 a second time).  A device-local
+ * arrival is that pair of steps without the rows leaving the device: the event ends in
+ * exactly the state that yrwi_term_search(ctx, q, rows, cap, &m) followed by yrwi_event_add
+ * of {ev, rows, m, local = 1} leaves -- stack, doublecheck set, flag counts, ReferenceOrder,
+ * host counts, yrwi_event_info and yrwi_event_source answers -- and later yrwi_event_add
+ * arrivals continue from it. */
+typedef struct yrwi_local_arrival {
+  yrwi_event* ev;
+  const yrwi_query_desc* q; /* incl, excl, max_distance, now_ms, urlselection: as yrwi_term_search reads them;
+                               k, profile, language, filter unused (the event has its own) */
+  int64_t m;                /* out: rows of the joined and excluded container that arrived */
+  int32_t rc;               /* out: 0 or YRWI_E_* for this arrival (CAPACITY) */
+} yrwi_local_arrival;
+typedef struct yrwi_local_stats {
+  int64_t rows_joined, rows_arrived; /* before / after exclusion, summed over the call */
+  int64_t bytes_h2d, bytes_d2h;      /* bytes the call moved over PCIe: descriptors, tables, statuses -- never rows */
+  int32_t launches_tail;             /* launches, copies and memsets enqueued after the join phase */
+  int32_t syncs;                     /* host waits on the device in the whole call */
+  int64_t t_total_ns;
+  int64_t device_allocs;             /* device-wide allocation events of the call (yrwi_realloc_events): the one
+                                        block of retained rows, none for a call whose containers are all empty */
+} yrwi_local_stats;
+/* Applies the arrivals in array order within an event; arrivals of different events run in
+ * parallel, one workgroup per event, as yrwi_event_add does.  The containers of all arrivals
+ * are joined in one pass, turned into rows on the device (k_local_rows) and read by
+ * k_event_add where they lie: no row crosses PCIe, and launches_tail and syncs do not depend
+ * on narr.  An absent include term or an empty join gives m = 0, rc = 0 and leaves the event
+ * as it is (no arrival number is used up).  Planning errors (YRWI_E_HASH, YRWI_E_UNSUPPORTED
+ * urlselection cases, YRWI_E_ARG -- an event from yrwi_event_open_order included --,
+ * YRWI_E_NOMEM) return before anything is applied to any event; YRWI_E_CAPACITY is reported
+ * per arrival in rc and the first nonzero rc is returned.  A context of a shard group
+ * (yrwi_open_shard with world > 1) returns YRWI_E_UNSUPPORTED: a shard holds only its url
+ * range of the container, and events are not combined across ranks.  Waits for batches in
+ * flight and serialises with the other event entry points.  st may be NULL.
+ * The arrivals' rows stay in device memory (one allocation per call, 40 bytes per joined
+ * row, shared by the events of the call) until the last of those events closes or the
+ * context does: yrwi_event_rows reads them. */
+int yrwi_event_add_local(yrwi_ctx* ctx, yrwi_local_arrival* arr, int32_t narr, yrwi_local_stats* st);
+/* The posting of each url at urls12 + 12 i as the event admitted it (its doublecheck set,
+ * as yrwi_event_source): found[i] = 1 and the row at rows40_out + 40 i when that posting
+ * arrived through yrwi_event_add_local; found[i] = 0 and 40 zero bytes for a url that is not
+ * in the set, was seeded by the filter, or was admitted from a yrwi_event_add arrival (whose
+ * rows the caller holds).  A hit taken by yrwi_event_pull stays in the set, so its row is
+ * still found.  rows40_out may be yrwi_host_alloc memory (written directly when 8-byte
+ * aligned). */
+int yrwi_event_rows(yrwi_ctx* ctx, yrwi_event* ev, const uint8_t* urls12, int32_t n, uint8_t* rows40_out,
+                    uint8_t* found /* n bytes */);
 void yrwi_event_close(yrwi_ctx* ctx, yrwi_event* ev);
 
 /* ---- index abstracts and the secondary search ---- */

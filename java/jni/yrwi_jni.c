@@ -497,6 +497,55 @@ JNIEXPORT jint JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_eventAdd(JNIEnv* env, j
   return rc;
 }
 
+/* addRWIs(termSearch.joined(), local = true) without the rows leaving the device
+ * (yrwi_event_add_local): the joined and excluded container of the terms (sel: a url
+ * selection or NULL) arrives at the event.  Returns m, the rows that arrived (0: an empty
+ * container, the event is unchanged), or the (negative) error code. */
+JNIEXPORT jlong JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_eventAddLocal(JNIEnv* env, jclass c, jlong ctx, jlong ev,
+                                                                       jbyteArray incl, jint nincl, jbyteArray excl,
+                                                                       jint nexcl, jbyteArray sel, jint nsel,
+                                                                       jint maxd, jlong now) {
+  jbyte* ib = (*env)->GetByteArrayElements(env, incl, NULL);
+  jbyte* eb = (*env)->GetByteArrayElements(env, excl, NULL);
+  jbyte* sb = sel ? (*env)->GetByteArrayElements(env, sel, NULL) : NULL;
+  yrwi_query_desc q;
+  memset(&q, 0, sizeof(q));
+  q.incl = (const uint8_t*)ib; q.nincl = nincl;
+  q.excl = (const uint8_t*)eb; q.nexcl = nexcl;
+  q.max_distance = maxd; q.k = 1; q.now_ms = now;
+  q.urlselection = (const uint8_t*)sb; q.nurlselection = sb ? nsel : 0;
+  yrwi_local_arrival a;
+  memset(&a, 0, sizeof(a));
+  a.ev = (yrwi_event*)(intptr_t)ev;
+  a.q = &q;
+  int rc = yrwi_event_add_local((yrwi_ctx*)(intptr_t)ctx, &a, 1, NULL);
+  (*env)->ReleaseByteArrayElements(env, incl, ib, JNI_ABORT);
+  (*env)->ReleaseByteArrayElements(env, excl, eb, JNI_ABORT);
+  if (sb) (*env)->ReleaseByteArrayElements(env, sel, sb, JNI_ABORT);
+  return rc == 0 ? (jlong)a.m : (jlong)rc;
+}
+
+/* The rows the event retained for n url hashes (yrwi_event_rows): n * 40 row bytes followed
+ * by n found bytes (1: the url's admitted posting arrived through eventAddLocal, its row is
+ * there; 0: 40 zero bytes) */
+JNIEXPORT jbyteArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_eventRows(JNIEnv* env, jclass c, jlong ctx, jlong ev,
+                                                                        jbyteArray urls, jint n) {
+  uint8_t* u = copy_in(env, urls, (int64_t)n * 12);
+  if (!u) return NULL;
+  const size_t nn = (size_t)(n > 0 ? n : 1);
+  uint8_t* out = (uint8_t*)malloc(nn * 41);
+  int rc = out ? yrwi_event_rows((yrwi_ctx*)(intptr_t)ctx, (yrwi_event*)(intptr_t)ev, u, n, out, out + (size_t)n * 40)
+               : YRWI_E_NOMEM;
+  free(u);
+  jbyteArray res = NULL;
+  if (rc == 0) {
+    res = (*env)->NewByteArray(env, (jsize)(n * 41));
+    (*env)->SetByteArrayRegion(env, res, 0, (jsize)(n * 41), (const jbyte*)out);
+  }
+  free(out);
+  return res;
+}
+
 /* ReferenceOrder.normalizeWith + cardinal continuing the event's ReferenceOrder
  * (yrwi_event_order): one score per row of the container, in its order */
 JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_eventOrder(JNIEnv* env, jclass c, jlong ctx, jlong ev,

@@ -12,6 +12,7 @@
 //   search/query/SearchEvent.java:612-631      -> GpuRWI.query(...) (whole local RWI path)
 //   search/query/SearchEvent.java:736-806,1297 -> GpuRWI.queryFiltered(...) (constraints, doubledom)
 //   search/query/SearchEvent.java:612-631,1297 -> GpuRWI.queryRows(...) (the hits with their joined postings: rwiStack elements)
+//   search/query/SearchEvent.java:612-631,651  -> GpuRWI.eventAddLocal(...) (the local container into a GpuRWIStack event, device to device)
 //   kelondro/rwi/IndexCell.java:353-386        -> GpuRWI.loadHeaps(...) (BLOB heaps into HBM)
 //   kelondro/rwi/IndexCell.java:131-166        -> GpuRWI.dumpHeap(...) (the FlushThread dump: HBM into a BLOB heap)
 //
@@ -322,6 +323,30 @@ public final class GpuRWI implements AutoCloseable {
         check(eventAdd(this.ctx, event, containerRows, n, local));
     }
 
+    /** addRWIs(termSearch.joined(), local = true) for an index that is this GpuRWI's
+     *  (yrwi_event_add_local): the joined and excluded container of the terms arrives at
+     *  the event without its rows leaving the device; urlselection as termSearch takes it,
+     *  or null.  Returns the rows that arrived (0: an empty container, the event and its
+     *  arrival numbering are unchanged).  Not on a shard of a sharded index. */
+    public synchronized long eventAddLocal(final long event, final byte[][] include, final byte[][] exclude,
+                                           final byte[][] urlselection, final int maxDistance, final long nowMillis) {
+        final long m = eventAddLocal(this.ctx, event, flatten(include), include.length, flatten(exclude),
+                                     exclude.length, urlselection == null ? null : flatten(urlselection),
+                                     urlselection == null ? 0 : urlselection.length, maxDistance, nowMillis);
+        if (m < 0) check((int) m);
+        return m;
+    }
+
+    /** The rows the event retained from eventAddLocal arrivals for n url hashes (12 bytes each;
+     *  yrwi_event_rows): n * 40 row bytes, then n found bytes -- 1 where the url's admitted
+     *  posting arrived through eventAddLocal, 0 (and 40 zero bytes) where the url is not in the
+     *  doublecheck set, was seeded, or came from an addRWIs arrival (the caller has those rows). */
+    public synchronized byte[] eventRows(final long event, final byte[] urls, final int n) {
+        final byte[] r = eventRows(this.ctx, event, urls, n);
+        if (r == null) throw new IllegalStateException("yrwi_event_rows failed");
+        return r;
+    }
+
     /** ReferenceOrder.normalizeWith(container, local) + cardinal of every row, continuing
      *  the event's ReferenceOrder (yrwi_event_order): min/max, the max-distance fold and
      *  the host counts accumulate over every container given to the event; the scores
@@ -451,6 +476,9 @@ public final class GpuRWI implements AutoCloseable {
     private static native long eventOpenOrder(long ctx, int[] profile32, String language, long nowMillis,
                                               long maxHosts);
     private static native int eventAdd(long ctx, long event, byte[] rows, int n, boolean local);
+    private static native long eventAddLocal(long ctx, long event, byte[] incl, int nincl, byte[] excl, int nexcl,
+                                             byte[] sel, int nsel, int maxDistance, long nowMillis);
+    private static native byte[] eventRows(long ctx, long event, byte[] urls, int n);
     private static native byte[] eventResult(long ctx, long event, int maxn);
     private static native long[] eventOrder(long ctx, long event, byte[] rows, int n, boolean local);
     private static native int[] eventAuthority(long ctx, long event, byte[] hosts6, int n);

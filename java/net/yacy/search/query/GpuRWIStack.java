@@ -108,6 +108,21 @@ public final class GpuRWIStack implements AutoCloseable {
         return n;
     }
 
+    /** add(termSearch.joined(), true) when the index is the GPU's (RWIProcess.run :612-631,
+     *  the sitehost retry :651): the joined and excluded container arrives from the device
+     *  index (yrwi_event_add_local) and no row crosses to Java.  The event keeps the rows;
+     *  pull() fetches those of the pulled entries (yrwi_event_rows).  Returns the rows that
+     *  arrived. */
+    public synchronized long addLocal(final byte[][] include, final byte[][] exclude, final int maxDistance) {
+        if (this.closed) return 0;
+        final long m = this.gpu.eventAddLocal(this.event, include, exclude, null, maxDistance, System.currentTimeMillis());
+        if (m > 0) {  // an empty container is no arrival (as add): the arrival numbers stay aligned
+            this.rows.add(null);  // its rows are on the device
+            this.local.add(Boolean.TRUE);
+        }
+        return m;
+    }
+
     /** SearchEvent.pullOneRWI(skipDoubleDom) up to maxn times: the entries in pull order,
      *  each the posting the doublecheck admitted for its url (yrwi_event_source: the
      *  url's first posting that passed the constraints, in whichever arrival) with its
@@ -124,11 +139,22 @@ public final class GpuRWIStack implements AutoCloseable {
         for (int h = 0; h < n; h++) System.arraycopy(hits, 24 * h, urls, 12 * h, 12);
         final int[] src = this.gpu.eventSource(this.event, urls, n);  // arrival (1-based), row per hit
         final ByteBuffer b = ByteBuffer.wrap(hits).order(ByteOrder.LITTLE_ENDIAN);
+        // entries admitted from a device-local arrival: their rows come from the event (one call)
+        byte[] kept = null;
+        for (int h = 0; h < n && kept == null; h++) {
+            final int a = src[2 * h] - 1;
+            if (a >= 0 && a < this.rows.size() && this.rows.get(a) == null) kept = this.gpu.eventRows(this.event, urls, n);
+        }
         for (int h = 0; h < n; h++) {
             final int a = src[2 * h] - 1, row = src[2 * h + 1];
             if (a < 0 || a >= this.rows.size()) continue;  // (cannot happen: every stack entry came from an arrival)
             final byte[] rb = new byte[ROW];
-            System.arraycopy(this.rows.get(a), row * ROW, rb, 0, ROW);
+            if (this.rows.get(a) != null) {
+                System.arraycopy(this.rows.get(a), row * ROW, rb, 0, ROW);
+            } else {
+                if (kept == null || kept[ROW * n + h] == 0) continue;  // (cannot happen: the event retained the arrival)
+                System.arraycopy(kept, ROW * h, rb, 0, ROW);
+            }
             // (WordReferenceRow's Row.Entry constructor is protected: the factory's produceSlow)
             final WordReference wr = Segment.wordReferenceFactory.produceSlow(WordReferenceRow.urlEntryRow.newEntry(rb));
             out.add(new WeakPriorityBlockingQueue.ReverseElement<WordReferenceVars>(

@@ -86,6 +86,17 @@ class CArrival(ctypes.Structure):
                 ("local", ctypes.c_int32), ("rc", ctypes.c_int32)]
 
 
+class CLocalArrival(ctypes.Structure):
+    _fields_ = [("ev", ctypes.c_void_p), ("q", ctypes.POINTER(CQuery)), ("m", ctypes.c_int64),
+                ("rc", ctypes.c_int32)]
+
+
+class CLocalStats(ctypes.Structure):
+    _fields_ = [("rows_joined", ctypes.c_int64), ("rows_arrived", ctypes.c_int64), ("bytes_h2d", ctypes.c_int64),
+                ("bytes_d2h", ctypes.c_int64), ("launches_tail", ctypes.c_int32), ("syncs", ctypes.c_int32),
+                ("t_total_ns", ctypes.c_int64), ("device_allocs", ctypes.c_int64)]
+
+
 class CEventInfo(ctypes.Structure):
     _fields_ = [("flagcount", ctypes.c_int32 * 32), ("postings_in", ctypes.c_int64),
                 ("admitted_local", ctypes.c_int64), ("admitted_remote", ctypes.c_int64),
@@ -196,6 +207,9 @@ SIGNATURES = {
     "yrwi_event_open_order": (ctypes.c_int, [_VP, ctypes.POINTER(CProfile), ctypes.c_char_p, ctypes.c_int64,
                                              ctypes.c_int64, _VP]),
     "yrwi_event_add": (ctypes.c_int, [_VP, ctypes.POINTER(CArrival), ctypes.c_int32]),
+    "yrwi_event_add_local": (ctypes.c_int, [_VP, ctypes.POINTER(CLocalArrival), ctypes.c_int32,
+                                            ctypes.POINTER(CLocalStats)]),
+    "yrwi_event_rows": (ctypes.c_int, [_VP, _VP, ctypes.c_char_p, ctypes.c_int32, _VP, _VP]),
     "yrwi_event_result": (ctypes.c_int, [_VP, _VP, ctypes.POINTER(CHit), ctypes.c_int32,
                                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(CEventInfo)]),
     "yrwi_check_url_ids": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),

@@ -33,9 +33,48 @@ struct yrwi_event {
   // table (postings given since the last exact count); the table grows before a
   // container could fill it (grow_host_table)
   int64_t hosts_bound = 0;
+  // rows retained from the event's device-local arrivals (yrwi_event_add_local), by the
+  // epoch each became; every entry holds a reference on its block (CtxBase::local_blocks)
+  struct LocalRows {
+    int32_t epoch, n;
+    const uint8_t* rows;
+    CtxBase::LocalBlock* blk;
+  };
+  std::vector<LocalRows> local;
 };
 
 namespace {
+
+// Arrivals grouped by event (first-appearance order), their order kept inside a group:
+// members[g] = the indices into arr of event evs[g]'s arrivals.
+struct EvGroups {
+  std::vector<yrwi_event*> evs;
+  std::vector<std::vector<int32_t>> members;
+};
+template <class A>
+EvGroups group_by_event(const A* arr, int32_t narr) {
+  EvGroups G;
+  std::unordered_map<const yrwi_event*, int32_t> gid;
+  for (int32_t i = 0; i < narr; i++)
+    if (gid.emplace(arr[i].ev, (int32_t)G.evs.size()).second) G.evs.push_back(arr[i].ev);
+  G.members.resize(G.evs.size());
+  for (int32_t i = 0; i < narr; i++) G.members[(size_t)gid[arr[i].ev]].push_back(i);
+  return G;
+}
+
+// drops the event's references on retained rows; a block nobody holds any more is freed
+// (no kernel reads it: the caller synchronised the event's lane)
+void release_local_rows(yrwi_ctx* ctx, yrwi_event* ev) {
+  for (auto& r : ev->local) {
+    if (--r.blk->refs > 0) continue;
+    auto& v = ctx->local_blocks;
+    v.erase(std::remove(v.begin(), v.end(), r.blk), v.end());
+    ctx->local_bytes -= r.blk->bytes;
+    hipFree(r.blk->mem);
+    delete r.blk;
+  }
+  ev->local.clear();
+}
 
 int ceil_log2(int64_t x) {
   int l = 0;
@@ -239,12 +278,9 @@ extern "C" int yrwi_event_add(yrwi_ctx* ctx, yrwi_arrival* arr, int32_t narr) {
   Lane* L = ctx->lanes[0];
   if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
   // group the arrivals by event (first-appearance order), keeping their order inside a group
-  std::unordered_map<const yrwi_event*, int32_t> gid;
-  std::vector<const yrwi_event*> evs;
-  for (int32_t i = 0; i < narr; i++)
-    if (gid.emplace(arr[i].ev, (int32_t)evs.size()).second) evs.push_back(arr[i].ev);
-  std::vector<std::vector<int32_t>> members(evs.size());
-  for (int32_t i = 0; i < narr; i++) members[(size_t)gid[arr[i].ev]].push_back(i);
+  const EvGroups G = group_by_event(arr, narr);
+  const std::vector<yrwi_event*>& evs = G.evs;
+  const std::vector<std::vector<int32_t>>& members = G.members;
   int64_t total = 0;
   for (int32_t i = 0; i < narr; i++) total += arr[i].n;
   uint8_t* d_rows = arena_alloc<uint8_t>(L, total * YRWI_ROW_BYTES);
@@ -287,6 +323,176 @@ extern "C" int yrwi_event_add(yrwi_ctx* ctx, yrwi_arrival* arr, int32_t narr) {
   for (size_t j = 0; j < job_arr.size(); j++) {
     arr[job_arr[j]].rc = st[j];
     if (st[j] && !first) first = st[j];
+  }
+  if (first == YRWI_E_HASH) return ctx->fail(first, "arrival: url hash is not well-formed Base64");
+  if (first == YRWI_E_NULL_LANGUAGE) return ctx->fail(first, "arrival: row with empty language cell (reference NPE)");
+  if (first == YRWI_E_CAPACITY) return ctx->fail(first, "event tables full: max_postings too small");
+  return first;
+}
+
+// The local container of every arrival straight from the index: the planning and join steps of
+// yrwi_term_search over the whole call (join_containers), k_local_rows from each plan's container
+// to the arrival's 40-byte rows in a block the events keep, then k_event_add over those rows.  The
+// kept count of an arrival exists only on the device until the final readback: k_local_scan writes
+// it into the uploaded EvJob, k_local_fin returns it with the statuses and the events' epochs.
+extern "C" int yrwi_event_add_local(yrwi_ctx* ctx, yrwi_local_arrival* arr, int32_t narr, yrwi_local_stats* st) {
+  if (st) std::memset(st, 0, sizeof(*st));
+  if (!ctx || narr < 0 || (narr > 0 && !arr)) return YRWI_E_ARG;
+  EVENT_LOCK(ctx);
+  if (narr == 0) return 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int32_t i = 0; i < narr; i++) {
+    arr[i].rc = 0;
+    arr[i].m = 0;
+    if (!arr[i].ev || !arr[i].q) return ctx->fail(YRWI_E_ARG, "bad arrival");
+    if (!arr[i].ev->h.ukey) return ctx->fail(YRWI_E_ARG, "an order-only event takes no arrivals");
+  }
+  if (ctx->world > 1)
+    return ctx->fail(YRWI_E_UNSUPPORTED, "device-local arrivals on a shard: events are not combined across ranks");
+  hipSetDevice(ctx->device);
+  drain(ctx);
+  Lane* L = ctx->lanes[0];
+  const int64_t sync0 = L->n_sync, up0 = L->up_bytes, down0 = L->down_bytes, realloc0 = t_realloc;
+  std::vector<const yrwi_query_desc*> qs((size_t)narr);
+  for (int32_t i = 0; i < narr; i++) qs[(size_t)i] = arr[i].q;
+  std::vector<Plan> plans;
+  L->chain_groups_on_device = true;  // no table of the join phase grows with the lists
+  const int jrc = join_containers(ctx, L, qs.data(), narr, &plans);
+  L->chain_groups_on_device = false;
+  if (jrc) return jrc;
+  int32_t tail = 0;  // launches, copies and memsets from here on
+
+  const EvGroups G = group_by_event(arr, narr);
+  const int32_t nev = (int32_t)G.evs.size();
+  int64_t total = 0;
+  for (const Plan& P : plans) {
+    const int64_t n = P.empty ? 0 : P.cont.n;
+    if (n >= ((int64_t)1 << 31)) return ctx->fail(YRWI_E_LIMIT, "container too long for an arrival");
+    total += n;
+  }
+  // the one allocation of the call: room for every arrival's rows before exclusion
+  CtxBase::LocalBlock* blk = nullptr;
+  if (total > 0) {
+    void* mem = nullptr;
+    note_realloc("event local rows", (size_t)total * YRWI_ROW_BYTES);
+    if (hipMalloc(&mem, (size_t)total * YRWI_ROW_BYTES) != hipSuccess)
+      return ctx->fail(YRWI_E_NOMEM, "retained rows of the local arrivals");
+    blk = new CtxBase::LocalBlock{mem, (size_t)total * YRWI_ROW_BYTES, 0};
+  }
+  // until an event holds rows in it, a failure gives the block back (after the lane's work)
+  auto bail = [&](int code, const char* m) {
+    if (blk) {
+      lane_sync(L);
+      hipFree(blk->mem);
+      delete blk;
+    }
+    return m ? ctx->fail(code, m) : ctx->take(L, code);
+  };
+  std::vector<EvDev> hev;
+  std::vector<EvJob> jobs;
+  std::vector<LocalJob> ljobs;
+  std::vector<int64_t> tile_base;
+  std::vector<int32_t> jb{0}, job_arr;
+  int64_t roff = 0, tiles = 0;
+  for (int32_t g = 0; g < nev; g++) {
+    hev.push_back(G.evs[(size_t)g]->h);
+    for (int32_t i : G.members[(size_t)g]) {
+      const Plan& P = plans[(size_t)i];
+      const int64_t n = P.empty ? 0 : P.cont.n;
+      EvJob J{};
+      J.ev = g;
+      J.local = 1;
+      J.n = 0;  // k_local_scan: the rows that remain after exclusion
+      if (n > 0) {
+        LocalJob Lj{};
+        Lj.rows = P.cont.rows;  // a single include list is taken as it is stored (:355-370)
+        Lj.feat = P.cont.feat;
+        Lj.uid = P.cont.uid;
+        Lj.removed = P.removed;
+        Lj.n = n;
+        Lj.now_ms = P.now_ms;
+        Lj.out = static_cast<uint8_t*>(blk->mem) + roff * YRWI_ROW_BYTES;
+        Lj.tile0 = tiles;
+        Lj.evjob = (int32_t)jobs.size();
+        J.rows = Lj.out;
+        tile_base.push_back(tiles);
+        tiles += (n + LR_TILE - 1) / LR_TILE;
+        roff += n;
+        ljobs.push_back(Lj);
+      }
+      jobs.push_back(J);
+      job_arr.push_back(i);
+    }
+    jb.push_back((int32_t)jobs.size());
+  }
+  const int32_t nlj = (int32_t)ljobs.size();
+  EvDev* d_ev = arena_alloc<EvDev>(L, nev);
+  EvJob* d_jobs = arena_alloc<EvJob>(L, narr);
+  int32_t* d_jb = arena_alloc<int32_t>(L, (int64_t)nev + 1);
+  int32_t* d_status = arena_alloc<int32_t>(L, narr);
+  LocalJob* d_ljobs = arena_alloc<LocalJob>(L, nlj);
+  int64_t* d_tb = arena_alloc<int64_t>(L, nlj);
+  int32_t* d_tcnt = arena_alloc<int32_t>(L, tiles);
+  int64_t* d_fin = arena_alloc<int64_t>(L, 2 * (int64_t)narr + nev);
+  if (!d_ev || !d_jobs || !d_jb || !d_status || !d_ljobs || !d_tb || !d_tcnt || !d_fin)
+    return bail(YRWI_E_NOMEM, "arena");
+  hipStream_t s = L->stream;
+  if (upload(L, d_ev, hev, d_jobs, jobs, d_jb, jb, d_ljobs, ljobs, d_tb, tile_base)) return bail(YRWI_E_HIP, nullptr);
+  tail += 1;
+  if (launch_local_rows(d_ljobs, d_tb, nlj, tiles, ctx->dkhi, ctx->dklo, d_tcnt, d_jobs, s))
+    return bail(YRWI_E_HIP, "local rows launch");
+  tail += 3;
+  if (launch_event_add(d_ev, d_jobs, d_jb, nev, d_status, s)) return bail(YRWI_E_HIP, "event_add launch");
+  if (launch_local_fin(d_ev, nev, d_jobs, d_status, narr, d_fin, s)) return bail(YRWI_E_HIP, "local fin launch");
+  const uint8_t* fb = readback(L, &L->down_stage, d_fin, 2 * (int64_t)narr + nev, 8, 8);
+  if (!fb) return bail(YRWI_E_HIP, nullptr);
+  tail += 3;
+  if (lane_sync(L) != hipSuccess) return bail(YRWI_E_HIP, "event_add_local sync");
+  std::vector<int64_t> fin((size_t)(2 * (int64_t)narr + nev));
+  std::memcpy(fin.data(), fb, fin.size() * 8);
+  // every arrival that was applied (rows and no error) took the event's next epoch: the last
+  // of them has the epoch the event reports now
+  int first = 0;
+  int64_t arrived = 0;
+  size_t lj = 0;
+  for (int32_t g = 0; g < nev; g++) {
+    int32_t applied = 0;
+    for (int32_t j = jb[(size_t)g]; j < jb[(size_t)g + 1]; j++)
+      applied += fin[(size_t)j] > 0 && fin[(size_t)(narr + j)] == 0;
+    int32_t ep = (int32_t)fin[(size_t)(2 * (int64_t)narr + g)] - applied;
+    for (int32_t j = jb[(size_t)g]; j < jb[(size_t)g + 1]; j++) {
+      yrwi_local_arrival& A = arr[job_arr[(size_t)j]];
+      const int32_t rc = (int32_t)fin[(size_t)(narr + j)];
+      A.m = fin[(size_t)j];
+      A.rc = rc;
+      arrived += A.m;
+      if (rc && !first) first = rc;
+      const bool has_rows = jobs[(size_t)j].rows != nullptr;
+      if (A.m > 0 && rc == 0) {
+        A.ev->local.push_back({++ep, (int32_t)A.m, ljobs[lj].out, blk});
+        blk->refs++;
+      }
+      if (has_rows) lj++;
+    }
+  }
+  if (blk) {
+    if (blk->refs > 0) {
+      ctx->local_blocks.push_back(blk);
+      ctx->local_bytes += blk->bytes;
+    } else {  // every container was emptied by its exclusion, or refused
+      hipFree(blk->mem);
+      delete blk;
+    }
+  }
+  if (st) {
+    st->rows_joined = total;
+    st->rows_arrived = arrived;
+    st->bytes_h2d = L->up_bytes - up0;
+    st->bytes_d2h = L->down_bytes - down0;
+    st->launches_tail = tail;
+    st->syncs = (int32_t)(L->n_sync - sync0);
+    st->device_allocs = t_realloc - realloc0;
+    st->t_total_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
   }
   if (first == YRWI_E_HASH) return ctx->fail(first, "arrival: url hash is not well-formed Base64");
   if (first == YRWI_E_NULL_LANGUAGE) return ctx->fail(first, "arrival: row with empty language cell (reference NPE)");
@@ -467,6 +673,51 @@ extern "C" int yrwi_event_source(yrwi_ctx* ctx, yrwi_event* ev, const uint8_t* u
   return 0;
 }
 
+extern "C" int yrwi_event_rows(yrwi_ctx* ctx, yrwi_event* ev, const uint8_t* urls12, int32_t n, uint8_t* rows40_out,
+                               uint8_t* found) {
+  if (!ctx || !ev || n < 0 || (n > 0 && (!urls12 || !rows40_out || !found))) return YRWI_E_ARG;
+  if (n == 0) return 0;
+  if (!ev->h.ukey) return ctx->fail(YRWI_E_ARG, "an order-only event has no url set");
+  EVENT_LOCK(ctx);
+  std::vector<uint64_t> hi((size_t)n);
+  std::vector<uint8_t> lo((size_t)n);
+  for (int32_t i = 0; i < n; i++) {
+    KeyT k;
+    if (!key_of(urls12 + 12 * (size_t)i, &k)) return ctx->fail(YRWI_E_HASH, "url hash is not well-formed Base64");
+    hi[(size_t)i] = k.hi;
+    lo[(size_t)i] = (uint8_t)k.lo;
+  }
+  hipSetDevice(ctx->device);
+  drain(ctx);
+  Lane* L = ctx->lanes[0];
+  if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
+  std::vector<LocalBlk> blks;
+  for (const auto& r : ev->local) blks.push_back(LocalBlk{r.rows, r.epoch, r.n});
+  uint64_t* d_hi = arena_alloc<uint64_t>(L, n);
+  uint8_t* d_lo = arena_alloc<uint8_t>(L, n);
+  EvDev* d_ev = arena_alloc<EvDev>(L, 1);
+  LocalBlk* d_blk = arena_alloc<LocalBlk>(L, (int64_t)blks.size());
+  if (!d_hi || !d_lo || !d_ev || !d_blk) return ctx->fail(YRWI_E_NOMEM, "arena");
+  std::vector<EvDev> hev{ev->h};
+  if (upload(L, d_ev, hev, d_hi, hi, d_lo, lo, d_blk, blks)) return ctx->take(L, YRWI_E_HIP);
+  // the kernel writes pinned host memory: the caller's buffer when it came from yrwi_host_alloc
+  // and is 8-byte aligned (store_row), else the lane's landing buffer; `found` lands behind the rows
+  const size_t rb = (size_t)n * YRWI_ROW_BYTES;
+  const bool direct = (reinterpret_cast<uintptr_t>(rows40_out) & 7) == 0 && ctx->hostreg.contains(rows40_out, rb);
+  uint8_t* land = stage_reserve(L, &L->out_stage, rb + (size_t)n, true);
+  if (!land) return ctx->take(L, YRWI_E_HIP);
+  uint8_t* d_rows = nullptr;
+  uint8_t* d_found = nullptr;
+  HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&d_rows), direct ? rows40_out : land, 0));
+  HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&d_found), land + rb, 0));
+  if (launch_event_rows(d_ev, d_blk, (int32_t)blks.size(), d_hi, d_lo, n, d_rows, d_found, L->stream))
+    return ctx->fail(YRWI_E_HIP, "event_rows launch");
+  HIPCHK(ctx, lane_sync(L));
+  if (!direct) std::memcpy(rows40_out, land, rb);
+  std::memcpy(found, land + rb, (size_t)n);
+  return 0;
+}
+
 extern "C" int yrwi_event_result(yrwi_ctx* ctx, yrwi_event* ev, yrwi_hit* out, int32_t maxn, int32_t* nout,
                                  yrwi_event_info* info) {
   if (!ctx || !ev || maxn < 0 || (maxn > 0 && !out)) return YRWI_E_ARG;
@@ -615,6 +866,7 @@ extern "C" void yrwi_event_close(yrwi_ctx* ctx, yrwi_event* ev) {
     }
     drain(ctx);
     lane_sync(ctx->lanes[0]);
+    release_local_rows(ctx, ev);
   }
   hipFree(ev->mem);
   delete ev;

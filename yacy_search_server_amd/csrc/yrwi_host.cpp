@@ -394,6 +394,13 @@ extern "C" void yrwi_close(yrwi_ctx* ctx) {
   ctx->devx = nullptr;
   for (auto& b : ctx->ev_pool) hipFree(b.second);
   ctx->ev_pool.clear();
+  // rows retained for events the caller left open (their handles die with the context)
+  for (auto* b : ctx->local_blocks) {
+    hipFree(b->mem);
+    delete b;
+  }
+  ctx->local_blocks.clear();
+  ctx->local_bytes = 0;
   if (ctx->dump_dev) hipFree(ctx->dump_dev);
   if (ctx->dump_host) hipHostFree(ctx->dump_host);
   if (ctx->host_key) hipFree(ctx->host_key);
@@ -531,9 +538,10 @@ extern "C" int yrwi_index_stats(yrwi_ctx* ctx, int64_t* nterms, int64_t* npostin
   if (nterms) *nterms = (int64_t)ctx->lists.size();
   if (npostings) *npostings = ctx->npostings;
   if (device_bytes) {
-    // index memory, url ids, line heads, bitmaps, url dictionary, lane scratch
+    // index memory, url ids, line heads, bitmaps, url dictionary, lane scratch, and the rows
+    // open events retain from device-local arrivals
     size_t b = ctx->index_mem.capacity() + ctx->uid_cap * 4 + ctx->head_cap * 4 + ctx->bm_cap * 8 +
-               ctx->dict_cap * 9;
+               ctx->dict_cap * 9 + ctx->local_bytes;
     for (Lane* L : ctx->lanes) b += L->arena.capacity();
     *device_bytes = (int64_t)b;
   }
@@ -1129,6 +1137,9 @@ static int run_join_jobs(Lane* ctx, std::vector<Plan>& plans, std::vector<JoinQ>
   ChainQ* d_cq = nullptr;
   std::vector<int2> cgrp;  // chain groups: runs of up to CHAIN_GMAX merge tiles of one chained job (k_chain)
   int2* d_cgrp = nullptr;
+  // Lane::chain_groups_on_device: one entry per chained job instead, expanded by k_chain_groups
+  std::vector<ChainGroupJob> cgj;
+  ChainGroupJob* d_cgj = nullptr;
   if (chain) {
     // a group holds about 640 expected matches (independent lists: nA nB / nurls
     // per job), so a workgroup tests close to one round of 768
@@ -1141,6 +1152,8 @@ static int run_join_jobs(Lane* ctx, std::vector<Plan>& plans, std::vector<JoinQ>
       if (J.chain_bm)  // the probe already thinned the matches by the first later include
         per_tile *= std::min(1.0, (double)Cq.l[0].n / (double)std::max<int64_t>(1, ctx->nurls));
       const int G = (int)std::max(1.0, std::min((double)CHAIN_GMAX, 640.0 / std::max(1.0, per_tile)));
+      if (ctx->chain_groups_on_device)
+        cgj.push_back(ChainGroupJob{(int32_t)cgrp.size(), (int32_t)tile_base[(size_t)j], (int32_t)J.ntiles, G});
       for (int64_t t = 0; t < J.ntiles; t += G)
         cgrp.push_back(make_int2((int32_t)(tile_base[(size_t)j] + t), (int32_t)std::min<int64_t>(G, J.ntiles - t)));
     }
@@ -1171,9 +1184,15 @@ static int run_join_jobs(Lane* ctx, std::vector<Plan>& plans, std::vector<JoinQ>
       cq.push_back(C);
     }
   }
-  if (chain ? upload(ctx, d_jobs, jobs, d_tb, tile_base, d_cq, cq, d_cgrp, cgrp)
-            : upload(ctx, d_jobs, jobs, d_tb, tile_base))
+  if (chain && ctx->chain_groups_on_device) {
+    if (!(d_cgj = arena_alloc<ChainGroupJob>(ctx, (int64_t)cgj.size()))) return ctx->fail(YRWI_E_NOMEM, "arena");
+    if (upload(ctx, d_jobs, jobs, d_tb, tile_base, d_cq, cq, d_cgj, cgj)) return YRWI_E_HIP;
+    if (launch_chain_groups(d_cgj, (int32_t)cgj.size(), d_cgrp, (int64_t)cgrp.size(), ctx->stream))
+      return ctx->fail(YRWI_E_HIP, "chain groups launch");
+  } else if (chain ? upload(ctx, d_jobs, jobs, d_tb, tile_base, d_cq, cq, d_cgrp, cgrp)
+                   : upload(ctx, d_jobs, jobs, d_tb, tile_base)) {
     return YRWI_E_HIP;
+  }
   hipEvent_t e0 = tm ? ctx->event() : nullptr, em = tm ? ctx->event() : nullptr, e1 = tm ? ctx->event() : nullptr;
   hipEvent_t c0 = tm ? ctx->event() : nullptr, c1 = tm ? ctx->event() : nullptr;
   hipEvent_t sp = span_open(ctx, tm);
@@ -2708,6 +2727,24 @@ extern "C" int yrwi_term_search(yrwi_ctx* ctx, const yrwi_query_desc* q, uint8_t
   }
   *m = k;
   return 0;
+}
+
+int yrwi::join_containers(yrwi_ctx* ctx, Lane* L, const yrwi_query_desc* const* q, int32_t nq,
+                          std::vector<Plan>* plans_out) {
+  if (int rc0 = ensure_url_ids(ctx)) return rc0;
+  std::vector<Plan>& plans = *plans_out;
+  plans.assign((size_t)nq, Plan());
+  for (int32_t i = 0; i < nq; i++) {
+    yrwi_query_desc d = *q[i];
+    d.k = 1;
+    d.filter = nullptr;
+    if (int rc = ctx->take(L, plan_query(ctx, L, d, &plans[(size_t)i]))) return rc;
+  }
+  int rc;
+  if ((rc = ctx->take(L, resolve_selections(L, plans)))) return rc;
+  if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
+  if ((rc = ctx->take(L, plan_batch(L, plans)))) return rc;
+  return ctx->take(L, run_join_phase(L, plans, nullptr, nullptr));
 }
 
 extern "C" int yrwi_normalize_score(yrwi_ctx* ctx, const uint8_t* rows40, int64_t m, const yrwi_profile* prof,

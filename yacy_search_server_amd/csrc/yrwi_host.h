@@ -301,6 +301,13 @@ struct Lane {
   bool active = false, reserving = false;
   int rc = 0;
   int64_t wait_ns = 0;  // host time spent waiting for this lane's device work (lane_sync)
+  // running totals since the lane was made (an entry point reports the difference over its call):
+  // host waits (lane_sync), bytes staged to the device (upload) and landed from it (readback)
+  int64_t n_sync = 0, up_bytes = 0, down_bytes = 0;
+  // the join phase writes its chain-group table on the device (k_chain_groups) instead of uploading
+  // one entry per group of tiles: set by yrwi_event_add_local for its call, whose bytes over PCIe
+  // must not depend on the list lengths
+  bool chain_groups_on_device = false;
   // scratch high-water mark of the context's lanes (bytes): a lane whose arena is
   // smaller takes that size at the start of its next pass instead of growing
   // inside it (one allocation, before any of the pass's kernels)
@@ -446,6 +453,15 @@ struct CtxBase {
   std::recursive_mutex api_mu;
   std::mutex ev_pool_mu;
   std::vector<std::pair<size_t, void*>> ev_pool;
+  // rows retained for the device-local arrivals of open events (yrwi_event_add_local): one block
+  // per call, shared by the call's events and freed with the last of them (or by yrwi_close)
+  struct LocalBlock {
+    void* mem;
+    size_t bytes;
+    int32_t refs;  // open events holding rows in it
+  };
+  std::vector<LocalBlock*> local_blocks;
+  size_t local_bytes = 0;  // of local_blocks
   // yrwi_dump_heap (yrwi_dump.hip): two device and two pinned windows of dump_cap bytes each,
   // allocated on the first dump and kept
   uint8_t* dump_dev = nullptr;
@@ -489,6 +505,7 @@ inline hipError_t lane_sync(Lane* L) {
   if (e != hipSuccess) return e;
   const auto t0 = std::chrono::steady_clock::now();
   e = hipEventSynchronize(L->sync_ev);
+  L->n_sync++;
   L->wait_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
   return e;
 }
@@ -544,6 +561,7 @@ inline int upload_list(Lane* ctx, const UpEnt* e, int n) {
     const size_t off = (S.used + 255) & ~(size_t)255;
     std::memcpy(S.p + off, e[i].src, e[i].bytes);
     S.used = off + e[i].bytes;
+    ctx->up_bytes += (int64_t)e[i].bytes;
     if (c.n == COPY_IN_MAX) {
       if (launch_copy_in(c, ctx->stream)) return ctx->fail(YRWI_E_HIP, "copy-in launch");
       c = CopyIn{};
@@ -587,6 +605,7 @@ inline uint8_t* readback(Lane* L, Stage* S, const void* d_src, int64_t n, int32_
     L->fail(YRWI_E_HIP, "readback launch");
     return nullptr;
   }
+  L->down_bytes += std::max<int64_t>(n, 0) * elem;
   return h;
 }
 
@@ -616,6 +635,11 @@ struct Xfer {
 };
 // (re)build the url dictionary and every list's url ids if the index changed
 int ensure_url_ids(CtxBase* ctx);
+// The joined containers of nq TermSearch descriptors, as yrwi_term_search computes one: planning,
+// url selections, a new pass on lane L, the join and exclusion phase.  Leaves plans[i].cont (n is
+// known on the host), plans[i].removed and plans[i].now_ms; the containers live in L's arena until
+// its next pass.  k, profile, language and filter of the descriptors are not read.
+int join_containers(yrwi_ctx* ctx, Lane* L, const yrwi_query_desc* const* q, int32_t nq, std::vector<Plan>* plans);
 // device memory left for the lanes' scratch after the index is resident (CtxBase::scratch_total)
 void measure_scratch(CtxBase* ctx);
 // dense host ids in every index record (after ensure_url_ids; no batch in flight)

@@ -585,4 +585,48 @@ int launch_event_where(const EvDev* d_ev, const uint64_t* d_hi, const uint8_t* d
 // seeds the url set with the doublecheck urls of the filter (epoch 0)
 int launch_event_seed(const EvDev* d_ev, const uint64_t* d_hi, const uint8_t* d_lo, int64_t n, void* stream);
 
+// The chain groups of a join step (launch_join_step's d_cgrp: runs of up to G merge tiles of one
+// chained job) written on the device from one entry per chained job, for a caller whose uploads
+// must not grow with the lists (yrwi_event_add_local); groups [gbase, gbase + ceil(ntiles / G))
+// of the job are (tile0 + i G, min(G, ntiles - i G)).
+struct ChainGroupJob {
+  int32_t gbase, tile0, ntiles, G;
+};
+int launch_chain_groups(const ChainGroupJob* d_cgj, int32_t njobs, int2* d_cgrp, int64_t ngroups, void* stream);
+
+// ---- device-local arrivals (yrwi_event_add_local): a joined container becomes an
+// arrival's rows without leaving the device
+constexpr int LR_TILE = 256;  // container rows per tile of k_local_rows (one per thread)
+struct LocalJob {
+  const uint8_t* rows;     // the container's rows as stored (a single include list), or nullptr:
+  const uint64_t* feat;    //   its records, re-encoded with the dictionary key of uid[i] (J6)
+  const uint32_t* uid;
+  const uint8_t* removed;  // Plan::removed (nullptr: no row is excluded)
+  int64_t n;               // container rows
+  int64_t now_ms;          // freshUntil of a re-encoded row
+  uint8_t* out;            // the arrival's retained rows (room for n)
+  int64_t tile0;           // the job's first tile; it has ceil(n / LR_TILE)
+  int32_t evjob;           // EvJob of the arrival: its n receives the kept count
+  int32_t pad;
+};
+// Order-preserving compaction of every job's container into its 40-byte rows, three launches
+// for the whole call: kept rows per tile, the tile counts scanned per job (EvJob::n = the job's
+// total), the rows written.  tile_base[j] = jobs[j].tile0; d_tile_cnt: `tiles` ints of scratch.
+int launch_local_rows(const LocalJob* d_jobs, const int64_t* d_tile_base, int32_t njobs, int64_t tiles,
+                      const uint64_t* dkhi, const uint8_t* dklo, int32_t* d_tile_cnt, EvJob* d_evjobs, void* stream);
+// what the host reads back after k_event_add, in one buffer of 2 njobs + nev words: out[j] =
+// d_evjobs[j].n and out[njobs + j] = d_status[j] of the njobs arrivals, out[2 njobs + e] = the
+// epoch event e has reached
+int launch_local_fin(const EvDev* d_ev, int32_t nev, const EvJob* d_evjobs, const int32_t* d_status, int32_t njobs,
+                     int64_t* d_out, void* stream);
+// the retained rows of an event's device-local arrivals, by epoch
+struct LocalBlk {
+  const uint8_t* rows;
+  int32_t epoch, n;
+};
+// row of each url's admitted posting when it arrived through a device-local arrival (found[i] = 1),
+// else 40 zero bytes and found[i] = 0; rows_out is 8-byte aligned and may be pinned host memory
+int launch_event_rows(const EvDev* d_ev, const LocalBlk* d_blk, int32_t nblk, const uint64_t* d_hi,
+                      const uint8_t* d_lo, int32_t n, uint8_t* rows_out, uint8_t* found, void* stream);
+
 }  // namespace yrwi

@@ -5472,4 +5472,152 @@ int launch_event_seed(const EvDev* d_ev, const uint64_t* d_hi, const uint8_t* d_
   return rc(hipGetLastError());
 }
 
+// ------------------------------------------------ device-local arrivals (yrwi_event_add_local)
+// A joined container becomes the rows of an event arrival without leaving the
+// device: what k_feat_rows and the host loop of yrwi_term_search do, for every
+// arrival of the call at once.  Tile t of the launch is LR_TILE consecutive
+// container rows of the job that find_job names (every job has rows, so the tile
+// bases ascend strictly); a row is kept unless Plan::removed marks it.
+__device__ __forceinline__ bool local_keep(const LocalJob& J, int64_t i) {
+  return i < J.n && !(J.removed && J.removed[i]);
+}
+
+__global__ __launch_bounds__(LR_TILE) void k_local_count(const LocalJob* __restrict__ jobs,
+                                                         const int64_t* __restrict__ tile_base, int32_t njobs,
+                                                         int32_t* __restrict__ tile_cnt) {
+  __shared__ int32_t sScan[4];
+  const int64_t t = blockIdx.x;
+  const LocalJob& J = jobs[find_job(tile_base, njobs, t)];
+  const int64_t i = (t - J.tile0) * LR_TILE + threadIdx.x;
+  int32_t tot;
+  block_excl_sum256(local_keep(J, i) ? 1 : 0, sScan, &tot);
+  if (threadIdx.x == 0) tile_cnt[t] = tot;
+}
+
+// one workgroup per job: its tile counts -> their exclusive sums (where each tile's kept rows
+// start in the arrival), the total into the arrival's EvJob (k_event_add reads it from there)
+__global__ __launch_bounds__(256) void k_local_scan(const LocalJob* __restrict__ jobs, int32_t* __restrict__ tile_cnt,
+                                                    EvJob* __restrict__ evjobs) {
+  __shared__ int32_t sScan[4];
+  const LocalJob& J = jobs[blockIdx.x];
+  const int64_t ntiles = (J.n + LR_TILE - 1) / LR_TILE;
+  int32_t* c = tile_cnt + J.tile0;
+  int32_t carry = 0;
+  for (int64_t b = 0; b < ntiles; b += 256) {
+    const int64_t x = b + threadIdx.x;
+    int32_t tot;
+    const int32_t off = block_excl_sum256(x < ntiles ? c[x] : 0, sScan, &tot);
+    if (x < ntiles) c[x] = carry + off;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) evjobs[J.evjob].n = carry;
+}
+
+__global__ __launch_bounds__(LR_TILE) void k_local_rows(const LocalJob* __restrict__ jobs,
+                                                        const int64_t* __restrict__ tile_base, int32_t njobs,
+                                                        const uint64_t* __restrict__ dkhi,
+                                                        const uint8_t* __restrict__ dklo,
+                                                        const int32_t* __restrict__ tile_off) {
+  __shared__ int32_t sScan[4];
+  const int64_t t = blockIdx.x;
+  const LocalJob& J = jobs[find_job(tile_base, njobs, t)];
+  const int64_t i = (t - J.tile0) * LR_TILE + threadIdx.x;
+  const bool keep = local_keep(J, i);
+  int32_t tot;
+  const int32_t off = block_excl_sum256(keep ? 1 : 0, sScan, &tot);
+  if (!keep) return;
+  Row r;
+  if (J.rows) {
+    r = load_row(J.rows + i * YRWI_ROW_BYTES);  // a single include list: as stored (:355-370)
+  } else {
+    const uint32_t u = J.uid[i];
+    r = row_of_rec(load_rec(J.feat, i), dkhi[u], dklo[u], J.now_ms);
+  }
+  store_row(J.out + ((int64_t)tile_off[t] + off) * YRWI_ROW_BYTES, r);
+}
+
+int launch_local_rows(const LocalJob* d_jobs, const int64_t* d_tile_base, int32_t njobs, int64_t tiles,
+                      const uint64_t* dkhi, const uint8_t* dklo, int32_t* d_tile_cnt, EvJob* d_evjobs, void* st) {
+  if (njobs <= 0 || tiles <= 0) return 0;
+  if (tiles > 0x7FFFFFFFLL) return -1;
+  hipLaunchKernelGGL(k_local_count, dim3((unsigned)tiles), dim3(LR_TILE), 0, S(st), d_jobs, d_tile_base, njobs,
+                     d_tile_cnt);
+  hipLaunchKernelGGL(k_local_scan, dim3((unsigned)njobs), dim3(256), 0, S(st), d_jobs, d_tile_cnt, d_evjobs);
+  hipLaunchKernelGGL(k_local_rows, dim3((unsigned)tiles), dim3(LR_TILE), 0, S(st), d_jobs, d_tile_base, njobs, dkhi,
+                     dklo, d_tile_cnt);
+  return rc(hipGetLastError());
+}
+
+__global__ void k_chain_groups(const ChainGroupJob* __restrict__ cgj, int32_t njobs, int2* __restrict__ cgrp,
+                               int64_t ngroups) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= ngroups) return;
+  int lo = 0, hi = njobs - 1;  // the last job whose first group is <= g (every job has a group)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (cgj[mid].gbase <= g) lo = mid; else hi = mid - 1;
+  }
+  const ChainGroupJob J = cgj[lo];
+  const int32_t t = (int32_t)(g - J.gbase) * J.G;
+  cgrp[g] = make_int2(J.tile0 + t, min(J.G, J.ntiles - t));
+}
+
+int launch_chain_groups(const ChainGroupJob* d_cgj, int32_t njobs, int2* d_cgrp, int64_t ngroups, void* st) {
+  if (njobs <= 0 || ngroups <= 0) return 0;
+  hipLaunchKernelGGL(k_chain_groups, dim3(nblk(ngroups)), dim3(256), 0, S(st), d_cgj, njobs, d_cgrp, ngroups);
+  return rc(hipGetLastError());
+}
+
+__global__ void k_local_fin(const EvDev* __restrict__ evs, int32_t nev, const EvJob* __restrict__ evjobs,
+                            const int32_t* __restrict__ status, int32_t njobs, int64_t* __restrict__ out) {
+  const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i < njobs) {
+    out[i] = evjobs[i].n;
+    out[njobs + i] = status[i];
+  } else if (i < njobs + nev) {
+    out[njobs + i] = evs[i - njobs].st->epoch;
+  }
+}
+
+int launch_local_fin(const EvDev* d_ev, int32_t nev, const EvJob* d_evjobs, const int32_t* d_status, int32_t njobs,
+                     int64_t* d_out, void* st) {
+  const int32_t n = nev + njobs;
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(k_local_fin, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(st), d_ev, nev, d_evjobs, d_status,
+                     njobs, d_out);
+  return rc(hipGetLastError());
+}
+
+// the row of each url's admitted posting, for postings that arrived through a device-local
+// arrival: the url set's (epoch << 32 | row) word (k_event_where) names the retained block
+__global__ void k_event_rows(const EvDev* __restrict__ ev, const LocalBlk* __restrict__ blk, int32_t nblk_,
+                             const uint64_t* __restrict__ hi, const uint8_t* __restrict__ lo, int32_t n,
+                             uint8_t* __restrict__ rows_out, uint8_t* __restrict__ found) {
+  const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const int64_t s = uset_find(ev->ukey, ev->ulog, hi[i], lo[i]);
+  const uint64_t v = s >= 0 ? ld_dev(ev->uval + s) : ~0ull;
+  Row r{};
+  uint8_t f = 0;
+  if (v != ~0ull) {
+    const int32_t ep = (int32_t)(v >> 32);
+    const uint32_t row = (uint32_t)v;
+    for (int32_t b = 0; b < nblk_; b++)
+      if (blk[b].epoch == ep && row < (uint32_t)blk[b].n) {
+        r = load_row(blk[b].rows + (int64_t)row * YRWI_ROW_BYTES);
+        f = 1;
+        break;
+      }
+  }
+  store_row(rows_out + (int64_t)i * YRWI_ROW_BYTES, r);
+  found[i] = f;
+}
+
+int launch_event_rows(const EvDev* d_ev, const LocalBlk* d_blk, int32_t nblk_, const uint64_t* d_hi,
+                      const uint8_t* d_lo, int32_t n, uint8_t* rows_out, uint8_t* found, void* st) {
+  if (n > 0) hipLaunchKernelGGL(k_event_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(st), d_ev, d_blk,
+                                nblk_, d_hi, d_lo, n, rows_out, found);
+  return rc(hipGetLastError());
+}
+
 }  // namespace yrwi

@@ -171,6 +171,26 @@ class SearchEvent:
     def add_rwis(self, rows: np.ndarray, local: bool = False) -> int:
         return self._ix.add_rwis([(self, rows, local)])[0]
 
+    def add_local(self, include: Sequence[bytes], exclude: Sequence[bytes] = (), max_distance: int = INTEGER_MAX,
+                  now_ms: int = 0, urlselection: Optional[Sequence[bytes]] = None) -> int:
+        """The local container of the event straight from the device index
+        (yrwi_event_add_local): what add_rwis(index.term_search(...), True) leaves, without
+        the rows crossing to the host.  Returns the rows that arrived."""
+        return self._ix.add_local_rwis([(self, Query(include, exclude, max_distance, 1, None, "en", now_ms, None,
+                                                     urlselection))])[0]
+
+    def rows(self, urlhashes: Sequence[bytes]) -> List[Optional[bytes]]:
+        """The 40-byte row of each url's admitted posting when it arrived through add_local
+        (yrwi_event_rows); None for a url that was not admitted, was seeded by the filter, or
+        came from an add_rwis arrival (the caller holds those rows, see source())."""
+        n = len(urlhashes)
+        out = np.zeros((max(1, n), 40), dtype=np.uint8)
+        found = np.zeros(max(1, n), dtype=np.uint8)
+        if n:
+            _check(self._ix._h, _lib.lib().yrwi_event_rows(self._ix._h, self._e, _hashes(urlhashes), n,
+                                                           out.ctypes.data, found.ctypes.data))
+        return [out[i].tobytes() if found[i] else None for i in range(n)]
+
     def order(self, rows: np.ndarray, local: bool = False) -> np.ndarray:
         """ReferenceOrder.normalizeWith(container, local) + cardinal of every row
         (yrwi_event_order): the container continues the event's ReferenceOrder
@@ -468,6 +488,29 @@ class RWIIndex:
         codes = [arr[i].rc for i in range(len(arrivals))]
         _check(self._h, rc)
         return codes
+
+    def add_local_rwis(self, arrivals: Sequence[Tuple["SearchEvent", "Query"]],
+                       stats: Optional["_lib.CLocalStats"] = None) -> List[int]:
+        """Applies (event, Query) device-local arrivals in order, events in parallel
+        (yrwi_event_add_local): each event receives the joined and excluded container of its
+        query (include, exclude, max_distance, now_ms, urlselection) as its local arrival.
+        Returns the rows that arrived per arrival; raises on the first error, the exception
+        carrying the per-arrival codes as `codes`.  stats: a CLocalStats to fill."""
+        n = len(arrivals)
+        if n == 0:
+            return []
+        cq, keep, _, _, _ = self._marshal([q for _, q in arrivals], 1)
+        arr = (_lib.CLocalArrival * n)()
+        for i, (ev, _) in enumerate(arrivals):
+            arr[i].ev = ev._e
+            arr[i].q = ctypes.pointer(cq[i])
+        rc = _lib.lib().yrwi_event_add_local(self._h, arr, n, ctypes.byref(stats) if stats is not None else None)
+        try:
+            _check(self._h, rc)
+        except YrwiError as e:
+            e.codes = [arr[i].rc for i in range(n)]
+            raise
+        return [arr[i].m for i in range(n)]
 
     # ---- index abstracts (compressIndex) and the secondary search ----
     def index_abstracts(self, terms: Sequence[bytes], exclude: Optional[bytes] = None) -> List[bytes]:
