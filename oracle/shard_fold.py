@@ -102,7 +102,7 @@ def _b64key(h: bytes):
 def shard_term_search(local: Dict[bytes, np.ndarray], incl: Sequence[bytes], excl: Sequence[bytes],
                       max_distance: int, now_ms: int, allsum: Callable[[List[int]], List[int]]) -> np.ndarray:
     """TermSearch + joinExcludeContainers on ONE url-hash shard, the way libyrwi
-    runs it (yrwi_host.cpp plan_query / run_join_phase).
+    runs it (yrwi_host.cpp plan_query / yrwi_join.cpp run_join_phase).
 
     Every decision the reference takes on container sizes is taken on the GLOBAL
     sizes -- the sum over shards, obtained with ``allsum`` (element-wise sum of a

@@ -42,8 +42,8 @@ VARIANTS["topq"] = [(K, TOPQ, 2)]
 # variants that change code rather than duplicate a launch: (file, old, new) edits
 H = "yrwi_host.cpp"
 def _compact_lds(kb):  # k_compact with kb KiB of unused dynamic LDS: fewer resident workgroups per CU
-    return [(K, "hipLaunchKernelGGL(kc, dim3((unsigned)((total_tiles + COMPACT_TILES - 1) / COMPACT_TILES)), dim3(256), 0, S(st),",
-             "hipLaunchKernelGGL(kc, dim3((unsigned)((total_tiles + COMPACT_TILES - 1) / COMPACT_TILES)), dim3(256), %d, S(st)," % (kb * 1024))]
+    return [(K, "hipLaunchKernelGGL(kc, dim3((unsigned)((s.tiles + COMPACT_TILES - 1) / COMPACT_TILES)), dim3(256), 0, S(st),",
+             "hipLaunchKernelGGL(kc, dim3((unsigned)((s.tiles + COMPACT_TILES - 1) / COMPACT_TILES)), dim3(256), %d, S(st)," % (kb * 1024))]
 
 
 EDITS = {
@@ -124,7 +124,7 @@ EDITS["summin0"] = _sum_min(0)
 EDITS["summin16"] = _sum_min(16)
 
 # chained folds with exclusions inside the chain through k_compact_sum too
-EDITS["chainexcl"] = [("yrwi_host.cpp",
+EDITS["chainexcl"] = [("yrwi_join.cpp",
                        "J.want_sum = last && P.excl.empty() && !chain_excl && P.prof.coeff_authority <= 12 ? 1 : 0;",
                        "J.want_sum = last && P.excl.empty() && (chain_excl || !chain_excl) && P.prof.coeff_authority <= 12 ? 1 : 0;")]
 

@@ -1,6 +1,7 @@
 // yrwi_host.h -- host-side structures shared by libyrwi's host translation
-// units (yrwi_host.cpp: contexts, planning, query execution; yrwi_heap.cpp:
-// BLOB heap loader).  Internal; the public ABI is include/yrwi.h.
+// units (yrwi_host.cpp: contexts, planning, query execution; yrwi_join.cpp: the
+// join phase; yrwi_heap.cpp: BLOB heap loader).  Internal; the public ABI is
+// include/yrwi.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -633,6 +634,48 @@ struct Xfer {
   void* ptr;
   size_t bytes;
 };
+// ---- the two phases of a batch part: yrwi_join.cpp (join / exclusion) and
+// yrwi_host.cpp (planning, rank)
+struct Timing {
+  // per join step: before k_join, between k_join and k_probe, after k_probe
+  std::vector<std::array<hipEvent_t, 3>> kjoin;
+  std::vector<std::array<hipEvent_t, 2>> kexcl;  // around each exclusion step's k_probe
+  std::vector<std::array<hipEvent_t, 2>> kcompact;  // around each k_compact launch
+  std::vector<std::array<hipEvent_t, 2>> kreduce;   // around each k_reduce + k_shard_fin
+  std::vector<std::array<hipEvent_t, 2>> kscore;    // around each pass's k_score launches
+  std::vector<std::array<hipEvent_t, 2>> kchain;    // around each chained step's k_chain_part .. k_scan_tiles
+  // around every group of back-to-back kernel launches of the batch (no host
+  // synchronisation inside a span): their sum is the batch's kernel time
+  std::vector<std::array<hipEvent_t, 2>> spans;
+  hipEvent_t t0 = nullptr, tj = nullptr, tn = nullptr, ts = nullptr;
+};
+
+inline hipEvent_t span_open(Lane* L, Timing* tm) {
+  if (!tm) return nullptr;
+  hipEvent_t e = L->event();
+  hipEventRecord(e, L->stream);
+  return e;
+}
+inline void span_close(Lane* L, Timing* tm, hipEvent_t b) {
+  if (!tm) return;
+  hipEvent_t e = L->event();
+  hipEventRecord(e, L->stream);
+  tm->spans.push_back({b, e});
+}
+
+inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline ChainList chain_list(const ListRec* L) { return ChainList{L->uid, L->head, L->bm, L->n}; }
+
+// Element-wise sum of v over the url-hash shards (every rank passes vectors of
+// the same length, in the same sequence of calls); identity on one context.
+int allsum_host(Lane* L, std::vector<int64_t>& v);
+// Run the join/exclusion phase of all plans; leaves each plan's container in P.cont.
+// Every fold step's dispatch (J3) is taken on the global sizes of its two
+// containers: the next list's (Plan.seq_ng) and the accumulated container's,
+// which after the first step is the sum over the shards of their joined rows
+// (one exchange per step that some query continues past; none on one context).
+int run_join_phase(Lane* ctx, std::vector<Plan>& plans, yrwi_stats* st, Timing* tm);
+
 // (re)build the url dictionary and every list's url ids if the index changed
 int ensure_url_ids(CtxBase* ctx);
 // The joined containers of nq TermSearch descriptors, as yrwi_term_search computes one: planning,

@@ -193,7 +193,7 @@ struct JoinQ {
   // from the compaction (no exclusion marks, no authority counts): one ChunkSum per
   // tile of the job (index tile - tile_base), written by k_compact_sum
   ChunkSum* psum;
-  int32_t want_sum;    // host: psum wanted (run_join_jobs allocates it)
+  int32_t want_sum;    // host: psum wanted (alloc_pieces allocates it)
   int32_t pad_sum;
 };
 
@@ -423,26 +423,52 @@ struct OrderArgs {
   OrderProb p[2];
 };
 
-// jobs [0, nmerge) are JA_MERGE with tiles [0, merge_tiles); the rest are JA_PROBE
-// chain: the step has chained jobs (JoinQ::chain): k_chain and k_scan_tiles run
-// (d_tile_lvl: CHAIN_LVL counts per tile), k_compact does not -- the caller
-// launches it with launch_compact once the fold's dispatch modes are known
-int launch_join_step(const JoinQ* d_jobs, const int64_t* d_tile_base, int32_t njobs, int32_t nmerge,
-                     int64_t merge_tiles, int64_t total_tiles, TileDesc* d_desc, ProbeDesc* d_pdesc,
-                     uint2* d_pairs, uint32_t* d_pair_uid, int64_t* d_tile_src,
-                     int32_t* d_tile_cnt, int64_t* d_tile_off, bool mark, bool long_tiles, const BandOrder& bo,
-                     void* stream,
-                     void* ev_begin,
-                     void* ev_mid, void* ev_end, void* ev_compact0 = nullptr, void* ev_compact1 = nullptr,
-                     bool chain = false, int32_t* d_tile_lvl = nullptr, ProbeDesc* d_crange = nullptr,
-                     const int2* d_cgrp = nullptr, int64_t ngroups = 0, BmFast* d_fast = nullptr,
-                     BmFast* d_fast_perm = nullptr, int sum = 0);
-// sum: jobs of the step with normalisation pieces (JoinQ::psum), compacted by
-// k_compact_sum (one wave per tile): 0 none, 1 every job, 2 some (k_compact the rest)
-int launch_compact(const JoinQ* d_jobs, const int64_t* d_tile_base, int32_t njobs, int64_t total_tiles,
-                   const uint2* d_pairs, const uint32_t* d_pair_uid, const int64_t* d_tile_src,
-                   const int32_t* d_tile_cnt, const int64_t* d_tile_off, const BandOrder& bo, bool chain, void* stream,
-                   int sum = 0);
+// The device buffers of one join step: what launch_join_step and launch_compact read.
+struct JoinStep {
+  // job table: jobs [0, nmerge) are JA_MERGE with tiles [0, merge_tiles); the rest are JA_PROBE
+  JoinQ* d_jobs = nullptr;
+  int64_t* d_tile_base = nullptr;
+  int32_t njobs = 0, nmerge = 0;
+  int64_t merge_tiles = 0, tiles = 0;
+  // tile descriptors: merge tiles, probe tiles, and the bitmap-probe tiles' short
+  // descriptors in tile order and in k_probe's order
+  TileDesc* d_desc = nullptr;
+  ProbeDesc* d_pdesc = nullptr;
+  BmFast* d_fast = nullptr;
+  BmFast* d_fast_perm = nullptr;
+  // pair run (a marking step has none)
+  uint2* d_pairs = nullptr;
+  uint32_t* d_pair_uid = nullptr;
+  int64_t* d_tile_src = nullptr;
+  int32_t* d_tile_cnt = nullptr;
+  int64_t* d_tile_off = nullptr;
+  // chain: the step has chained jobs (JoinQ::chain): k_chain and k_scan_tiles run
+  // (d_tile_lvl: CHAIN_LVL counts per tile), k_compact does not -- the caller
+  // launches it with launch_compact once the fold's dispatch modes are known
+  bool chain = false;
+  int32_t* d_tile_lvl = nullptr;
+  ProbeDesc* d_crange = nullptr;  // the list ranges of k_chain_part, CHAIN_MAXL per group
+  int2* d_cgrp = nullptr;  // chain groups: runs of up to CHAIN_GMAX merge tiles of one chained job (k_chain)
+  int64_t ngroups = 0;
+  bool mark = false;        // an exclusion step: matches mark JoinQ::removed, nothing is compacted
+  bool long_tiles = false;  // some bitmap-probe job has KPT_LARGE * PROBE_TILE tiles
+  // sum: jobs of the step with normalisation pieces (JoinQ::psum), compacted by
+  // k_compact_sum (one wave per tile): 0 none, 1 every job, 2 some (k_compact the rest)
+  int sum = 0;
+  BandOrder bo;
+};
+// Timing events of a join step (hipEvent_t; nullptr: not recorded): before k_join,
+// between k_join and k_probe, after k_probe; compact0 / compact1 around the
+// compaction, or around k_chain alone when the step is chained.
+struct JoinEvents {
+  void* begin = nullptr;
+  void* mid = nullptr;
+  void* end = nullptr;
+  void* compact0 = nullptr;
+  void* compact1 = nullptr;
+};
+int launch_join_step(const JoinStep& step, void* stream, const JoinEvents& ev);
+int launch_compact(const JoinStep& step, bool chain, void* stream);
 int launch_rank(const RankQ* d_q, const int64_t* d_chunk_base, int32_t nq, int64_t total_chunks,
                 ChunkSum* d_chunks, ShardSum* d_shard, NormState* d_norm, int32_t world, void* stream);
 // hp_any: some query of the launch counts host buckets (RankQ::ecnt): k_reduce
@@ -585,7 +611,7 @@ int launch_event_where(const EvDev* d_ev, const uint64_t* d_hi, const uint8_t* d
 // seeds the url set with the doublecheck urls of the filter (epoch 0)
 int launch_event_seed(const EvDev* d_ev, const uint64_t* d_hi, const uint8_t* d_lo, int64_t n, void* stream);
 
-// The chain groups of a join step (launch_join_step's d_cgrp: runs of up to G merge tiles of one
+// The chain groups of a join step (JoinStep::d_cgrp: runs of up to G merge tiles of one
 // chained job) written on the device from one entry per chained job, for a caller whose uploads
 // must not grow with the lists (yrwi_event_add_local); groups [gbase, gbase + ceil(ntiles / G))
 // of the job are (tile0 + i G, min(G, ntiles - i G)).

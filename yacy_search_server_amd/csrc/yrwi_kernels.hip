@@ -4576,22 +4576,15 @@ int launch_feat_rows(const uint64_t* feat, const uint32_t* uid, const uint64_t* 
   return rc(hipGetLastError());
 }
 
-int launch_join_step(const JoinQ* d_jobs, const int64_t* d_tile_base, int32_t njobs, int32_t nmerge,
-                     int64_t merge_tiles, int64_t total_tiles, TileDesc* d_desc, ProbeDesc* d_pdesc,
-                     uint2* d_pairs, uint32_t* d_pair_uid, int64_t* d_tile_src, int32_t* d_tile_cnt,
-                     int64_t* d_tile_off, bool mark, bool long_tiles, const BandOrder& bo,
-                     void* st, void* ev0,
-                     void* evm, void* ev1, void* evc0, void* evc1, bool chain, int32_t* d_tile_lvl,
-                     ProbeDesc* d_crange, const int2* d_cgrp, int64_t ngroups, BmFast* d_fast,
-                     BmFast* d_fast_perm, int sum) {
-  if (total_tiles <= 0) return 0;
-  const int64_t probe_tiles = total_tiles - merge_tiles;
+int launch_join_step(const JoinStep& s, void* st, const JoinEvents& ev) {
+  if (s.tiles <= 0) return 0;
+  const int64_t probe_tiles = s.tiles - s.merge_tiles;
   // band orders (k_order_hist / k_order_scatter): all tiles for k_compact, probe tiles for k_probe
-  int2* perm = bo.key && bo.tile_job && !mark ? bo.perm : nullptr;
-  int2* pperm = bo.pkey && bo.tile_job && probe_tiles > 1 ? bo.pperm : nullptr;
-  uint32_t* tkey = perm ? bo.key : nullptr;
-  uint32_t* pkey = pperm ? bo.pkey : nullptr;
-  int32_t* tjob = bo.tile_job;
+  int2* perm = s.bo.key && s.bo.tile_job && !s.mark ? s.bo.perm : nullptr;
+  int2* pperm = s.bo.pkey && s.bo.tile_job && probe_tiles > 1 ? s.bo.pperm : nullptr;
+  uint32_t* tkey = perm ? s.bo.key : nullptr;
+  uint32_t* pkey = pperm ? s.bo.pkey : nullptr;
+  int32_t* tjob = s.bo.tile_job;
   static int join_grid = 0;  // resident k_join workgroups on the whole device
   if (!join_grid) {
     int dev = 0, cus = 0, per_cu = 0;
@@ -4602,15 +4595,17 @@ int launch_join_step(const JoinQ* d_jobs, const int64_t* d_tile_base, int32_t nj
       return YRWI_E_HIP;
     join_grid = std::max(1, cus * std::max(1, per_cu));
   }
-  if (merge_tiles > 0) {
-    hipLaunchKernelGGL(k_partition, dim3((unsigned)((merge_tiles + 255) / 256)), dim3(256), 0, S(st), d_jobs,
-                       d_tile_base, nmerge, merge_tiles, d_desc, d_tile_src, tkey, tjob);
-    if (!mark) hipLaunchKernelGGL(k_scan_bounds, dim3((unsigned)nmerge), dim3(256), 0, S(st), d_jobs, d_tile_base, d_tile_src);
+  if (s.merge_tiles > 0) {
+    hipLaunchKernelGGL(k_partition, dim3((unsigned)((s.merge_tiles + 255) / 256)), dim3(256), 0, S(st), s.d_jobs,
+                       s.d_tile_base, s.nmerge, s.merge_tiles, s.d_desc, s.d_tile_src, tkey, tjob);
+    if (!s.mark)
+      hipLaunchKernelGGL(k_scan_bounds, dim3((unsigned)s.nmerge), dim3(256), 0, S(st), s.d_jobs, s.d_tile_base,
+                         s.d_tile_src);
   }
   if (probe_tiles > 0)
-    hipLaunchKernelGGL(k_probe_part, dim3((unsigned)((probe_tiles + 255) / 256)), dim3(256), 0, S(st), d_jobs,
-                       d_tile_base, njobs, merge_tiles, probe_tiles, d_pdesc, tkey, tjob, pkey, bo.pshift,
-                       mark ? nullptr : d_fast);
+    hipLaunchKernelGGL(k_probe_part, dim3((unsigned)((probe_tiles + 255) / 256)), dim3(256), 0, S(st), s.d_jobs,
+                       s.d_tile_base, s.njobs, s.merge_tiles, probe_tiles, s.d_pdesc, tkey, tjob, pkey, s.bo.pshift,
+                       s.mark ? nullptr : s.d_fast);
   if (perm || pperm) {
     OrderArgs oa{};
     int nb = 0;
@@ -4626,70 +4621,69 @@ int launch_join_step(const JoinQ* d_jobs, const int64_t* d_tile_base, int32_t nj
       P.shift = shift;
       P.tile_job = job;
       P.perm = out;
-      P.hist = bo.hist + (int64_t)nb * ORDER_BUCKETS;
+      P.hist = s.bo.hist + (int64_t)nb * ORDER_BUCKETS;
       nb += P.nslices;
     };
-    if (perm) prob(0, tkey, total_tiles, bo.shift, tjob, perm);
+    if (perm) prob(0, tkey, s.tiles, s.bo.shift, tjob, perm);
     if (pperm)
-      prob(perm ? 1 : 0, pkey, probe_tiles, 0, tjob + merge_tiles, pperm, mark ? nullptr : d_fast,
-           mark ? nullptr : d_fast_perm);
+      prob(perm ? 1 : 0, pkey, probe_tiles, 0, tjob + s.merge_tiles, pperm, s.mark ? nullptr : s.d_fast,
+           s.mark ? nullptr : s.d_fast_perm);
     hipLaunchKernelGGL(k_order_hist, dim3((unsigned)nb), dim3(ORDER_THREADS), 0, S(st), oa);
     hipLaunchKernelGGL(k_order_scatter, dim3((unsigned)nb), dim3(ORDER_THREADS), 0, S(st), oa);
   }
-  if (ev0) hipEventRecord(reinterpret_cast<hipEvent_t>(ev0), S(st));
-  if (merge_tiles > 0)
-    hipLaunchKernelGGL(k_join, dim3((unsigned)std::min<int64_t>(merge_tiles, join_grid)), dim3(JOIN_THREADS), 0,
-                       S(st), d_jobs, d_desc, merge_tiles, d_pairs, d_pair_uid, d_tile_src, d_tile_cnt, mark ? 1 : 0);
-  if (evm) hipEventRecord(reinterpret_cast<hipEvent_t>(evm), S(st));
+  if (ev.begin) hipEventRecord(reinterpret_cast<hipEvent_t>(ev.begin), S(st));
+  if (s.merge_tiles > 0)
+    hipLaunchKernelGGL(k_join, dim3((unsigned)std::min<int64_t>(s.merge_tiles, join_grid)), dim3(JOIN_THREADS), 0,
+                       S(st), s.d_jobs, s.d_desc, s.merge_tiles, s.d_pairs, s.d_pair_uid, s.d_tile_src, s.d_tile_cnt,
+                       s.mark ? 1 : 0);
+  if (ev.mid) hipEventRecord(reinterpret_cast<hipEvent_t>(ev.mid), S(st));
   if (probe_tiles > 0) {
-    auto kp = long_tiles ? (mark ? k_probe<true, true> : k_probe<true, false>)
-                         : (mark ? k_probe<false, true> : k_probe<false, false>);
-    const BmFast* fast = mark || !d_fast ? nullptr : pperm ? d_fast_perm : d_fast;  // (k_probe's order)
-    hipLaunchKernelGGL(kp, dim3((unsigned)probe_tiles), dim3(PROBE_TILE), 0, S(st), d_jobs, d_tile_base, d_pdesc,
-                       merge_tiles, d_pairs, d_pair_uid, d_tile_src, d_tile_cnt, (const int2*)pperm, d_tile_lvl, fast);
+    auto kp = s.long_tiles ? (s.mark ? k_probe<true, true> : k_probe<true, false>)
+                           : (s.mark ? k_probe<false, true> : k_probe<false, false>);
+    const BmFast* fast = s.mark || !s.d_fast ? nullptr : pperm ? s.d_fast_perm : s.d_fast;  // (k_probe's order)
+    hipLaunchKernelGGL(kp, dim3((unsigned)probe_tiles), dim3(PROBE_TILE), 0, S(st), s.d_jobs, s.d_tile_base,
+                       s.d_pdesc, s.merge_tiles, s.d_pairs, s.d_pair_uid, s.d_tile_src, s.d_tile_cnt,
+                       (const int2*)pperm, s.d_tile_lvl, fast);
   }
-  if (ev1) hipEventRecord(reinterpret_cast<hipEvent_t>(ev1), S(st));
-  if (!mark) {
-    if (chain && ngroups > 0) {  // chain groups
-      const int64_t nr = ngroups * CHAIN_MAXL;
-      hipLaunchKernelGGL(k_chain_part, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, S(st), d_jobs,
-                         d_tile_base, njobs, d_cgrp, ngroups, (const uint32_t*)d_pair_uid,
-                         (const int64_t*)d_tile_src, (const int32_t*)d_tile_cnt, d_crange);
-      // chained steps: evc0 / evc1 bracket k_chain alone (the population rocprofv3 averages)
-      if (evc0) hipEventRecord(reinterpret_cast<hipEvent_t>(evc0), S(st));
-      hipLaunchKernelGGL(k_chain, dim3((unsigned)ngroups), dim3(256), 0, S(st), d_jobs, d_tile_base, njobs, d_cgrp,
-                         d_pairs, d_pair_uid, d_tile_src, d_tile_cnt, d_tile_lvl, (const ProbeDesc*)d_crange);
-      if (evc1) hipEventRecord(reinterpret_cast<hipEvent_t>(evc1), S(st));
+  if (ev.end) hipEventRecord(reinterpret_cast<hipEvent_t>(ev.end), S(st));
+  if (!s.mark) {
+    if (s.chain && s.ngroups > 0) {  // chain groups
+      const int64_t nr = s.ngroups * CHAIN_MAXL;
+      hipLaunchKernelGGL(k_chain_part, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, S(st), s.d_jobs,
+                         s.d_tile_base, s.njobs, s.d_cgrp, s.ngroups, (const uint32_t*)s.d_pair_uid,
+                         (const int64_t*)s.d_tile_src, (const int32_t*)s.d_tile_cnt, s.d_crange);
+      // chained steps: compact0 / compact1 bracket k_chain alone (the population rocprofv3 averages)
+      if (ev.compact0) hipEventRecord(reinterpret_cast<hipEvent_t>(ev.compact0), S(st));
+      hipLaunchKernelGGL(k_chain, dim3((unsigned)s.ngroups), dim3(256), 0, S(st), s.d_jobs, s.d_tile_base, s.njobs,
+                         s.d_cgrp, s.d_pairs, s.d_pair_uid, s.d_tile_src, s.d_tile_cnt, s.d_tile_lvl,
+                         (const ProbeDesc*)s.d_crange);
+      if (ev.compact1) hipEventRecord(reinterpret_cast<hipEvent_t>(ev.compact1), S(st));
     }
-    hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)njobs), dim3(256), 0, S(st), d_jobs, d_tile_base, d_tile_cnt,
-                       d_tile_off, (const int32_t*)(chain ? d_tile_lvl : nullptr));
-    if (!chain) {  // chained steps compact once the fold's dispatch modes are known (launch_compact)
-      if (evc0) hipEventRecord(reinterpret_cast<hipEvent_t>(evc0), S(st));
-      if (int r = launch_compact(d_jobs, d_tile_base, njobs, total_tiles, d_pairs, d_pair_uid, d_tile_src, d_tile_cnt,
-                                 d_tile_off, bo, false, st, sum))
-        return r;
-      if (evc1) hipEventRecord(reinterpret_cast<hipEvent_t>(evc1), S(st));
+    hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)s.njobs), dim3(256), 0, S(st), s.d_jobs, s.d_tile_base,
+                       s.d_tile_cnt, s.d_tile_off, (const int32_t*)(s.chain ? s.d_tile_lvl : nullptr));
+    if (!s.chain) {  // chained steps compact once the fold's dispatch modes are known (launch_compact)
+      if (ev.compact0) hipEventRecord(reinterpret_cast<hipEvent_t>(ev.compact0), S(st));
+      if (int r = launch_compact(s, false, st)) return r;
+      if (ev.compact1) hipEventRecord(reinterpret_cast<hipEvent_t>(ev.compact1), S(st));
     }
   }
   return rc(hipGetLastError());
 }
 
-int launch_compact(const JoinQ* d_jobs, const int64_t* d_tile_base, int32_t njobs, int64_t total_tiles,
-                   const uint2* d_pairs, const uint32_t* d_pair_uid, const int64_t* d_tile_src,
-                   const int32_t* d_tile_cnt, const int64_t* d_tile_off, const BandOrder& bo, bool chain, void* st,
-                   int sum) {
-  if (total_tiles <= 0) return 0;
-  const int2* perm = bo.key && bo.tile_job ? bo.perm : nullptr;
-  if (sum != 1) {  // jobs without normalisation pieces (all of them when sum == 0)
+int launch_compact(const JoinStep& s, bool chain, void* st) {
+  if (s.tiles <= 0) return 0;
+  const int2* perm = s.bo.key && s.bo.tile_job ? s.bo.perm : nullptr;
+  if (s.sum != 1) {  // jobs without normalisation pieces (all of them when sum == 0)
     auto kc = chain ? k_compact<true> : k_compact<false>;
-    hipLaunchKernelGGL(kc, dim3((unsigned)((total_tiles + COMPACT_TILES - 1) / COMPACT_TILES)), dim3(256), 0, S(st),
-                       d_jobs, d_tile_base, njobs, total_tiles, d_pairs, d_pair_uid, d_tile_src, d_tile_cnt, d_tile_off,
-                       perm, (const int32_t*)bo.tile_job, sum ? 1 : 0);
+    hipLaunchKernelGGL(kc, dim3((unsigned)((s.tiles + COMPACT_TILES - 1) / COMPACT_TILES)), dim3(256), 0, S(st),
+                       s.d_jobs, s.d_tile_base, s.njobs, s.tiles, s.d_pairs, s.d_pair_uid, s.d_tile_src, s.d_tile_cnt,
+                       s.d_tile_off, perm, (const int32_t*)s.bo.tile_job, s.sum ? 1 : 0);
   }
-  if (sum) {  // the jobs with pieces: one wave per tile
+  if (s.sum) {  // the jobs with pieces: one wave per tile
     auto ks = chain ? k_compact_sum<true> : k_compact_sum<false>;
-    hipLaunchKernelGGL(ks, dim3((unsigned)total_tiles), dim3(64), 0, S(st), d_jobs, d_tile_base, njobs, total_tiles,
-                       d_pairs, d_pair_uid, d_tile_src, d_tile_cnt, d_tile_off, perm, (const int32_t*)bo.tile_job);
+    hipLaunchKernelGGL(ks, dim3((unsigned)s.tiles), dim3(64), 0, S(st), s.d_jobs, s.d_tile_base, s.njobs, s.tiles,
+                       s.d_pairs, s.d_pair_uid, s.d_tile_src, s.d_tile_cnt, s.d_tile_off, perm,
+                       (const int32_t*)s.bo.tile_job);
   }
   return rc(hipGetLastError());
 }
