@@ -265,6 +265,29 @@ int yrwi_add_postings(yrwi_ctx* ctx, const uint8_t* terms12, const uint8_t* rows
  * yrwi_put_list(n = 0).  st->removed = rows removed.  st may be NULL. */
 int yrwi_remove_postings(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uint8_t* urls12,
                          int64_t nurls, yrwi_update_stats* st);
+/* Removes every posting whose url hash carries one of the nhosts host hashes (hosts6 + 6 i: url-hash
+ * characters 6..11, as yrwi_filter.sitehash) from the named lists; nterms == 0: from every list.
+ * It behaves exactly as yrwi_remove_postings(ctx, terms12, nterms, U, |U|, st) with U = the url hashes
+ * in the selected lists whose characters 6..11 are in the host set: duplicate hosts and terms count
+ * once, unknown terms and hosts nobody has are ignored, a list left empty disappears, st is filled the
+ * same way (st may be NULL), and the call waits for the batches in flight.  No list is read back: one
+ * pass over the 9 key bytes of every selected posting marks the hits (the host set is searched in LDS
+ * up to YRWI_HOST_LDS_MAX hosts, in global memory above), then the lists that lose rows are compacted
+ * in chunks of whole lists of at most YRWI_RM_CHUNK rows (environment, read per call; default
+ * 67,108,864, at least 256, at most 2^31 - 2; 12 B of scratch per row of the largest chunk), so the
+ * call never returns YRWI_E_LIMIT, and st->launches / st->syncs depend on the number of chunks alone.
+ * nhosts == 0 or nothing selected: a successful no-op.  YRWI_E_HASH (a host or term hash with a
+ * character outside the Base64 alphabet) or YRWI_E_NOMEM: nothing has changed.  A sharded context
+ * removes from what it holds; every rank is given the same hosts, and the ranks' `removed` add up. */
+#define YRWI_HOST_LDS_MAX 2048
+int yrwi_remove_hosts(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uint8_t* hosts6,
+                      int32_t nhosts, yrwi_update_stats* st);
+/* What yrwi_remove_hosts would remove, without changing anything: counts[i] = postings of host i in
+ * the selected lists (a host given twice gets its full count twice); *lists_hit = selected lists with at
+ * least one such posting (may be NULL).  Errors as yrwi_remove_hosts; a sharded context counts what
+ * it holds. */
+int yrwi_count_hosts(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uint8_t* hosts6,
+                     int32_t nhosts, int64_t* counts, int64_t* lists_hit);
 /* Brings the url dictionary (url hash -> order-preserving 32-bit url id, the
  * join key in HBM) up to date now instead of at the next query.  The first
  * build sorts every key; later put_list / removal / load_heaps changes are

@@ -48,7 +48,8 @@ JNIEXPORT jint JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_putList(JNIEnv* env, jc
   return rc;
 }
 
-/* ---- index updates on the device (yrwi_add_postings / yrwi_remove_postings) ---- */
+/* ---- index updates on the device (yrwi_add_postings / yrwi_remove_postings / yrwi_remove_hosts /
+ *      yrwi_count_hosts) ---- */
 /* yrwi_update_stats as long[9]: terms, new_terms, emptied_terms, added, replaced, dropped, removed,
  * launches, syncs; NULL when rc != 0 */
 static jlongArray update_stats(JNIEnv* env, int rc, const yrwi_update_stats* st) {
@@ -93,6 +94,51 @@ JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_removePostings(JN
   free(t);
   free(u);
   return update_stats(env, rc, &st);
+}
+
+/* yrwi_remove_hosts: hosts = nhosts * 6 bytes (url-hash characters 6..11); the statistics of removePostings */
+JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_removeHosts(JNIEnv* env, jclass c, jlong ctx,
+                                                                          jbyteArray terms, jint nterms,
+                                                                          jbyteArray hosts, jint nhosts) {
+  uint8_t* t = copy_in(env, terms, (int64_t)nterms * 12);
+  if (!t) return NULL;
+  uint8_t* h = copy_in(env, hosts, (int64_t)nhosts * 6);
+  if (!h) {
+    free(t);
+    return NULL;
+  }
+  yrwi_update_stats st;
+  int rc = yrwi_remove_hosts((yrwi_ctx*)(intptr_t)ctx, t, nterms, h, nhosts, &st);
+  free(t);
+  free(h);
+  return update_stats(env, rc, &st);
+}
+
+/* yrwi_count_hosts as long[nhosts + 1]: the postings of every host in the selected lists, then the
+ * selected lists that hold at least one of them; NULL when the call failed */
+JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_countHosts(JNIEnv* env, jclass c, jlong ctx,
+                                                                         jbyteArray terms, jint nterms,
+                                                                         jbyteArray hosts, jint nhosts) {
+  uint8_t* t = copy_in(env, terms, (int64_t)nterms * 12);
+  if (!t) return NULL;
+  uint8_t* h = copy_in(env, hosts, (int64_t)nhosts * 6);
+  if (!h) {
+    free(t);
+    return NULL;
+  }
+  jlong* v = (jlong*)calloc((size_t)nhosts + 1, sizeof(jlong));
+  int64_t hit = 0;
+  int rc = v ? yrwi_count_hosts((yrwi_ctx*)(intptr_t)ctx, t, nterms, h, nhosts, (int64_t*)v, &hit) : YRWI_E_NOMEM;
+  free(t);
+  free(h);
+  jlongArray res = NULL;
+  if (rc == 0) {
+    v[nhosts] = hit;
+    res = (*env)->NewLongArray(env, nhosts + 1);
+    if (res) (*env)->SetLongArrayRegion(env, res, 0, nhosts + 1, v);
+  }
+  free(v);
+  return res;
 }
 
 JNIEXPORT jbyteArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_joinExclude(JNIEnv* env, jclass c, jlong ctx,

@@ -126,6 +126,30 @@ public final class GpuRWI implements AutoCloseable {
         return st;
     }
 
+    /** Removes every posting whose url hash carries one of the host hashes (6 bytes each: url-hash
+     *  characters 6..11, as queryFiltered's sitehash) from the lists of `terms`; terms == null or empty:
+     *  from every list (yrwi_remove_hosts).  The hosts' url hashes are found on the device: no list
+     *  crosses to the host.  Returns the statistics of removePostings.  Uncompiled like the rest of
+     *  this class (see the head of the file). */
+    public synchronized long[] removeHosts(final byte[][] terms, final byte[][] hosts) {
+        final int nterms = terms == null ? 0 : terms.length;
+        final long[] st = removeHosts(this.ctx, nterms == 0 ? new byte[0] : flatten(terms), nterms,
+                                      flattenN(hosts, 6), hosts.length);
+        if (st == null) throw new IllegalStateException("yrwi_remove_hosts failed");
+        return st;
+    }
+
+    /** What removeHosts(terms, hosts) would remove, the index unchanged (yrwi_count_hosts):
+     *  long[hosts.length + 1] = the postings of every host in the selected lists (a host given twice
+     *  gets its count twice), then the number of selected lists that hold at least one of them. */
+    public synchronized long[] countHosts(final byte[][] terms, final byte[][] hosts) {
+        final int nterms = terms == null ? 0 : terms.length;
+        final long[] counts = countHosts(this.ctx, nterms == 0 ? new byte[0] : flatten(terms), nterms,
+                                         flattenN(hosts, 6), hosts.length);
+        if (counts == null) throw new IllegalStateException("yrwi_count_hosts failed");
+        return counts;
+    }
+
     /** Index.size(termHash) of each term on the GPU index (yrwi_list_size; 0: no list). */
     public synchronized long[] listSizes(final byte[][] terms) {
         return listSizes(this.ctx, flatten(terms), terms.length);
@@ -441,6 +465,8 @@ public final class GpuRWI implements AutoCloseable {
     private static native int putList(long ctx, byte[] term, byte[] rows, int n, int sorted);
     private static native long[] addPostings(long ctx, byte[] terms, byte[] rows, int n, int policy);
     private static native long[] removePostings(long ctx, byte[] terms, int nterms, byte[] urls, int nurls);
+    private static native long[] removeHosts(long ctx, byte[] terms, int nterms, byte[] hosts6, int nhosts);
+    private static native long[] countHosts(long ctx, byte[] terms, int nterms, byte[] hosts6, int nhosts);
     private static native byte[] joinExclude(long ctx, byte[] incl, int nincl, byte[] excl, int nexcl,
                                              int maxDistance, long nowMillis);
     private static native long[] normalizeScore(long ctx, byte[] rows, int m, int[] profile32, String language,

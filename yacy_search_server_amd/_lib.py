@@ -139,6 +139,8 @@ class CUpdateStats(ctypes.Structure):
 
 ADD_POLICIES = {"replace": 0, "keep": 1, "recent": 2}
 
+HOST_LDS_MAX = 2048  # YRWI_HOST_LDS_MAX: the largest host set yrwi_remove_hosts / yrwi_count_hosts search in LDS
+
 
 DUMP_WINDOW_DEFAULT = 32 << 20  # yrwi_dump_heap's window without YRWI_DUMP_WINDOW (bytes)
 
@@ -167,6 +169,10 @@ SIGNATURES = {
                                          ctypes.POINTER(CUpdateStats)]),
     "yrwi_remove_postings": (ctypes.c_int, [_VP, _VP, ctypes.c_int32, _VP, ctypes.c_int64,
                                             ctypes.POINTER(CUpdateStats)]),
+    "yrwi_remove_hosts": (ctypes.c_int, [_VP, _VP, ctypes.c_int32, _VP, ctypes.c_int32,
+                                         ctypes.POINTER(CUpdateStats)]),
+    "yrwi_count_hosts": (ctypes.c_int, [_VP, _VP, ctypes.c_int32, _VP, ctypes.c_int32, _VP,
+                                        ctypes.POINTER(ctypes.c_int64)]),
     "yrwi_build_url_ids": (ctypes.c_int, [_VP]),
     "yrwi_list_size": (ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]),
     "yrwi_get_list": (ctypes.c_int, [_VP, ctypes.c_char_p, _VP, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),

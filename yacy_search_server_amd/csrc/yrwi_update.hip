@@ -17,6 +17,26 @@
 // deduplicated url set and counts the hits per list (read back once); only the lists that
 // lose rows are flagged, scanned and compacted (k_rm_flag, one scan, k_rm_place).
 //
+// yrwi_remove_hosts / yrwi_count_hosts: the predicate is the host hash, url-hash characters
+// 6..11 = the low 36 bits of the 72-bit key every list stores next to its rows (host36), so
+// one streaming pass (k_host_mark) over the flattened khi / klo of the selected lists, 9 B per
+// posting, marks every posting of the sorted, deduplicated host set and reads no row.  The
+// set is staged in LDS and searched there when it holds at most YRWI_HOST_LDS_MAX = 2048
+// keys (16 KiB per workgroup); a larger set is searched in global memory; the two searches
+// are the same function over another pointer.  At most 2048 workgroups each take a contiguous
+// span of the flattened postings, so a workgroup stages the set once for all its postings and a
+// lane looks its list up again only where it passes a list's end.  Hits are counted
+// per list with one atomic per list per wave (the lanes of a list are neighbours and a wave's
+// lists ascend: it sums a list's hits over its steps and adds them on leaving the list); per host
+// (count_hosts only) in LDS per workgroup and then one global atomic per hit slot per
+// workgroup when the set is in LDS, else one global atomic per slot per wave.  The per-list
+// counts are read back once.  The lists that lose rows are compacted in chunks: runs of whole
+// lists of at most YRWI_RM_CHUNK rows in all (environment, read per call, at least 256,
+// default 2^26; a longer list is a chunk of its own), each flag -> scan -> place (k_host_flag,
+// one scan, k_rm_place) in the scratch of the chunk before it, 12 B per row of the largest
+// chunk, with no host wait between chunks: launches and syncs depend on the number of chunks
+// alone, and nothing stops at 2^31 postings.
+//
 // A changed list is a new list in index memory (the old copy is dead until repack_index,
 // reached through ensure_url_ids) and goes through index_changed like a replaced list.
 
@@ -27,6 +47,10 @@
 using namespace yrwi;
 
 namespace {
+
+constexpr int HOST_LDS_MAX = YRWI_HOST_LDS_MAX;         // host keys searched in LDS (8 B each)
+constexpr int HOST_MARK_BLOCKS = 2048;                  // k_host_mark's grid cap
+constexpr int64_t RM_CHUNK_DEFAULT = (int64_t)1 << 26;  // rows compacted at a time (YRWI_RM_CHUNK)
 
 struct UpdJob {  // one touched list and the job's rows in the sorted batch
   const uint64_t* akhi;
@@ -271,6 +295,174 @@ __global__ __launch_bounds__(256) void k_rm_place(const RmJob* __restrict__ jobs
     dstp = J.orows + pos * YRWI_ROW_BYTES;
   }
   wave_move_rows(srcp, dstp);
+}
+
+// ---------------------------------------------------------------- hosts
+// url-hash chars 6..11 (the host hash) = the key's low 36 bits (key_host36, yrwi_kernels.hip)
+__device__ __forceinline__ uint64_t host36(uint64_t hi, uint32_t lo) { return ((hi & 0xFFFFFFFull) << 8) | (lo & 0xFFu); }
+
+// slot of h in the ascending set hs[0, nh), -1: not in it
+__device__ __forceinline__ int host_slot(const uint64_t* __restrict__ hs, int nh, uint64_t h) {
+  int lo = 0, hi = nh;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (hs[mid] < h) lo = mid + 1; else hi = mid;
+  }
+  return lo < nh && hs[lo] == h ? lo : -1;
+}
+
+// A lane's place in the flattened lists.  A workgroup walks a contiguous span of postings upwards, so a
+// lane's postings ascend: its list is looked up again (a binary search over the lists above) only when
+// it passes the end of the one it is in, and the list's pointers stay in registers meanwhile.
+struct SegCursor {
+  int c = -1;
+  int64_t lo = 0, hi = 0;  // list c holds postings [lo, hi)
+  const uint64_t* kh = nullptr;
+  const uint8_t* kl = nullptr;
+};
+
+__device__ __forceinline__ void seg_seek(SegCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                         int nj, int64_t total, int64_t i) {
+  if (i < s.hi) return;
+  s.c += 1 + seg_of(off + s.c + 1, nj - s.c - 1, i);  // (i < total: a list above c holds it)
+  s.lo = off[s.c];
+  s.hi = s.c + 1 < nj ? off[s.c + 1] : total;
+  s.kh = jobs[s.c].khi;
+  s.kl = jobs[s.c].klo;
+}
+
+constexpr int HOST_TILE = 1024;  // postings a workgroup takes per step: 4 per thread, their loads in flight together
+
+// the workgroup's span [begin, end) of the flattened postings: whole tiles, the same for every thread
+__device__ __forceinline__ void host_span(int64_t total, int64_t* begin, int64_t* end) {
+  const int64_t per = ((total + gridDim.x - 1) / gridDim.x + HOST_TILE - 1) / HOST_TILE * HOST_TILE;
+  *begin = std::min<int64_t>((int64_t)blockIdx.x * per, total);
+  *end = std::min<int64_t>(*begin + per, total);
+}
+
+// One step of a thread: postings base + 256 u + thread (u < 4) below end -> their host slots (-1: not of
+// the set, or past end) and lists.  The four key loads are issued before the first search.
+template <bool LDS>
+__device__ __forceinline__ void mark_tile(SegCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                          int nj, int64_t total, const uint64_t* hs, int nh, int64_t base, int64_t end,
+                                          int slot[4], int c[4]) {
+  uint64_t h[4];
+  uint32_t l[4];
+#pragma unroll
+  for (int u = 0; u < 4; u++) {
+    const int64_t i = base + u * 256 + threadIdx.x;
+    c[u] = -1;
+    h[u] = 0;
+    l[u] = 0;
+    if (i < end) {
+      seg_seek(s, jobs, off, nj, total, i);
+      c[u] = s.c;
+      h[u] = s.kh[i - s.lo];
+      l[u] = s.kl[i - s.lo];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < 4; u++) slot[u] = c[u] >= 0 ? host_slot(hs, nh, host36(h[u], l[u])) : -1;
+}
+
+// the host set into LDS (LDS = true: nh <= HOST_LDS_MAX), or left where it is
+template <bool LDS>
+__device__ __forceinline__ const uint64_t* stage_set(uint64_t* s_set, const uint64_t* __restrict__ hset, int nh) {
+  if (!LDS) return hset;
+  for (int i = threadIdx.x; i < nh; i += blockDim.x) s_set[i] = hset[i];
+  __syncthreads();
+  return s_set;
+}
+
+// Marking pass: jrem[c] += postings of list c whose host is in the set; COUNT: hcnt[slot] += postings of
+// host slot.  Every wave of a workgroup runs every step whole (the ballots).
+template <bool LDS, bool COUNT>
+__global__ __launch_bounds__(256) void k_host_mark(const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                                   int nj, int64_t total, const uint64_t* __restrict__ hset, int nh,
+                                                   unsigned long long* __restrict__ jrem,
+                                                   unsigned long long* __restrict__ hcnt) {
+  __shared__ uint64_t s_set[LDS ? HOST_LDS_MAX : 1];
+  __shared__ uint32_t s_cnt[LDS && COUNT ? HOST_LDS_MAX : 1];
+  if (LDS && COUNT)
+    for (int i = threadIdx.x; i < nh; i += blockDim.x) s_cnt[i] = 0;
+  const uint64_t* hs = stage_set<LDS>(s_set, hset, nh);
+  const int lane = threadIdx.x & 63;
+  int64_t begin, end;
+  host_span(total, &begin, &end);
+  SegCursor cur;
+  int acc_c = -1;
+  uint32_t acc_n = 0;
+  for (int64_t base = begin; base < end; base += HOST_TILE) {
+    int slots[4], cs[4];
+    mark_tile<LDS>(cur, jobs, off, nj, total, hs, nh, base, end, slots, cs);
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int slot = slots[u], c = cs[u];
+      const bool hit = slot >= 0;
+      // per list: the lanes of one list are neighbours and the wave's lists ascend, so the wave sums a
+      // list's hits over its steps (acc_c, acc_n: the same in every lane) and adds them once, on leaving it
+      uint64_t act = __ballot(hit);
+      while (act) {
+        const int lead = __ffsll((unsigned long long)act) - 1;
+        const int lc = __shfl(c, lead, 64);
+        const uint64_t same = __ballot(hit && c == lc);
+        if (lc != acc_c) {
+          if (acc_n && lane == 0) atomicAdd(&jrem[acc_c], (unsigned long long)acc_n);
+          acc_c = lc;
+          acc_n = 0;
+        }
+        acc_n += (uint32_t)__popcll(same);
+        act &= ~same;
+      }
+      if (COUNT) {
+        act = __ballot(hit);
+        if (LDS) {
+          // one host owns the wave's hits (a hot spot): one LDS add; else one per lane, spread over the slots
+          const int lead = act ? __ffsll((unsigned long long)act) - 1 : 0;
+          const int ls = __shfl(slot, lead, 64);
+          if (__ballot(hit && slot != ls) == 0) {
+            if (act && lane == lead) atomicAdd(&s_cnt[ls], (uint32_t)__popcll(act));
+          } else if (hit) {
+            atomicAdd(&s_cnt[slot], 1u);
+          }
+        } else {
+          while (act) {  // equal slots aggregated within the wave
+            const int lead = __ffsll((unsigned long long)act) - 1;
+            const int ls = __shfl(slot, lead, 64);
+            const uint64_t same = __ballot(hit && slot == ls);
+            if (lane == lead) atomicAdd(&hcnt[ls], (unsigned long long)__popcll(same));
+            act &= ~same;
+          }
+        }
+      }
+    }
+  }
+  if (acc_n && lane == 0) atomicAdd(&jrem[acc_c], (unsigned long long)acc_n);
+  if (LDS && COUNT) {  // one global atomic per hit slot per workgroup
+    __syncthreads();
+    for (int i = threadIdx.x; i < nh; i += blockDim.x)
+      if (s_cnt[i]) atomicAdd(&hcnt[i], (unsigned long long)s_cnt[i]);
+  }
+}
+
+// keep[i] = posting i of the chunk's flattened lists stays; keep[total] = 0 (the scan's last element)
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_host_flag(const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                                   int nj, int64_t total, const uint64_t* __restrict__ hset, int nh,
+                                                   int32_t* __restrict__ keep) {
+  __shared__ uint64_t s_set[LDS ? HOST_LDS_MAX : 1];
+  const uint64_t* hs = stage_set<LDS>(s_set, hset, nh);
+  if (blockIdx.x == 0 && threadIdx.x == 0) keep[total] = 0;
+  int64_t begin, end;
+  host_span(total, &begin, &end);
+  SegCursor cur;
+  for (int64_t base = begin; base < end; base += HOST_TILE) {
+    int slots[4], cs[4];
+    mark_tile<LDS>(cur, jobs, off, nj, total, hs, nh, base, end, slots, cs);
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+      if (cs[u] >= 0) keep[base + u * 256 + threadIdx.x] = slots[u] < 0;
+  }
 }
 
 unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
@@ -630,6 +822,235 @@ extern "C" int yrwi_remove_postings(yrwi_ctx* ctx, const uint8_t* terms12, int32
       R.n = J.n - rem[(size_t)j];
       it->second = R;
       index_changed(ctx, jkey[(size_t)j], rem[(size_t)j], true);
+    }
+  }
+  put_stats(st, S, T);
+  return 0;
+}
+
+// ---------------------------------------------------------------- removal and counts by host
+namespace {
+
+// what both host calls start from: the host set and the selected lists, flattened
+struct HostPass {
+  std::vector<uint64_t> in;  // the 36-bit key of every host given, in the caller's order
+  std::vector<uint64_t> hk;  // the set: sorted, each once
+  std::vector<KeyT> jkey;
+  std::vector<RmJob> jobs;
+  std::vector<int64_t> off;
+  int64_t total = 0;
+  uint64_t* d_hk = nullptr;
+  RmJob* d_jobs = nullptr;
+  int64_t* d_off = nullptr;
+  std::vector<int64_t> res;  // after host_mark: hits per selected list, then (count) postings per set slot
+};
+
+// arguments -> host set and selected lists (host only); waits for the batches in flight
+int host_select(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uint8_t* hosts6, int32_t nhosts,
+                HostPass* P) {
+  P->in.resize((size_t)nhosts);
+  for (int32_t i = 0; i < nhosts; i++) {
+    uint64_t x = 0;
+    for (int j = 0; j < 6; j++) {  // key_of's rule, per character
+      const int8_t v = AHP[hosts6[(size_t)i * 6 + j]];
+      if (v < 0) return ctx->fail(YRWI_E_HASH, "host hash is not well-formed Base64");
+      x = (x << 6) | (uint64_t)v;
+    }
+    P->in[(size_t)i] = x;
+  }
+  P->hk = P->in;
+  std::sort(P->hk.begin(), P->hk.end());
+  P->hk.erase(std::unique(P->hk.begin(), P->hk.end()), P->hk.end());
+  std::vector<KeyT> tks;
+  {
+    std::unordered_set<KeyT, KeyHash> seen;
+    for (int32_t i = 0; i < nterms; i++) {
+      KeyT tk;
+      if (!key_of(terms12 + (size_t)i * 12, &tk)) return ctx->fail(YRWI_E_HASH, "term hash is not well-formed Base64");
+      if (seen.insert(tk).second) tks.push_back(tk);
+    }
+  }
+  hipSetDevice(ctx->device);
+  drain(ctx);
+  auto take = [&](const KeyT& tk, const ListRec& R) {
+    if (R.n == 0) return;
+    P->jkey.push_back(tk);
+    P->jobs.push_back(RmJob{R.khi, R.klo, R.rows, R.n, nullptr, nullptr, nullptr});
+    P->off.push_back(P->total);
+    P->total += R.n;
+  };
+  if (nterms == 0) {
+    for (auto& kv : ctx->lists) take(kv.first, kv.second);
+  } else {
+    for (const KeyT& tk : tks) {
+      auto it = ctx->lists.find(tk);
+      if (it != ctx->lists.end()) take(tk, it->second);
+    }
+  }
+  return 0;
+}
+
+unsigned mark_blocks(int64_t n) { return (unsigned)std::min<int64_t>((n + HOST_TILE - 1) / HOST_TILE, HOST_MARK_BLOCKS); }
+
+// The marking pass on lane L (a new pass): the set and the list table uploaded once, one launch over
+// the flattened keys, one read-back, one wait.  4 launches, 2 syncs, whatever was selected or given.
+int host_mark(yrwi_ctx* ctx, Lane* L, HostPass* P, bool count, Tally* T) {
+  if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
+  T->syncs++;
+  const int nj = (int)P->jobs.size(), nh = (int)P->hk.size();
+  const int64_t nres = (int64_t)nj + (count ? nh : 0);
+  P->d_hk = arena_alloc<uint64_t>(L, nh);
+  P->d_jobs = arena_alloc<RmJob>(L, nj);
+  P->d_off = arena_alloc<int64_t>(L, nj);
+  unsigned long long* res = arena_alloc<unsigned long long>(L, nres);
+  if (!P->d_hk || !P->d_jobs || !P->d_off || !res) return ctx->fail(YRWI_E_NOMEM, "device allocation (host marking pass)");
+  if (int rc = upload(L, P->d_hk, P->hk, P->d_jobs, P->jobs, P->d_off, P->off)) return ctx->take(L, rc);
+  HIPCHK(ctx, hipMemsetAsync(res, 0, (size_t)nres * 8, L->stream));
+  const dim3 g(mark_blocks(P->total)), b(256);
+  const bool lds = nh <= HOST_LDS_MAX;
+  if (lds && count)
+    hipLaunchKernelGGL((k_host_mark<true, true>), g, b, 0, L->stream, P->d_jobs, P->d_off, nj, P->total, P->d_hk, nh, res, res + nj);
+  else if (lds)
+    hipLaunchKernelGGL((k_host_mark<true, false>), g, b, 0, L->stream, P->d_jobs, P->d_off, nj, P->total, P->d_hk, nh, res, res + nj);
+  else if (count)
+    hipLaunchKernelGGL((k_host_mark<false, true>), g, b, 0, L->stream, P->d_jobs, P->d_off, nj, P->total, P->d_hk, nh, res, res + nj);
+  else
+    hipLaunchKernelGGL((k_host_mark<false, false>), g, b, 0, L->stream, P->d_jobs, P->d_off, nj, P->total, P->d_hk, nh, res, res + nj);
+  HIPCHK(ctx, hipGetLastError());
+  const int64_t* h = reinterpret_cast<const int64_t*>(readback(L, &L->down_stage, res, nres, 8, 8));
+  if (!h) return ctx->take(L, YRWI_E_HIP);
+  T->launches += 4;
+  HIPCHK(ctx, lane_sync(L));
+  T->syncs++;
+  P->res.assign(h, h + nres);  // (the pinned landing buffer may be reused)
+  return 0;
+}
+
+// rows compacted at a time: YRWI_RM_CHUNK, read per call (tests force chunk boundaries with it)
+int64_t rm_chunk() {
+  const char* e = getenv("YRWI_RM_CHUNK");
+  const int64_t v = e ? atoll(e) : RM_CHUNK_DEFAULT;
+  return std::min<int64_t>(std::max<int64_t>(v, 256), (int64_t)INT32_MAX - 1);
+}
+
+}  // namespace
+
+extern "C" int yrwi_count_hosts(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uint8_t* hosts6,
+                                int32_t nhosts, int64_t* counts, int64_t* lists_hit) {
+  if (!ctx || nterms < 0 || nhosts < 0 || (nterms > 0 && !terms12) || (nhosts > 0 && (!hosts6 || !counts)))
+    return YRWI_E_ARG;
+  HostPass P;
+  if (int rc = host_select(ctx, terms12, nterms, hosts6, nhosts, &P)) return rc;
+  for (int32_t i = 0; i < nhosts; i++) counts[i] = 0;
+  if (lists_hit) *lists_hit = 0;
+  if (P.hk.empty() || P.jobs.empty()) return 0;
+  Tally T;
+  if (int rc = host_mark(ctx, ctx->lanes[0], &P, true, &T)) return rc;
+  const size_t nj = P.jobs.size();
+  for (int32_t i = 0; i < nhosts; i++) {
+    const size_t slot = (size_t)(std::lower_bound(P.hk.begin(), P.hk.end(), P.in[(size_t)i]) - P.hk.begin());
+    counts[i] = P.res[nj + slot];
+  }
+  if (lists_hit)
+    for (size_t j = 0; j < nj; j++) *lists_hit += P.res[j] > 0;
+  return 0;
+}
+
+extern "C" int yrwi_remove_hosts(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uint8_t* hosts6,
+                                 int32_t nhosts, yrwi_update_stats* st) {
+  if (!ctx || nterms < 0 || nhosts < 0 || (nterms > 0 && !terms12) || (nhosts > 0 && !hosts6)) return YRWI_E_ARG;
+  yrwi_update_stats S;
+  std::memset(&S, 0, sizeof(S));
+  Tally T;
+  if (st) std::memset(st, 0, sizeof(*st));
+  HostPass P;
+  if (int rc = host_select(ctx, terms12, nterms, hosts6, nhosts, &P)) return rc;
+  if (P.hk.empty() || P.jobs.empty()) return 0;
+  Lane* L = ctx->lanes[0];
+  if (int rc = host_mark(ctx, L, &P, false, &T)) return rc;
+  const int nj = (int)P.jobs.size(), nh = (int)P.hk.size();
+  const std::vector<int64_t>& rem = P.res;
+  // ---- the lists that lose rows (an emptied list needs no compaction), in chunks of whole lists
+  std::vector<int> lose;
+  std::vector<RmJob> cjobs;
+  std::vector<int64_t> coff;            // offsets within the list's chunk
+  std::vector<std::pair<int, int>> ch;  // chunks: [first, last) of cjobs
+  const int64_t cap = rm_chunk();
+  int64_t ctotal = 0, maxc = 0;
+  for (int j = 0; j < nj; j++) {
+    if (rem[(size_t)j] == 0) continue;
+    lose.push_back(j);
+    if (rem[(size_t)j] == P.jobs[(size_t)j].n) continue;
+    RmJob J = P.jobs[(size_t)j];
+    const size_t nn = (size_t)(J.n - rem[(size_t)j]);
+    J.orows = ctx->index_mem.alloc(nn * 40);
+    J.okhi = reinterpret_cast<uint64_t*>(ctx->index_mem.alloc(nn * 8));
+    J.oklo = ctx->index_mem.alloc(nn);
+    if (!J.orows || !J.okhi || !J.oklo) return ctx->fail(YRWI_E_NOMEM, "device index allocation failed");
+    P.jobs[(size_t)j] = J;
+    if (ch.empty() || ctotal + J.n > cap) {  // (a list longer than the cap: a chunk of its own)
+      ch.push_back({(int)cjobs.size(), (int)cjobs.size()});
+      ctotal = 0;
+    }
+    cjobs.push_back(J);
+    coff.push_back(ctotal);
+    ctotal += J.n;
+    ch.back().second = (int)cjobs.size();
+    maxc = std::max(maxc, ctotal);
+  }
+  if (lose.empty()) {
+    put_stats(st, S, T);
+    return 0;
+  }
+  if (!ch.empty()) {
+    RmJob* d_cjobs = arena_alloc<RmJob>(L, (int64_t)cjobs.size());
+    int64_t* d_coff = arena_alloc<int64_t>(L, (int64_t)cjobs.size());
+    int32_t* keep = arena_alloc<int32_t>(L, maxc + 1);
+    int64_t* kx = arena_alloc<int64_t>(L, maxc + 1);
+    size_t tb = 0;
+    HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, keep, kx, (int)(maxc + 1), L->stream));
+    void* tmp = L->arena.alloc(tb);
+    if (!d_cjobs || !d_coff || !keep || !kx || !tmp)
+      return ctx->fail(YRWI_E_NOMEM, "device allocation (remove_hosts compaction)");
+    if (int rc = upload(L, d_cjobs, cjobs, d_coff, coff)) return ctx->take(L, rc);
+    T.launches++;
+    for (const auto& c : ch) {  // flag -> scan -> place, each chunk in the scratch of the one before
+      const int ncj = c.second - c.first;
+      const int64_t n = coff[(size_t)c.second - 1] + cjobs[(size_t)c.second - 1].n;
+      const RmJob* dj = d_cjobs + c.first;
+      const int64_t* doff = d_coff + c.first;
+      if (nh <= HOST_LDS_MAX)
+        hipLaunchKernelGGL((k_host_flag<true>), dim3(mark_blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, P.d_hk, nh, keep);
+      else
+        hipLaunchKernelGGL((k_host_flag<false>), dim3(mark_blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, P.d_hk, nh, keep);
+      size_t tbc = tb;
+      HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(tmp, tbc, keep, kx, (int)(n + 1), L->stream));
+      hipLaunchKernelGGL(k_rm_place, dim3(blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, keep, kx);
+      HIPCHK(ctx, hipGetLastError());
+      T.launches += 3;
+    }
+    HIPCHK(ctx, lane_sync(L));
+    T.syncs++;
+  }
+  // ---- bookkeeping, as yrwi_remove_postings: the removed postings are the dictionary churn
+  for (int j : lose) {
+    const RmJob& J = P.jobs[(size_t)j];
+    auto it = ctx->lists.find(P.jkey[(size_t)j]);
+    S.removed += rem[(size_t)j];
+    S.terms++;
+    ctx->npostings -= rem[(size_t)j];
+    if (rem[(size_t)j] == J.n) {
+      index_changed(ctx, P.jkey[(size_t)j], J.n, false);
+      ctx->lists.erase(it);
+      S.emptied_terms++;
+    } else {
+      ListRec R;
+      R.khi = J.okhi;
+      R.klo = J.oklo;
+      R.rows = J.orows;
+      R.n = J.n - rem[(size_t)j];
+      it->second = R;
+      index_changed(ctx, P.jkey[(size_t)j], rem[(size_t)j], true);
     }
   }
   put_stats(st, S, T);

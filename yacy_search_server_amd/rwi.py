@@ -367,6 +367,41 @@ class RWIIndex:
                                                         ctypes.byref(st)))
         return {f: getattr(st, f) for f, _ in _lib.CUpdateStats._fields_}
 
+    @staticmethod
+    def _host_args(hosts: Sequence[bytes], terms: Optional[Sequence[bytes]]):
+        hb = b"".join(bytes(h) for h in hosts)
+        if len(hb) != 6 * len(hosts):
+            raise ValueError("host hashes must be 6 bytes")
+        return np.frombuffer(hb, dtype=np.uint8), np.frombuffer(_hashes(terms or ()), dtype=np.uint8)
+
+    def remove_hosts(self, hosts: Sequence[bytes], terms: Optional[Sequence[bytes]] = None) -> dict:
+        """Removes every posting of the hosts (6-byte host hashes: url-hash characters 6..11, as
+        QueryFilter's sitehash) from the lists of `terms`, or with terms=None from every list
+        (yrwi_remove_hosts); no list leaves the device.  Returns the call's yrwi_update_stats as
+        a dict, as remove_postings does for the url hashes of those hosts."""
+        hb, tb = self._host_args(hosts, terms)
+        if terms is not None and len(terms) == 0:
+            return {f: 0 for f, _ in _lib.CUpdateStats._fields_}  # no term named: nothing to do
+        st = _lib.CUpdateStats()
+        _check(self._h, _lib.lib().yrwi_remove_hosts(self._h, tb.ctypes.data if len(tb) else None, len(tb) // 12,
+                                                     hb.ctypes.data if len(hb) else None, len(hb) // 6,
+                                                     ctypes.byref(st)))
+        return {f: getattr(st, f) for f, _ in _lib.CUpdateStats._fields_}
+
+    def count_hosts(self, hosts: Sequence[bytes], terms: Optional[Sequence[bytes]] = None) -> Tuple[np.ndarray, int]:
+        """What remove_hosts(hosts, terms) would remove, the index unchanged (yrwi_count_hosts):
+        (postings of each host in the selected lists, int64, in the order given; selected lists
+        with at least one of them)."""
+        hb, tb = self._host_args(hosts, terms)
+        counts = np.zeros(len(hosts), dtype=np.int64)
+        if terms is not None and len(terms) == 0:
+            return counts, 0
+        hit = ctypes.c_int64()
+        _check(self._h, _lib.lib().yrwi_count_hosts(self._h, tb.ctypes.data if len(tb) else None, len(tb) // 12,
+                                                    hb.ctypes.data if len(hb) else None, len(hb) // 6,
+                                                    counts.ctypes.data if len(counts) else None, ctypes.byref(hit)))
+        return counts, hit.value
+
     def load_heaps(self, paths: Sequence[str], order_by_name: bool = False) -> "_lib.CLoadStats":
         """Load YaCy BLOB heap files (IndexCell's ReferenceContainerArray) into the index;
         lists already present act as the RAM cache (the files' rows win)."""
