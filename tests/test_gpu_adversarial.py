@@ -365,6 +365,47 @@ def test_pruning_with_ties_at_k(n, mode):
         ix.close()
 
 
+LADDER = ((700, 100), (4000, 100), (8200, 3000), (16500, 3000))  # (rows, k): 1, 2, 5 and 9 chunks of 2048
+
+
+def test_topk_pass_ladder():
+    """The top-k passes over the chunks' candidate lists (run_rank_phase, yrwi_rank.cpp), one
+    batch of single-term queries whose lists take different numbers of passes:
+      a missing term       no chunk: the count is the pass's zero word
+      700 rows, k = 100    one chunk: final as k_score left it, never in a pass
+      4000 rows, k = 100   two chunks, merged in pass 1; it sits out the later passes, so its
+                           final list stays pass 1's output while the others' inputs move on
+      8200 rows, k = 3000  five chunks: 5 -> 2 -> 1 lists
+      16500 rows, k = 3000 nine chunks: 9 -> 3 -> 2 -> 1 lists
+    The batch's largest k is 3000: chunk lists of stride 2048, 8192 candidates per group, so
+    pass 1 merges 4 lists a group and the later passes (stride 3000) 2.  Rows of few values:
+    ties cross the list boundaries.  The batch in this order and reversed (other group bases),
+    through search_batch and through the call that returns the hits' rows."""
+    from test_gpu_hit_rows import _same as _same_rows
+    assert [-(-n // 2048) for n, _ in LADDER] == [1, 2, 5, 9]
+    d = {b"TERMladder%d_" % i: adv_rows(n, 80 + i, "few") for i, (n, _) in enumerate(LADDER)}
+    assert [len(r) for r in d.values()] == [n for n, _ in LADDER]
+    prof = jl.RankingProfile()
+    rp, op = _rp(prof), orc.profile_from(prof)
+    cases = [(b"TERMladderNO", 100, b"", [])]
+    for (h, rows), (_, k) in zip(d.items(), LADDER):
+        exp = _orc_raw(d, [h], [], op, "en", NOW, k)
+        assert len(exp) == k * HIT  # precondition, from the reference alone: every list fills its k
+        cases.append((h, k, exp, orc.term_search(d, [h], [], INF, NOW)))
+    ix = RWIIndex(0)
+    try:
+        for h, rows in d.items():
+            ix.add(h, rows)
+        for order in (cases, cases[::-1]):
+            batch = [Query([h], [], k=k, profile=rp, now_ms=NOW) for h, k, _, _ in order]
+            for (h, k, exp, _), g in zip(order, _gpu_raw(ix, batch)):
+                _same_hits(g, exp, (h, k, order is cases))
+            for (h, k, exp, joined), g in zip(order, ix.search_batch(batch, rows=True)):
+                _same_rows(g, _decode(exp), joined, (h, k, order is cases, "rows"))
+    finally:
+        ix.close()
+
+
 # ------------------------------------------------------------------ f
 def test_flag_bits_outside_tables():
     """Flag words of one bit each (0..31), all ones and none, 600 rows (CardTab path, in

@@ -25,22 +25,24 @@ VARIANTS = {
     "probe": [(K, "    hipLaunchKernelGGL(kp, dim3((unsigned)probe_tiles), dim3(PROBE_TILE), 0, S(st), d_jobs, d_tile_base, d_pdesc,\n"
                   "                       merge_tiles, d_pairs, d_pair_uid, d_tile_src, d_tile_cnt, (const int2*)pperm, d_tile_lvl,\n"
                   "                       (const ProbeDesc*)d_prange);\n", 2)],
-    "reduce": [(K, "    hipLaunchKernelGGL(k_reduce, dim3((unsigned)total_chunks), dim3(CHUNK_THREADS),\n"
-                   "                       hp_any ? HPART_MAXS * sizeof(int32_t) : 0, S(st), d_q, d_chunk_q, d_chunks, d_shard);\n", 2)],
-    "shardfin": [(K, "  hipLaunchKernelGGL(k_shard_fin, dim3((unsigned)nq), dim3(64), 0, S(st), d_q, d_chunk_base, d_chunks, d_shard);\n", 2)],
-    "combine": [(K, "  hipLaunchKernelGGL(k_combine, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, S(st), d_q, nq, d_shards, world, d_norm);\n", 2)],
-    "emit": [(K, "  hipLaunchKernelGGL(k_emit, dim3((unsigned)nq), dim3(256), 0, S(st), d_q, nq, d_final, d_final_cnt, kmax,\n"
-                 "                     d_hits, d_nout, mode);\n", 2)],
+    "reduce": [(K, "    hipLaunchKernelGGL(k_reduce, dim3((unsigned)s.chunks), dim3(CHUNK_THREADS),\n"
+                   "                       s.hp_any ? HPART_MAXS * sizeof(int32_t) : 0, S(st), s.d_q, s.d_chunk_q, s.d_chunks, s.d_shard);\n", 2)],
+    "shardfin": [(K, "  hipLaunchKernelGGL(k_shard_fin, dim3((unsigned)s.nq), dim3(64), 0, S(st), s.d_q, s.d_chunk_base, s.d_chunks, s.d_shard);\n", 2)],
+    "combine": [(K, "  hipLaunchKernelGGL(k_combine, dim3((unsigned)((s.nq + 63) / 64)), dim3(64), 0, S(st), s.d_q, s.nq, s.d_all, s.world,\n"
+                    "                     s.d_norm);\n", 2)],
+    "emit": [(K, "  hipLaunchKernelGGL(k_emit, dim3((unsigned)s.nq), dim3(256), 0, S(st), s.d_q, s.nq, s.d_final, s.d_final_cnt,\n"
+                 "                     dst.stride, dst.hits, dst.cnt, mode);\n", 2)],
     "copyin": [(K, "  hipLaunchKernelGGL(k_copy_in, dim3(blocks), dim3(256), 0, (hipStream_t)stream, c);\n", 2)],
-    "qtabs": [(K, "  hipLaunchKernelGGL(k_qtabs, dim3((unsigned)nq), dim3(256), 0, S(st), d_q, d_norm, qt);\n", 2)],
+    "qtabs": [(K, "  hipLaunchKernelGGL(k_qtabs, dim3((unsigned)s.nq), dim3(256), 0, S(st), s.d_q, (const NormState*)s.d_norm, qt);\n", 2)],
 }
-TOPQ = ("    hipLaunchKernelGGL(k_topq<4096>, dim3((unsigned)ngroups), dim3(TOPQ_THREADS), 2 * 4096 * sizeof(uint64_t), S(st),\n"
-        "                       d_gbase, d_gn, d_gk, d_in, d_in_cnt, in_stride, keff, d_out, d_out_cnt);\n")
+TOPQ = ("    hipLaunchKernelGGL(k_topq<4096>, dim3((unsigned)p.ngroups), dim3(TOPQ_THREADS), 2 * 4096 * sizeof(uint64_t), S(st),\n"
+        "                       p.d_gbase, p.d_gn, p.d_gk, p.d_in, p.d_in_cnt, p.in_stride, p.keff, p.d_out, p.d_out_cnt);\n")
 VARIANTS["topq"] = [(K, TOPQ, 2)]
 
 
 # variants that change code rather than duplicate a launch: (file, old, new) edits
 H = "yrwi_host.cpp"
+R = "yrwi_rank.cpp"
 def _compact_lds(kb):  # k_compact with kb KiB of unused dynamic LDS: fewer resident workgroups per CU
     return [(K, "hipLaunchKernelGGL(kc, dim3((unsigned)((s.tiles + COMPACT_TILES - 1) / COMPACT_TILES)), dim3(256), 0, S(st),",
              "hipLaunchKernelGGL(kc, dim3((unsigned)((s.tiles + COMPACT_TILES - 1) / COMPACT_TILES)), dim3(256), %d, S(st)," % (kb * 1024))]
@@ -52,16 +54,17 @@ EDITS = {
     "clds40": _compact_lds(40),
     # k_emit into a device buffer, then DMA copies to the pinned destination
     "emitdma": [
-        (H, "  uint8_t* land = nullptr;\n  {\n    void* hp = h_hits;",
-            "  uint8_t* land = nullptr;\n  void* hp_dst = nullptr;\n  void* np_dst = nullptr;\n  {\n    void* hp = h_hits;"),
-        (H, "    HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&d_hits), hp, 0));\n"
-            "    HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&d_nout), np, 0));\n  }",
-            "    hp_dst = hp;\n    np_dst = np;\n    d_hits = arena_alloc<yrwi_hit>(ctx, (int64_t)nq * kmax);\n"
-            "    d_nout = arena_alloc<int32_t>(ctx, nq);\n    if (!d_hits || !d_nout) return ctx->fail(YRWI_E_NOMEM, \"arena\");\n  }"),
-        (H, "  if (tm) { tm->ts = ctx->event(); hipEventRecord(tm->ts, ctx->stream); }\n  HIPCHK(ctx, lane_sync(ctx));\n  if (hD_land) {",
-            "  HIPCHK(ctx, hipMemcpyAsync(hp_dst, d_hits, hb, hipMemcpyDeviceToHost, ctx->stream));\n"
-            "  HIPCHK(ctx, hipMemcpyAsync(np_dst, d_nout, nb, hipMemcpyDeviceToHost, ctx->stream));\n"
-            "  if (tm) { tm->ts = ctx->event(); hipEventRecord(tm->ts, ctx->stream); }\n  HIPCHK(ctx, lane_sync(ctx));\n  if (hD_land) {"),
+        (R, "  uint8_t* land = nullptr;\n  HitList out;",
+            "  uint8_t* land = nullptr;\n  void* hp_dst = nullptr;\n  void* np_dst = nullptr;\n  HitList out;"),
+        (R, "  HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&D->out.hits), hp, 0));\n"
+            "  HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&D->out.cnt), np, 0));\n",
+            "  D->hp_dst = hp;\n  D->np_dst = np;\n  D->out.hits = arena_alloc<yrwi_hit>(ctx, (int64_t)R.nq * kmax);\n"
+            "  D->out.cnt = arena_alloc<int32_t>(ctx, R.nq);\n"
+            "  if (!D->out.hits || !D->out.cnt) return ctx->fail(YRWI_E_NOMEM, \"arena\");\n"),
+        (R, "  if (R.tm) { R.tm->ts = ctx->event(); hipEventRecord(R.tm->ts, ctx->stream); }\n  HIPCHK(ctx, lane_sync(ctx));\n",
+            "  HIPCHK(ctx, hipMemcpyAsync(D.hp_dst, D.out.hits, D.hb, hipMemcpyDeviceToHost, ctx->stream));\n"
+            "  HIPCHK(ctx, hipMemcpyAsync(D.np_dst, D.out.cnt, D.nb, hipMemcpyDeviceToHost, ctx->stream));\n"
+            "  if (R.tm) { R.tm->ts = ctx->event(); hipEventRecord(R.tm->ts, ctx->stream); }\n  HIPCHK(ctx, lane_sync(ctx));\n"),
     ],
 }
 

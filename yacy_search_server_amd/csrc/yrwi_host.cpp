@@ -859,586 +859,6 @@ static int plan_batch(Lane* L, std::vector<Plan>& plans) {
   return 0;
 }
 
-// Global host counts for authority (ReferenceOrder.java:176-216) across url-hash
-// shards: (query, host, count) messages to the host's owner rank, summed there,
-// totals sent back; the per-query max count is all-reduced.  Collective.
-static int exchange_host_counts(Lane* ctx, int nq, int64_t nslots, const std::vector<int64_t>& slot_base,
-                                uint64_t* d_hkeys, uint32_t* d_hcnt, ShardSum* d_ss) {
-  const int W = ctx->world, me = ctx->rank;
-  uint32_t* d_ocnt = arena_alloc<uint32_t>(ctx, W);
-  uint32_t* d_M = arena_alloc<uint32_t>(ctx, (int64_t)W * W);
-  int64_t* d_sb = arena_alloc<int64_t>(ctx, nq + 1);
-  int32_t* d_gmax = arena_alloc<int32_t>(ctx, nq);
-  if (!d_ocnt || !d_M || !d_sb || !d_gmax) return ctx->fail(YRWI_E_NOMEM, "arena");
-  HIPCHK(ctx, hipMemsetAsync(d_ocnt, 0, W * 4, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(d_gmax, 0, nq * 4, ctx->stream));
-  if (upload(ctx, d_sb, slot_base)) return YRWI_E_HIP;
-  const uint64_t* hkey = ctx->host_ids ? ctx->host_key : nullptr;  // tables of dense host ids (run_rank_phase)
-  if (launch_host_count(d_hkeys, nslots, W, d_ocnt, ctx->stream, hkey)) return ctx->fail(YRWI_E_HIP, "host count");
-  if (int rc = coll_allgather(ctx, d_ocnt, d_M, (size_t)W * 4)) return rc;
-  const uint8_t* hm = readback(ctx, &ctx->down_stage, d_M, (int64_t)W * W, 4, 4);
-  if (!hm) return YRWI_E_HIP;
-  HIPCHK(ctx, lane_sync(ctx));
-  std::vector<uint32_t> M((size_t)W * W);
-  std::memcpy(M.data(), hm, M.size() * 4);
-  // row s of M = what rank s sends to each owner
-  std::vector<int64_t> soff((size_t)W + 1, 0), roff((size_t)W + 1, 0);
-  for (int p = 0; p < W; p++) {
-    soff[(size_t)p + 1] = soff[(size_t)p] + M[(size_t)me * W + p];
-    roff[(size_t)p + 1] = roff[(size_t)p] + M[(size_t)p * W + me];
-  }
-  const int64_t nsend = soff[(size_t)W], nrecv = roff[(size_t)W];
-  std::vector<uint32_t> cur((size_t)W);
-  for (int p = 0; p < W; p++) cur[(size_t)p] = (uint32_t)soff[(size_t)p];
-  uint32_t* d_cur = arena_alloc<uint32_t>(ctx, W);
-  HostMsg* d_send = arena_alloc<HostMsg>(ctx, nsend);
-  uint64_t* d_sslot = arena_alloc<uint64_t>(ctx, nsend);
-  HostMsg* d_recv = arena_alloc<HostMsg>(ctx, nrecv);
-  uint32_t* d_reply = arena_alloc<uint32_t>(ctx, nrecv);
-  uint32_t* d_back = arena_alloc<uint32_t>(ctx, nsend);
-  uint64_t ocap = 1;
-  while (ocap < (uint64_t)(2 * std::max<int64_t>(nrecv, 1))) ocap <<= 1;
-  uint64_t* d_okeys = arena_alloc<uint64_t>(ctx, (int64_t)ocap);
-  uint32_t* d_ovals = arena_alloc<uint32_t>(ctx, (int64_t)ocap);
-  if (!d_cur || !d_send || !d_sslot || !d_recv || !d_reply || !d_back || !d_okeys || !d_ovals)
-    return ctx->fail(YRWI_E_NOMEM, "arena");
-  if (upload(ctx, d_cur, cur)) return YRWI_E_HIP;
-  HIPCHK(ctx, hipMemsetAsync(d_okeys, 0, ocap * 8, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(d_ovals, 0, ocap * 4, ctx->stream));
-  if (launch_host_pack(d_hkeys, d_hcnt, d_sb, nq, nslots, W, d_cur, d_send, d_sslot, ctx->stream, hkey))
-    return ctx->fail(YRWI_E_HIP, "host pack");
-  {
-    std::vector<Xfer> snd, rcv;
-    for (int p = 0; p < W; p++) {
-      snd.push_back({p, d_send + soff[(size_t)p], (size_t)(soff[(size_t)p + 1] - soff[(size_t)p]) * sizeof(HostMsg)});
-      rcv.push_back({p, d_recv + roff[(size_t)p], (size_t)(roff[(size_t)p + 1] - roff[(size_t)p]) * sizeof(HostMsg)});
-    }
-    if (int rc = coll_exchange(ctx, snd, rcv)) return rc;
-  }
-  if (launch_host_owner(d_recv, nrecv, d_okeys, d_ovals, ocap - 1, d_gmax, d_reply, ctx->stream))
-    return ctx->fail(YRWI_E_HIP, "host owner");
-  if (int rc = coll_allreduce_i32(ctx, d_gmax, (size_t)nq, true)) return rc;
-  {
-    std::vector<Xfer> snd, rcv;  // replies to what p sent me; totals for what I sent p
-    for (int p = 0; p < W; p++) {
-      snd.push_back({p, d_reply + roff[(size_t)p], (size_t)(roff[(size_t)p + 1] - roff[(size_t)p]) * 4});
-      rcv.push_back({p, d_back + soff[(size_t)p], (size_t)(soff[(size_t)p + 1] - soff[(size_t)p]) * 4});
-    }
-    if (int rc = coll_exchange(ctx, snd, rcv)) return rc;
-  }
-  if (launch_host_apply(d_back, d_sslot, nsend, d_hcnt, d_ss, d_gmax, nq, ctx->stream))
-    return ctx->fail(YRWI_E_HIP, "host apply");
-  return 0;
-}
-
-// Normalise (+ cross-shard exchange), then either score+top-k (hits) or all scores.
-static int run_rank_phase(Lane* ctx, std::vector<Plan>& plans, int32_t kmax, yrwi_hit* h_hits,
-                          int32_t* h_nout, int64_t* h_scores_all, yrwi_stats* st, Timing* tm, bool exchange = true,
-                          uint8_t* h_rows = nullptr) {
-  const int nq = (int)plans.size();
-  const int W = exchange ? ctx->world : 1;
-  const bool shx = exchange && ctx->sharded;  // the url-hash-shard protocol
-  std::vector<RankQ> rq((size_t)nq);
-  std::vector<int64_t> chunk_base((size_t)nq), slot_base((size_t)nq + 1);
-  int64_t chunks = 0, nslots = 0;
-  bool any_auth = false;
-  for (int qi = 0; qi < nq; qi++) {
-    Plan& P = plans[(size_t)qi];
-    RankQ& R = rq[(size_t)qi];
-    std::memset(&R, 0, sizeof(R));
-    R.feat = P.cont.feat;
-    R.uid = P.cont.uid;
-    R.ekhi = P.cont.uid ? nullptr : P.cont.khi;
-    R.eklo = P.cont.uid ? nullptr : P.cont.klo;
-    R.dkhi = ctx->dkhi;
-    R.dklo = ctx->dklo;
-    R.removed = P.removed;
-    R.n = P.empty ? 0 : P.cont.n;
-    R.pieces = P.empty || P.removed ? nullptr : P.pieces;
-    R.npieces = R.pieces ? P.npieces : 0;
-    R.ngroups = ceil_div(R.npieces, 64);
-    R.nchunks = ceil_div(R.n, CHUNK);
-    R.chunk_base = chunks;
-    chunk_base[(size_t)qi] = chunks;
-    chunks += R.nchunks;
-    R.prof = P.prof;
-    R.lang[0] = P.lang[0];
-    R.lang[1] = P.lang[1];
-    R.lang_ok = P.lang_ok;
-    R.now_ms = P.now_ms;
-    R.k = P.k;
-    R.want_authority = P.prof.coeff_authority > 12 && R.n > 0;
-    R.idx_tag = shx ? (uint32_t)ctx->rank << 28 : 0u;
-    R.doubledom = P.filter && P.filter->skip_double_dom ? 1 : 0;
-    R.host_rec = ctx->host_ids && P.cont.uid != nullptr ? 1 : 0;  // index records: dense host ids
-    R.kout = P.k;
-    if (R.doubledom) R.k = YRWI_MAX_K;  // pullOneRWI draws from the whole rwiStack (max_results_rwi)
-    // identical on every rank (same queries): decides the collective host-count exchange
-    if (P.prof.coeff_authority > 12) any_auth = true;
-    if (R.want_authority) {
-      uint64_t cap = 1;
-      while (cap < (uint64_t)(2 * R.n)) cap <<= 1;
-      R.hmask = cap - 1;
-      slot_base[(size_t)qi] = nslots;
-      nslots += (int64_t)cap;
-    } else {
-      slot_base[(size_t)qi] = nslots;
-    }
-    if (st) {
-      st->joined += R.n;
-      st->bytes_alg += 23 * (int64_t)P.seq.size() * R.n;  // ranking feature bytes per surviving posting and term
-      st->bytes_features += 23 * (int64_t)P.seq.size() * R.n;
-      st->bytes_alg_capped += 23 * (int64_t)P.seq.size() * R.n;
-    }
-  }
-  slot_base[(size_t)nq] = nslots;
-  // authority host tables of all queries, one allocation
-  uint64_t* d_hkeys = nullptr;
-  uint32_t* d_hcnt = nullptr;
-  if (nslots > 0) {
-    d_hkeys = arena_alloc<uint64_t>(ctx, nslots);
-    d_hcnt = arena_alloc<uint32_t>(ctx, nslots);
-    if (!d_hkeys || !d_hcnt) return ctx->fail(YRWI_E_NOMEM, "arena");
-    HIPCHK(ctx, hipMemsetAsync(d_hkeys, 0, (size_t)nslots * 8, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(d_hcnt, 0, (size_t)nslots * 4, ctx->stream));
-    for (int qi = 0; qi < nq; qi++) {
-      RankQ& R = rq[(size_t)qi];
-      if (!R.want_authority) continue;
-      R.hkeys = d_hkeys + slot_base[(size_t)qi];
-      R.hcnt = d_hcnt + slot_base[(size_t)qi];
-    }
-  }
-  // authority by partition (RankQ::ecnt; one context, records with host ids): each
-  // query's hosts hashed into ~HPART_TARGET-element buckets, per-element counts
-  int64_t hp_hist = 0, hp_elems = 0, hp_buckets = 0;
-  std::vector<int2> bq;
-  const char* hpm = getenv("YRWI_HPART_MAXB");  // (tests: fewer buckets, so large queries overflow the LDS tables)
-  const int64_t maxb = hpm ? std::max(1, std::min(HPART_MAXS, atoi(hpm))) : HPART_MAXS;
-  for (int qi = 0; qi < nq; qi++) {
-    RankQ& R = rq[(size_t)qi];
-    if (!R.want_authority || !R.host_rec || shx) continue;
-    R.hp_nb = (int32_t)std::min<int64_t>(maxb, std::max<int64_t>(1, ceil_div(R.n, HPART_TARGET)));
-    R.hp_hoff = hp_hist;
-    hp_hist += R.nchunks * R.hp_nb;
-    for (int32_t s = 0; s < R.hp_nb; s++) bq.push_back(make_int2(qi, s));
-    hp_buckets += R.hp_nb;
-  }
-  int32_t *d_hist = nullptr, *d_hoffs = nullptr, *d_ecnt = nullptr;
-  uint2* d_part = nullptr;
-  int2* d_bq = nullptr;
-  void* d_hptmp = nullptr;
-  size_t hp_tmp = 0;
-  if (hp_buckets > 0) {
-    for (int qi = 0; qi < nq; qi++) if (rq[(size_t)qi].hp_nb) hp_elems += rq[(size_t)qi].n;
-    hp_tmp = host_part_tmp_bytes(hp_hist);
-    d_hist = arena_alloc<int32_t>(ctx, hp_hist + 1);
-    d_hoffs = arena_alloc<int32_t>(ctx, hp_hist + 1);
-    d_ecnt = arena_alloc<int32_t>(ctx, hp_elems);
-    d_part = arena_alloc<uint2>(ctx, hp_elems);
-    d_bq = arena_alloc<int2>(ctx, hp_buckets);
-    d_hptmp = arena_alloc<uint8_t>(ctx, (int64_t)std::max<size_t>(hp_tmp, 1));
-    if (!d_hist || !d_hoffs || !d_ecnt || !d_part || !d_bq || !d_hptmp) return ctx->fail(YRWI_E_NOMEM, "arena");
-    HIPCHK(ctx, hipMemsetAsync(d_hist + hp_hist, 0, 4, ctx->stream));  // the scan's extra entry: the total
-    int64_t eb = 0;
-    for (int qi = 0; qi < nq; qi++) {
-      RankQ& R = rq[(size_t)qi];
-      if (!R.hp_nb) continue;
-      R.ecnt = d_ecnt + eb;
-      R.hp_hist = d_hist;
-      eb += R.n;
-    }
-    if (upload(ctx, d_bq, bq)) return YRWI_E_HIP;
-  }
-  // addRWIs constraints: one FilterQ per filtered query, key arrays and flag counters
-  std::vector<int> fidx((size_t)nq, -1);
-  int nf = 0;
-  bool any_dd = false, any_flagcount = false;
-  for (int qi = 0; qi < nq; qi++) {
-    if (plans[(size_t)qi].filter) fidx[(size_t)qi] = nf++;
-    if (rq[(size_t)qi].doubledom) any_dd = true;
-    if (plans[(size_t)qi].filter && plans[(size_t)qi].filter->flagcount) any_flagcount = true;
-  }
-  int32_t* d_flag = nullptr;
-  if (nf > 0) {
-    std::vector<FilterQ> fq((size_t)nf);
-    std::vector<uint64_t> sx, uh;
-    std::vector<uint8_t> ul;
-    std::vector<int64_t> sx0((size_t)nf), uh0((size_t)nf);
-    for (int qi = 0; qi < nq; qi++) {
-      if (fidx[(size_t)qi] < 0) continue;
-      const yrwi_filter& F = *plans[(size_t)qi].filter;
-      FilterQ& G = fq[(size_t)fidx[(size_t)qi]];
-      std::vector<uint64_t> v;
-      std::vector<KeyT> u;
-      build_filterq(F, &G, &v, &u);
-      sx0[(size_t)fidx[(size_t)qi]] = (int64_t)sx.size();
-      sx.insert(sx.end(), v.begin(), v.end());
-      uh0[(size_t)fidx[(size_t)qi]] = (int64_t)uh.size();
-      for (auto& k : u) { uh.push_back(k.hi); ul.push_back((uint8_t)k.lo); }
-    }
-    FilterQ* d_fq = arena_alloc<FilterQ>(ctx, nf);
-    uint64_t* d_sx = arena_alloc<uint64_t>(ctx, (int64_t)sx.size());
-    uint64_t* d_uh = arena_alloc<uint64_t>(ctx, (int64_t)uh.size());
-    uint8_t* d_ul = arena_alloc<uint8_t>(ctx, (int64_t)ul.size());
-    d_flag = any_flagcount ? arena_alloc<int32_t>(ctx, (int64_t)nf * 32) : nullptr;
-    if (!d_fq || !d_sx || !d_uh || !d_ul || (any_flagcount && !d_flag)) return ctx->fail(YRWI_E_NOMEM, "arena");
-    if (d_flag) HIPCHK(ctx, hipMemsetAsync(d_flag, 0, (size_t)nf * 32 * 4, ctx->stream));
-    for (int qi = 0; qi < nq; qi++) {
-      const int f = fidx[(size_t)qi];
-      if (f < 0) continue;
-      FilterQ& G = fq[(size_t)f];
-      G.siteex = d_sx + sx0[(size_t)f];
-      G.url_hi = d_uh + uh0[(size_t)f];
-      G.url_lo = d_ul + uh0[(size_t)f];
-      G.flagcount = plans[(size_t)qi].filter->flagcount ? d_flag + (int64_t)f * 32 : nullptr;
-      rq[(size_t)qi].filt = d_fq + f;
-    }
-    if (upload(ctx, d_fq, fq, d_sx, sx, d_uh, uh, d_ul, ul))
-      return YRWI_E_HIP;
-  }
-  // flag counters back to the callers' filters (summed over the shards)
-  auto flagcounts_out = [&]() -> int {
-    if (!d_flag) return 0;
-    if (shx)
-      if (int rc = coll_allreduce_i32(ctx, d_flag, (size_t)nf * 32, false)) return rc;
-    const uint8_t* hf = readback(ctx, &ctx->down_stage, d_flag, (int64_t)nf * 32, 4, 4);
-    if (!hf) return YRWI_E_HIP;
-    HIPCHK(ctx, lane_sync(ctx));
-    std::vector<int32_t> h((size_t)nf * 32);
-    std::memcpy(h.data(), hf, h.size() * 4);
-    for (int qi = 0; qi < nq; qi++)
-      if (fidx[(size_t)qi] >= 0 && plans[(size_t)qi].filter->flagcount)
-        std::memcpy(plans[(size_t)qi].filter->flagcount, &h[(size_t)fidx[(size_t)qi] * 32], 32 * 4);
-    return 0;
-  };
-  RankQ* d_q = arena_alloc<RankQ>(ctx, nq);
-  int64_t* d_cb = arena_alloc<int64_t>(ctx, nq);
-  ChunkSum* d_cs = arena_alloc<ChunkSum>(ctx, chunks);
-  ShardSum* d_ss = arena_alloc<ShardSum>(ctx, nq);
-  ShardSum* d_all = shx ? arena_alloc<ShardSum>(ctx, (int64_t)nq * W) : d_ss;
-  NormState* d_norm = arena_alloc<NormState>(ctx, nq);
-  if (!d_q || !d_cb || !d_cs || !d_ss || !d_all || !d_norm) return ctx->fail(YRWI_E_NOMEM, "arena");
-  std::vector<int32_t> chunk_q((size_t)chunks);
-  for (int qi = 0; qi < nq; qi++)
-    for (int64_t c = 0; c < rq[(size_t)qi].nchunks; c++) chunk_q[(size_t)(chunk_base[(size_t)qi] + c)] = qi;
-  int32_t* d_cq = arena_alloc<int32_t>(ctx, chunks);
-  if (!d_cq) return ctx->fail(YRWI_E_NOMEM, "arena");
-  // groups of the compaction's pieces (k_piece_merge): (query, group) of each
-  std::vector<int2> group_q;
-  for (int qi = 0; qi < nq; qi++)
-    for (int64_t g = 0; g < rq[(size_t)qi].ngroups; g++) group_q.push_back(make_int2(qi, (int32_t)g));
-  int2* d_gq = nullptr;
-  if (!group_q.empty()) {
-    ChunkSum* d_groups = arena_alloc<ChunkSum>(ctx, (int64_t)group_q.size());
-    d_gq = arena_alloc<int2>(ctx, (int64_t)group_q.size());
-    if (!d_groups || !d_gq) return ctx->fail(YRWI_E_NOMEM, "arena");
-    int64_t gb = 0;
-    for (int qi = 0; qi < nq; qi++) {
-      RankQ& R = rq[(size_t)qi];
-      R.groups = R.ngroups ? d_groups + gb : nullptr;
-      gb += R.ngroups;
-    }
-    if (upload(ctx, d_gq, group_q)) return YRWI_E_HIP;
-  }
-  if (upload(ctx, d_q, rq, d_cb, chunk_base, d_cq, chunk_q)) return YRWI_E_HIP;
-  HIPCHK(ctx, hipMemsetAsync(d_ss, 0, sizeof(ShardSum) * nq, ctx->stream));
-  hipEvent_t sp = span_open(ctx, tm);
-  hipEvent_t rmid = tm ? ctx->event() : nullptr;  // after k_reduce, before k_shard_fin
-  bool reduce = false;  // a query without the compaction's pieces
-  for (int qi = 0; qi < nq; qi++) reduce |= !rq[(size_t)qi].pieces && rq[(size_t)qi].nchunks > 0;
-  if (launch_reduce(d_q, d_cb, d_cq, nq, chunks, d_cs, d_ss, ctx->stream, rmid, hp_buckets > 0, reduce, d_gq,
-                    (int64_t)group_q.size()))
-    return ctx->fail(YRWI_E_HIP, "reduce launch");
-  if (hp_buckets > 0 &&
-      launch_host_part(d_q, d_cq, chunks, d_hist, d_hoffs, hp_hist, d_hptmp, hp_tmp, d_part, d_bq,
-                       (int32_t)hp_buckets, d_ss, ctx->stream))
-    return ctx->fail(YRWI_E_HIP, "host count launch");
-  span_close(ctx, tm, sp);
-  if (tm) tm->kreduce.push_back({sp, rmid});  // k_reduce alone: the population rocprofv3 averages
-  if (st) {
-    st->n_rank_passes++;
-    for (int qi = 0; qi < nq; qi++) {
-      const int64_t n = rq[(size_t)qi].n;
-      if (!rq[(size_t)qi].pieces) st->bytes_reduce += (int64_t)FEAT_BYTES * n + (rq[(size_t)qi].removed ? n : 0);
-      st->bytes_score += (int64_t)FEAT_BYTES * n + (rq[(size_t)qi].removed ? n : 0);
-    }
-  }
-  if (shx && any_auth) {
-    int rc2 = exchange_host_counts(ctx, nq, nslots, slot_base, d_hkeys, d_hcnt, d_ss);
-    if (rc2) return rc2;
-  }
-  if (shx) {
-    if (int rc = coll_allgather(ctx, d_ss, d_all, sizeof(ShardSum) * nq)) return rc;
-  }
-  sp = span_open(ctx, tm);
-  if (launch_combine(d_q, nq, d_all, W, d_norm, ctx->stream)) return ctx->fail(YRWI_E_HIP, "combine launch");
-  span_close(ctx, tm, sp);
-  if (tm) { tm->tn = ctx->event(); hipEventRecord(tm->tn, ctx->stream); }
-
-  if (h_scores_all) {  // yrwi_normalize_score
-    int64_t* d_sc = arena_alloc<int64_t>(ctx, rq[0].n);
-    if (!d_sc) return ctx->fail(YRWI_E_NOMEM, "arena");
-    if (launch_score_all(d_q, d_cq, nq, chunks, d_norm, d_sc, ctx->stream)) return ctx->fail(YRWI_E_HIP, "score launch");
-    HIPCHK(ctx, hipMemcpyAsync(h_scores_all, d_sc, sizeof(int64_t) * rq[0].n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, lane_sync(ctx));
-    NormState nsh;
-    HIPCHK(ctx, hipMemcpy(&nsh, d_norm, sizeof(nsh), hipMemcpyDeviceToHost));
-    if (nsh.D < 0) return ctx->fail(YRWI_E_UNSUPPORTED, "distance fold summary overflow");
-    return 0;
-  }
-
-  // ---- score + per-chunk top-k
-  int32_t keff = 1;
-  for (auto& R : rq) keff = std::max(keff, R.k);
-  const int32_t kc = std::min<int32_t>(keff, CHUNK);  // per-chunk candidate list stride
-  Cand* d_cand = arena_alloc<Cand>(ctx, std::max<int64_t>(chunks, 1) * kc);
-  int32_t* d_ccnt = arena_alloc<int32_t>(ctx, std::max<int64_t>(chunks, 1));
-  if (!d_cand || !d_ccnt) return ctx->fail(YRWI_E_NOMEM, "arena");
-  // d_zero[0]: a zero count (queries without chunks); d_zero[1]: k_score's redo count
-  int32_t* d_zero = arena_alloc<int32_t>(ctx, 2);
-  int32_t* d_redo = arena_alloc<int32_t>(ctx, std::max<int64_t>(chunks, 1));
-  if (!d_zero || !d_redo) return ctx->fail(YRWI_E_NOMEM, "arena");
-  HIPCHK(ctx, hipMemsetAsync(d_zero, 0, 2 * sizeof(int32_t), ctx->stream));
-  sp = span_open(ctx, tm);
-  // chunk order for k_score: every query's chunk 0, then every chunk 1, ... so that
-  // a big query's later chunks run after its threshold is set (PruneP)
-  std::vector<int32_t> order((size_t)chunks * 2);  // (chunk, query) pairs
-  {
-    // counting sort by chunk index c (stable in query order): O(chunks + max chunks)
-    int64_t maxc = 0;
-    for (auto& R : rq) maxc = std::max(maxc, R.nchunks);
-    std::vector<int64_t> at((size_t)maxc + 1, 0);
-    for (auto& R : rq)
-      for (int64_t c = 0; c < R.nchunks; c++) at[(size_t)c + 1]++;
-    for (int64_t c = 0; c < maxc; c++) at[(size_t)c + 1] += at[(size_t)c];
-    for (int qi = 0; qi < nq; qi++)
-      for (int64_t c = 0; c < rq[(size_t)qi].nchunks; c++) {
-        const size_t o = (size_t)at[(size_t)c]++;
-        order[2 * o] = (int32_t)(chunk_base[(size_t)qi] + c);
-        order[2 * o + 1] = qi;
-      }
-  }
-  int32_t* d_order = arena_alloc<int32_t>(ctx, 2 * chunks);
-  unsigned long long* d_tq = arena_alloc<unsigned long long>(ctx, nq);
-  uint8_t* d_qtab = arena_alloc<uint8_t>(ctx, (int64_t)nq * (int64_t)score_qtab_bytes());
-  if (!d_order || !d_tq || !d_qtab) return ctx->fail(YRWI_E_NOMEM, "arena");
-  if (upload(ctx, d_order, order)) return YRWI_E_HIP;
-  HIPCHK(ctx, hipMemsetAsync(d_tq, 0, sizeof(unsigned long long) * (size_t)nq, ctx->stream));
-  // (a separate launch of every query's first chunk, so that all later chunks
-  // start with a threshold, measured 39 + 86 us against 99 us for one launch:
-  // the seed launch is one round of full-length blocks)
-  const int64_t seed = 0;
-  // the k_score launches alone (the population rocprofv3 averages): from right
-  // before them to before k_score_full
-  hipEvent_t s0 = span_open(ctx, tm);
-  hipEvent_t smid = tm ? ctx->event() : nullptr;
-  if (launch_score(d_q, d_cq, d_order, nq, chunks, seed, d_norm, d_cand, d_ccnt, kc, d_redo, d_zero + 1, d_tq,
-                   d_qtab, ctx->stream, smid))
-    return ctx->fail(YRWI_E_HIP, "score launch");
-  span_close(ctx, tm, sp);
-  if (tm) tm->kscore.push_back({s0, smid});
-  // ---- top-k passes over groups of candidate lists until one list per query;
-  // a query with a single list (one chunk) is final as it stands
-  std::vector<const Cand*> fptr((size_t)nq);
-  std::vector<const int32_t*> fcnt((size_t)nq);
-  std::vector<int64_t> lists((size_t)nq), lbase((size_t)nq);
-  for (int qi = 0; qi < nq; qi++) {
-    lists[(size_t)qi] = rq[(size_t)qi].nchunks;
-    lbase[(size_t)qi] = chunk_base[(size_t)qi];
-    fptr[(size_t)qi] = d_cand + chunk_base[(size_t)qi] * kc;
-    fcnt[(size_t)qi] = lists[(size_t)qi] ? d_ccnt + chunk_base[(size_t)qi] : d_zero;
-  }
-  const Cand* cur = d_cand;
-  const int32_t* curc = d_ccnt;
-  int32_t in_stride = kc;
-  while (true) {
-    const int64_t G = std::max<int64_t>(2, std::min<int64_t>(64, topq_capacity(keff) / in_stride));
-    std::vector<int64_t> gb;
-    std::vector<int32_t> gn, gk;
-    std::vector<int> part;
-    for (int qi = 0; qi < nq; qi++) {
-      const int64_t L = lists[(size_t)qi];
-      if (L <= 1) continue;
-      const int64_t ng = ceil_div(L, G);
-      const int64_t first = (int64_t)gb.size();
-      for (int64_t g = 0; g < ng; g++) {
-        gb.push_back(lbase[(size_t)qi] + g * G);
-        gn.push_back((int32_t)std::min<int64_t>(G, L - g * G));
-        gk.push_back(rq[(size_t)qi].k);
-      }
-      lists[(size_t)qi] = ng;
-      lbase[(size_t)qi] = first;
-      part.push_back(qi);
-    }
-    if (gb.empty()) break;
-    const int64_t ngr = (int64_t)gb.size();
-    int64_t* d_gb = arena_alloc<int64_t>(ctx, ngr);
-    int32_t* d_gn = arena_alloc<int32_t>(ctx, ngr);
-    int32_t* d_gk = arena_alloc<int32_t>(ctx, ngr);
-    Cand* d_out = arena_alloc<Cand>(ctx, ngr * keff);
-    int32_t* d_oc = arena_alloc<int32_t>(ctx, ngr);
-    if (!d_gb || !d_gn || !d_gk || !d_out || !d_oc) return ctx->fail(YRWI_E_NOMEM, "arena");
-    if (upload(ctx, d_gb, gb, d_gn, gn, d_gk, gk)) return YRWI_E_HIP;
-    hipEvent_t sq = span_open(ctx, tm);
-    if (launch_topq(d_gb, d_gn, d_gk, ngr, cur, curc, in_stride, keff, d_out, d_oc, ctx->stream))
-      return ctx->fail(YRWI_E_HIP, "top-k launch");
-    span_close(ctx, tm, sq);
-    for (int qi : part) {
-      fptr[(size_t)qi] = d_out + lbase[(size_t)qi] * keff;
-      fcnt[(size_t)qi] = d_oc + lbase[(size_t)qi];
-    }
-    in_stride = keff;
-    cur = d_out;
-    curc = d_oc;
-  }
-  const Cand** d_fptr = arena_alloc<const Cand*>(ctx, nq);
-  const int32_t** d_fcnt = arena_alloc<const int32_t*>(ctx, nq);
-  // Results go straight into pinned host memory -- the caller's buffer when it
-  // came from yrwi_host_alloc, else this lane's landing buffer (then copied out
-  // per query).  One GPU: k_emit writes them (doubledom queries: their stacks,
-  // ordered by k_pull).  Sharded: every shard's stack is gathered, merged on the
-  // device (k_gmerge_*) and pulled (k_pull); every rank ends with the same lists.
-  const int32_t kint = any_dd ? YRWI_MAX_K : kmax;  // stack stride
-  const size_t hb = sizeof(yrwi_hit) * (size_t)nq * kmax, hb_al = (hb + 255) & ~(size_t)255;
-  const size_t nb = sizeof(int32_t) * (size_t)nq;
-  yrwi_hit* d_hits = nullptr;
-  int32_t* d_nout = nullptr;
-  const bool direct = ctx->hostreg && ctx->hostreg->contains(h_hits, hb) && ctx->hostreg->contains(h_nout, nb);
-  // the hits' rows (yrwi_query_*_rows) go the same way: into the caller's buffer when it is
-  // pinned and 8-byte aligned (k_hit_rows stores 8-byte words), else behind the hits in the
-  // landing buffer
-  const size_t rb = h_rows ? (size_t)YRWI_ROW_BYTES * (size_t)nq * kmax : 0;
-  const bool rows_direct = h_rows && ctx->hostreg && (reinterpret_cast<uintptr_t>(h_rows) & 7) == 0 &&
-                           ctx->hostreg->contains(h_rows, rb);
-  const size_t land_rows = direct ? 0 : (hb_al + nb + 255) & ~(size_t)255;
-  uint8_t* land = nullptr;
-  uint8_t* d_rows = nullptr;
-  {
-    void* hp = h_hits;
-    void* np = h_nout;
-    void* rp = h_rows;
-    if (!direct || (h_rows && !rows_direct)) {
-      land = stage_reserve(ctx, &ctx->out_stage, h_rows && !rows_direct ? land_rows + rb : hb_al + nb, true);
-      if (!land) return YRWI_E_HIP;
-    }
-    if (!direct) {
-      hp = land;
-      np = land + hb_al;
-    }
-    if (h_rows && !rows_direct) rp = land + land_rows;
-    if (h_rows) HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&d_rows), rp, 0));
-    // the emit kernels write the pinned destination directly (a DMA copy from a
-    // device buffer instead measured 1.17 vs 1.07 ms per C2 step)
-    HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&d_hits), hp, 0));
-    HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&d_nout), np, 0));
-  }
-  if (!d_fptr || !d_fcnt) return ctx->fail(YRWI_E_NOMEM, "arena");
-  // rows asked for: k_pull (doubledom, sharded) leaves its hits in device memory, where
-  // k_hit_rows reads them, looks their rows up and forwards them to the pinned destination
-  HitRowQ* d_hq = nullptr;
-  yrwi_hit* d_phits = d_hits;
-  int32_t* d_pnout = d_nout;
-  if (!h_rows) {
-    if (upload(ctx, d_fptr, fptr, d_fcnt, fcnt)) return YRWI_E_HIP;
-  } else {
-    std::vector<HitRowQ> hq((size_t)nq);
-    int own_shift = -1;
-    if (shx) {
-      own_shift = 6;
-      for (int w = ctx->world; w > 1; w >>= 1) own_shift--;
-    }
-    for (int qi = 0; qi < nq; qi++) {
-      const Plan& P = plans[(size_t)qi];
-      HitRowQ& H = hq[(size_t)qi];
-      H.rows = P.empty ? nullptr : P.cont.rows;
-      H.now_ms = P.now_ms;
-      H.src = shx || rq[(size_t)qi].doubledom ? HR_HITS : HR_CAND;
-      H.own_shift = own_shift;
-      H.own_rank = ctx->rank;
-      H.pad = 0;
-    }
-    d_hq = arena_alloc<HitRowQ>(ctx, nq);
-    if (!d_hq) return ctx->fail(YRWI_E_NOMEM, "arena");
-    // (the rows' descriptors ride in the candidate lists' copy kernel: no launch of their own)
-    if (upload(ctx, d_fptr, fptr, d_fcnt, fcnt, d_hq, hq)) return YRWI_E_HIP;
-    if (shx || any_dd) {
-      d_phits = arena_alloc<yrwi_hit>(ctx, (int64_t)nq * kmax);
-      d_pnout = arena_alloc<int32_t>(ctx, nq);
-      if (!d_phits || !d_pnout) return ctx->fail(YRWI_E_NOMEM, "arena");
-    }
-  }
-  std::vector<int32_t> hD;  // max-distance fold state per query (overflow check)
-  const uint8_t* hD_land = nullptr;
-  if (!shx) {
-    sp = span_open(ctx, tm);
-    if (launch_emit(d_q, nq, d_fptr, d_fcnt, kmax, d_hits, d_nout, 0, ctx->stream))
-      return ctx->fail(YRWI_E_HIP, "emit launch");
-    span_close(ctx, tm, sp);
-    if (any_dd) {
-      yrwi_hit* d_stack = arena_alloc<yrwi_hit>(ctx, (int64_t)nq * kint);
-      int32_t* d_scnt = arena_alloc<int32_t>(ctx, nq);
-      if (!d_stack || !d_scnt) return ctx->fail(YRWI_E_NOMEM, "arena");
-      sp = span_open(ctx, tm);
-      if (launch_emit(d_q, nq, d_fptr, d_fcnt, kint, d_stack, d_scnt, 2, ctx->stream) ||
-          launch_pull(d_q, nq, d_stack, d_scnt, kint, 1, kmax, d_phits, d_pnout, ctx->stream))
-        return ctx->fail(YRWI_E_HIP, "doubledom launch");
-      span_close(ctx, tm, sp);
-    }
-  } else {
-    yrwi_hit* d_mine = arena_alloc<yrwi_hit>(ctx, (int64_t)nq * kint);
-    int32_t* d_mcnt = arena_alloc<int32_t>(ctx, nq);
-    yrwi_hit* d_allh = arena_alloc<yrwi_hit>(ctx, (int64_t)nq * kint * W);
-    int32_t* d_alln = arena_alloc<int32_t>(ctx, (int64_t)nq * W);
-    uint32_t* d_slot = arena_alloc<uint32_t>(ctx, (int64_t)nq * kint * W);
-    uint8_t* d_dup = arena_alloc<uint8_t>(ctx, (int64_t)nq * kint * W);
-    yrwi_hit* d_stack = arena_alloc<yrwi_hit>(ctx, (int64_t)nq * kint);
-    int32_t* d_scnt = arena_alloc<int32_t>(ctx, nq);
-    if (!d_mine || !d_mcnt || !d_allh || !d_alln || !d_slot || !d_dup || !d_stack || !d_scnt)
-      return ctx->fail(YRWI_E_NOMEM, "arena");
-    sp = span_open(ctx, tm);
-    if (launch_emit(d_q, nq, d_fptr, d_fcnt, kint, d_mine, d_mcnt, 1, ctx->stream))
-      return ctx->fail(YRWI_E_HIP, "emit launch");
-    span_close(ctx, tm, sp);
-    if (int rc = coll_allgather(ctx, d_mine, d_allh, sizeof(yrwi_hit) * (size_t)nq * kint)) return rc;
-    if (int rc = coll_allgather(ctx, d_mcnt, d_alln, sizeof(int32_t) * (size_t)nq)) return rc;
-    if (ctx->release_after_final) turn_release(ctx);  // the next batch part's collectives may follow now
-    sp = span_open(ctx, tm);
-    if (launch_gmerge(d_q, d_allh, d_alln, W, nq, kint, d_slot, d_dup, d_stack, d_scnt, ctx->stream) ||
-        launch_pull(d_q, nq, d_stack, d_scnt, kint, 0, kmax, d_phits, d_pnout, ctx->stream))
-      return ctx->fail(YRWI_E_HIP, "shard merge launch");
-    span_close(ctx, tm, sp);
-    hD_land = readback(ctx, &ctx->down_stage, reinterpret_cast<const uint8_t*>(d_norm) + offsetof(NormState, D), nq,
-                       4, (int64_t)sizeof(NormState));
-    if (!hD_land) return YRWI_E_HIP;
-  }
-  if (h_rows) {
-    sp = span_open(ctx, tm);
-    if (launch_hit_rows(d_q, d_hq, nq, d_fptr, d_fcnt, d_phits, d_pnout, kmax, d_hits, d_nout, d_rows, ctx->stream))
-      return ctx->fail(YRWI_E_HIP, "hit rows launch");
-    span_close(ctx, tm, sp);
-  }
-  if (tm) { tm->ts = ctx->event(); hipEventRecord(tm->ts, ctx->stream); }
-  HIPCHK(ctx, lane_sync(ctx));
-  if (hD_land) {
-    hD.resize((size_t)nq);
-    std::memcpy(hD.data(), hD_land, (size_t)nq * 4);
-  }
-  for (int32_t D : hD)
-    if (D < 0) return ctx->fail(YRWI_E_UNSUPPORTED, "distance fold summary overflow");
-  if (!direct) {
-    std::memcpy(h_nout, land + hb_al, nb);
-    for (int qi = 0; qi < nq; qi++)
-      std::memcpy(h_hits + (size_t)qi * kmax, land + sizeof(yrwi_hit) * (size_t)qi * kmax,
-                  sizeof(yrwi_hit) * (size_t)std::max(0, std::min(h_nout[qi], kmax)));
-  }
-  if (h_rows && !rows_direct)
-    for (int qi = 0; qi < nq; qi++)
-      std::memcpy(h_rows + (size_t)YRWI_ROW_BYTES * (size_t)qi * kmax,
-                  land + land_rows + (size_t)YRWI_ROW_BYTES * (size_t)qi * kmax,
-                  (size_t)YRWI_ROW_BYTES * (size_t)std::max(0, std::min(h_nout[qi], kmax)));
-  return flagcounts_out();
-}
-
 static int64_t now_ns() {
   return (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
              std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -1568,7 +988,7 @@ static int run_batch_part_(const yrwi_ctx* ix, Lane* L, const yrwi_query_desc* q
       hipEventRecord(tm.tj, L->stream);
     }
     // (a pass's rows leave its arena here, before the next pass reuses it, at its queries' own positions)
-    rc = run_rank_phase(L, plans, kmax, out + (size_t)g0 * kmax, nout + g0, nullptr, st, tmp, true,
+    rc = run_rank_phase(L, plans, kmax, out + (size_t)g0 * kmax, nout + g0, nullptr, st, tmp, /*collective=*/true,
                         rows ? rows + (size_t)YRWI_ROW_BYTES * (size_t)g0 * kmax : nullptr);
     if (rc) return rc;
     tr += now_ns() - tr0;
@@ -1990,5 +1410,6 @@ extern "C" int yrwi_normalize_score(yrwi_ctx* ctx, const uint8_t* rows40, int64_
                          : (int64_t)std::chrono::duration_cast<std::chrono::milliseconds>(
                                std::chrono::system_clock::now().time_since_epoch()).count();
   P.k = 1;
-  return ctx->take(L, run_rank_phase(L, plans, 1, nullptr, nullptr, score_out, nullptr, nullptr, false));
+  return ctx->take(L, run_rank_phase(L, plans, 1, nullptr, nullptr, score_out, nullptr, nullptr, /*collective=*/false,
+                                     nullptr));
 }

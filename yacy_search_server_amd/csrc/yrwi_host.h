@@ -1,7 +1,7 @@
 // yrwi_host.h -- host-side structures shared by libyrwi's host translation
 // units (yrwi_host.cpp: contexts, planning, query execution; yrwi_join.cpp: the
-// join phase; yrwi_heap.cpp: BLOB heap loader).  Internal; the public ABI is
-// include/yrwi.h.
+// join phase; yrwi_rank.cpp: the rank phase; yrwi_heap.cpp: BLOB heap loader).
+// Internal; the public ABI is include/yrwi.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -635,7 +635,7 @@ struct Xfer {
   size_t bytes;
 };
 // ---- the two phases of a batch part: yrwi_join.cpp (join / exclusion) and
-// yrwi_host.cpp (planning, rank)
+// yrwi_rank.cpp (rank); yrwi_host.cpp plans and drives them
 struct Timing {
   // per join step: before k_join, between k_join and k_probe, after k_probe
   std::vector<std::array<hipEvent_t, 3>> kjoin;
@@ -675,6 +675,13 @@ int allsum_host(Lane* L, std::vector<int64_t>& v);
 // which after the first step is the sum over the shards of their joined rows
 // (one exchange per step that some query continues past; none on one context).
 int run_join_phase(Lane* ctx, std::vector<Plan>& plans, yrwi_stats* st, Timing* tm);
+// Normalise the plans' containers (P.cont), then either score + top-k -- hits to h_hits (row
+// stride kmax) and h_nout, their rows to h_rows (nullptr: not asked for) -- or, with
+// h_scores_all, the score of every element of the single plan (yrwi_normalize_score).
+// collective: every rank of a sharded context calls it with the same queries (the cross-shard
+// exchanges run); false: this context alone.
+int run_rank_phase(Lane* ctx, std::vector<Plan>& plans, int32_t kmax, yrwi_hit* h_hits, int32_t* h_nout,
+                   int64_t* h_scores_all, yrwi_stats* st, Timing* tm, bool collective, uint8_t* h_rows);
 
 // (re)build the url dictionary and every list's url ids if the index changed
 int ensure_url_ids(CtxBase* ctx);

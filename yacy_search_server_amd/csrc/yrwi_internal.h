@@ -469,63 +469,110 @@ struct JoinEvents {
 };
 int launch_join_step(const JoinStep& step, void* stream, const JoinEvents& ev);
 int launch_compact(const JoinStep& step, bool chain, void* stream);
-int launch_rank(const RankQ* d_q, const int64_t* d_chunk_base, int32_t nq, int64_t total_chunks,
-                ChunkSum* d_chunks, ShardSum* d_shard, NormState* d_norm, int32_t world, void* stream);
-// hp_any: some query of the launch counts host buckets (RankQ::ecnt): k_reduce
-// then takes HPART_MAXS ints of dynamic LDS for them (the others launch without)
-// reduce: some query of the launch has no normalisation pieces (RankQ::pieces) --
-// without one k_reduce is not launched
-// group_q / ngroups: (query, group) of every group of merged pieces (k_piece_merge)
-int launch_reduce(const RankQ* d_q, const int64_t* d_chunk_base, const int32_t* d_chunk_q, int32_t nq,
-                  int64_t total_chunks,
-                  ChunkSum* d_chunks, ShardSum* d_shard, void* stream, void* ev_mid = nullptr, bool hp_any = false,
-                  bool reduce = true, const int2* d_group_q = nullptr, int64_t ngroups = 0);
+
+// The device buffers of one rank pass (yrwi_rank.cpp): what the rank-phase launchers read.
+struct RankStep {
+  // query table: the pass's queries, every query's first chunk, every chunk's query
+  const RankQ* d_q = nullptr;
+  const int64_t* d_chunk_base = nullptr;
+  const int32_t* d_chunk_q = nullptr;
+  int32_t nq = 0;
+  int64_t chunks = 0;
+  // summaries: per chunk, per query of this shard, per query and shard (d_all: world
+  // ShardSums per query, rank-major; one context: d_shard itself), the combined state
+  ChunkSum* d_chunks = nullptr;
+  ShardSum* d_shard = nullptr;
+  ShardSum* d_all = nullptr;
+  int32_t world = 1;
+  NormState* d_norm = nullptr;
+  const int2* d_group_q = nullptr;  // (query, group) of every group of merged pieces (k_piece_merge)
+  int64_t ngroups = 0;
+  // reduce: some query has no normalisation pieces (RankQ::pieces) -- without one k_reduce is not
+  // launched.  hp_any: some query counts host buckets (RankQ::ecnt): k_reduce then takes
+  // HPART_MAXS ints of dynamic LDS for them (the others launch without)
+  bool reduce = false, hp_any = false;
+  // host partition (authority, RankQ::ecnt): the (query bucket, chunk) histogram of nhist entries
+  // and its scan, the scan's scratch, the scattered (host id, element) pairs, the buckets' (query, bucket)
+  int32_t* d_hist = nullptr;
+  int32_t* d_hoffs = nullptr;
+  int64_t nhist = 0;
+  void* d_tmp = nullptr;
+  size_t tmp_bytes = 0;
+  uint2* d_part = nullptr;
+  const int2* d_bq = nullptr;
+  int32_t nbuckets = 0;
+  // scoring: chunks in d_order ((chunk, query) int pairs); every chunk's candidate list (stride kc)
+  // and count; the chunks k_score_full redoes and their number; d_tq: per-query score threshold
+  // (zeroed), see PruneP in yrwi_kernels.hip; d_qtab: score_qtab_bytes() per query
+  const int32_t* d_order = nullptr;
+  Cand* d_cand = nullptr;
+  int32_t* d_cand_cnt = nullptr;
+  int32_t kc = 0;
+  int32_t* d_redo = nullptr;
+  int32_t* d_nredo = nullptr;
+  unsigned long long* d_tq = nullptr;
+  void* d_qtab = nullptr;
+  int64_t* d_scores = nullptr;  // launch_score_all: the score of every element of query 0
+  // final lists: every query's last candidate list and its count (after the top-k passes)
+  const Cand* const* d_final = nullptr;
+  const int32_t* const* d_final_cnt = nullptr;
+};
+// Hits of every query of a pass, `stride` entries apart, and how many each has: the pinned
+// destination, a device copy of it, a stack (stride kint) or the gathered stacks of all shards
+// (hits[world][nq][stride], cnt[world][nq]).
+struct HitList {
+  yrwi_hit* hits = nullptr;
+  int32_t* cnt = nullptr;
+  int32_t stride = 0;
+};
+// k_reduce (+ k_piece_merge), ev_mid (nullptr: not recorded), k_shard_fin
+int launch_reduce(const RankStep& step, void* stream, void* ev_mid);
 // authority host counts by partition (RankQ::ecnt): histogram per (query bucket, chunk) -> scan ->
 // scatter (host id, element) -> per-bucket LDS counts, every element's count, maxdomcount
-int launch_host_part(const RankQ* d_q, const int32_t* d_chunk_q, int64_t total_chunks, int32_t* d_hist,
-                     int32_t* d_hoffs, int64_t nhist, void* d_tmp, size_t tmp_bytes, uint2* d_part, const int2* d_bq,
-                     int32_t nbuckets, ShardSum* d_shard, void* stream);
+int launch_host_part(const RankStep& step, void* stream);
 size_t host_part_tmp_bytes(int64_t nhist);  // scan scratch for nhist + 1 histogram entries
 constexpr int HPART_MAXS = 1024, HPART_TARGET = 512;  // buckets per query at most; elements per bucket aimed at
-int launch_combine(const RankQ* d_q, int32_t nq, const ShardSum* d_shards, int32_t world,
-                   NormState* d_norm, void* stream);
-// chunks in d_order ((chunk, query) int pairs); d_tq: per-query score threshold (zeroed), see PruneP in yrwi_kernels.hip
-int launch_score(const RankQ* d_q, const int32_t* d_chunk_q, const int32_t* d_order, int32_t nq, int64_t total_chunks,
-                 int64_t seed_chunks, const NormState* d_norm, Cand* d_cand, int32_t* d_cand_cnt, int32_t kc,
-                 int32_t* d_redo, int32_t* d_nredo, unsigned long long* d_tq, void* d_qtab, void* stream,
-                 void* ev_mid = nullptr);
-size_t score_qtab_bytes();  // per query: d_qtab of launch_score (its pruning parameters and term tables)
+int launch_combine(const RankStep& step, void* stream);
+// k_qtabs, k_score, ev_mid (nullptr: not recorded), k_score_full
+int launch_score(const RankStep& step, void* stream, void* ev_mid);
+size_t score_qtab_bytes();  // per query: RankStep::d_qtab (its pruning parameters and term tables)
 // candidates one k_topq group may hold (lists per group = min(64, capacity / list stride))
 int topq_capacity(int32_t keff);
-// top-k of candidate-list groups: group g = lists [gbase[g], gbase[g]+gn[g]) of d_in (stride
+// One top-k pass over candidate-list groups: group g = lists [gbase[g], gbase[g]+gn[g]) of d_in (stride
 // in_stride, counts d_in_cnt), k = gk[g]; output list g at d_out + g*keff, count d_out_cnt[g]
-int launch_topq(const int64_t* d_gbase, const int32_t* d_gn, const int32_t* d_gk, int64_t ngroups, const Cand* d_in,
-                const int32_t* d_in_cnt, int32_t in_stride, int32_t keff, Cand* d_out, int32_t* d_out_cnt, void* stream);
+struct TopqPass {
+  const int64_t* d_gbase = nullptr;
+  const int32_t* d_gn = nullptr;
+  const int32_t* d_gk = nullptr;
+  int64_t ngroups = 0;
+  const Cand* d_in = nullptr;
+  const int32_t* d_in_cnt = nullptr;
+  int32_t in_stride = 0, keff = 0;
+  Cand* d_out = nullptr;
+  int32_t* d_out_cnt = nullptr;
+};
+int launch_topq(const TopqPass& pass, void* stream);
 // mode 0: first kout hits of the non-doubledom queries; 1: every query's stack
 // (k hits); 2: only the doubledom queries' stacks
-int launch_emit(const RankQ* d_q, int32_t nq, const Cand* const* d_final, const int32_t* const* d_final_cnt,
-                int32_t kmax, yrwi_hit* d_hits, int32_t* d_nout, int mode, void* stream);
+int launch_emit(const RankStep& step, const HitList& dst, int mode, void* stream);
 // out[i] = sum or max over r of all[r * n + i] (loopback allreduce)
 int launch_reduce_i32(const int32_t* all, int world, int64_t n, int32_t* out, int max_op, void* stream);
-// results from stacks (stride kint): pullOneRWI(skipDoubleDom) order for doubledom
-// queries, the first kout entries for the others (only_dd: doubledom queries only)
-int launch_pull(const RankQ* d_q, int32_t nq, const yrwi_hit* d_stack, const int32_t* d_scnt, int32_t kint,
-                int only_dd, int32_t kmax, yrwi_hit* d_hits, int32_t* d_nout, void* stream);
-// the 40-byte row of every final hit (row of hit i of query q at d_rows + (q * kmax + i) * 40, 8-byte
-// aligned).  HR_CAND queries: the hits k_emit wrote from d_final.  HR_HITS queries: the hits are
-// d_src_hits[q * kmax + i], i < d_src_cnt[q] (k_pull's output in device memory), and are forwarded
-// to d_hits / d_nout as well
-int launch_hit_rows(const RankQ* d_q, const HitRowQ* d_hq, int32_t nq, const Cand* const* d_final,
-                    const int32_t* const* d_final_cnt, const yrwi_hit* d_src_hits, const int32_t* d_src_cnt,
-                    int32_t kmax, yrwi_hit* d_hits, int32_t* d_nout, uint8_t* d_rows, void* stream);
-// merge of gathered shard stacks allh[world][nq][kint] into stack[nq][kint] (TreeSet in shard order)
-int launch_gmerge(const RankQ* d_q, const yrwi_hit* d_allh, const int32_t* d_alln, int world, int32_t nq, int32_t kint,
-                  uint32_t* d_slot, uint8_t* d_dup, yrwi_hit* d_stack, int32_t* d_scnt, void* stream);
+// results from stacks: pullOneRWI(skipDoubleDom) order for doubledom queries, the
+// first kout entries for the others (only_dd: doubledom queries only)
+int launch_pull(const RankStep& step, const HitList& stack, int only_dd, const HitList& dst, void* stream);
+// the 40-byte row of every final hit (row of hit i of query q at d_rows + (q * dst.stride + i) * 40,
+// 8-byte aligned).  HR_CAND queries: the hits k_emit wrote from d_final.  HR_HITS queries: the hits are
+// src.hits[q * dst.stride + i], i < src.cnt[q] (k_pull's output in device memory), and are forwarded
+// to dst as well
+int launch_hit_rows(const RankStep& step, const HitRowQ* d_hq, const HitList& src, const HitList& dst,
+                    uint8_t* d_rows, void* stream);
+// merge of gathered shard stacks all.hits[world][nq][stride] into stack.hits[nq][stride] (TreeSet in shard order)
+int launch_gmerge(const RankStep& step, const HitList& all, uint32_t* d_slot, uint8_t* d_dup, const HitList& stack,
+                  void* stream);
 // cardinal(URIMetadataNode) of n node records
 int launch_score_nodes(const yrwi_node* d_nodes, int64_t n, const yrwi_profile* d_prof, const char* lang8,
                        int32_t maxdomcount, int64_t* d_scores, void* stream);
-int launch_score_all(const RankQ* d_q, const int32_t* d_chunk_q, int32_t nq, int64_t total_chunks,
-                     const NormState* d_norm, int64_t* d_scores, void* stream);
+int launch_score_all(const RankStep& step, void* stream);
 
 // ------------------------------------------------ search events
 // A SearchEvent that receives containers one after another (the local RWI

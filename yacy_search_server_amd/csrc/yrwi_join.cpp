@@ -1,7 +1,7 @@
 // yrwi_join.cpp -- the join / exclusion phase of a batch part (run_join_phase):
 // every fold step's dispatch (J3, yrwi_host.cpp), its jobs' layout, launches and
-// byte accounting, chained folds and the exclusion step.  Planning, the rank
-// phase and the C entry points are in yrwi_host.cpp.
+// byte accounting, chained folds and the exclusion step.  Planning and the C
+// entry points are in yrwi_host.cpp, the rank phase in yrwi_rank.cpp.
 
 #include "yrwi_host.h"
 

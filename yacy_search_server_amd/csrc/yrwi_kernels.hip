@@ -4733,31 +4733,28 @@ extern "C" int yrwi_chain_prof(unsigned long long* out) {  // profiling build on
 }
 #endif
 
-int launch_reduce(const RankQ* d_q, const int64_t* d_chunk_base, const int32_t* d_chunk_q, int32_t nq,
-                  int64_t total_chunks,
-                  ChunkSum* d_chunks, ShardSum* d_shard, void* st, void* ev_mid, bool hp_any, bool reduce,
-                  const int2* d_group_q, int64_t ngroups) {
+int launch_reduce(const RankStep& s, void* st, void* ev_mid) {
   // (static, the 4 KB cost every batch's k_reduce LDS whether it counted hosts or not)
-  if (total_chunks > 0 && reduce)
-    hipLaunchKernelGGL(k_reduce, dim3((unsigned)total_chunks), dim3(CHUNK_THREADS),
-                       hp_any ? HPART_MAXS * sizeof(int32_t) : 0, S(st), d_q, d_chunk_q, d_chunks, d_shard);
-  if (ngroups > 0) hipLaunchKernelGGL(k_piece_merge, dim3((unsigned)ngroups), dim3(64), 0, S(st), d_q, d_group_q);
+  if (s.chunks > 0 && s.reduce)
+    hipLaunchKernelGGL(k_reduce, dim3((unsigned)s.chunks), dim3(CHUNK_THREADS),
+                       s.hp_any ? HPART_MAXS * sizeof(int32_t) : 0, S(st), s.d_q, s.d_chunk_q, s.d_chunks, s.d_shard);
+  if (s.ngroups > 0)
+    hipLaunchKernelGGL(k_piece_merge, dim3((unsigned)s.ngroups), dim3(64), 0, S(st), s.d_q, s.d_group_q);
   if (ev_mid) hipEventRecord(reinterpret_cast<hipEvent_t>(ev_mid), S(st));  // k_reduce alone (statistics)
-  hipLaunchKernelGGL(k_shard_fin, dim3((unsigned)nq), dim3(64), 0, S(st), d_q, d_chunk_base, d_chunks, d_shard);
+  hipLaunchKernelGGL(k_shard_fin, dim3((unsigned)s.nq), dim3(64), 0, S(st), s.d_q, s.d_chunk_base, s.d_chunks, s.d_shard);
   return rc(hipGetLastError());
 }
 
-int launch_host_part(const RankQ* d_q, const int32_t* d_chunk_q, int64_t total_chunks, int32_t* d_hist,
-                     int32_t* d_hoffs, int64_t nhist, void* d_tmp, size_t tmp_bytes, uint2* d_part, const int2* d_bq,
-                     int32_t nbuckets, ShardSum* d_shard, void* st) {
-  if (total_chunks <= 0 || nbuckets <= 0) return 0;
+int launch_host_part(const RankStep& s, void* st) {
+  if (s.chunks <= 0 || s.nbuckets <= 0) return 0;
   // (the histogram: k_reduce, launched before on this stream)
-  size_t t = tmp_bytes;
-  if (hipcub::DeviceScan::ExclusiveSum(d_tmp, t, d_hist, d_hoffs, (int)(nhist + 1), S(st)) != hipSuccess) return -1;
-  hipLaunchKernelGGL(k_hpart_scatter, dim3((unsigned)total_chunks), dim3(CHUNK_THREADS), 0, S(st), d_q, d_chunk_q,
-                     (const int32_t*)d_hoffs, d_part);
-  hipLaunchKernelGGL(k_hbucket, dim3((unsigned)nbuckets), dim3(CHUNK_THREADS), 0, S(st), d_q, d_bq,
-                     (const int32_t*)d_hoffs, (const uint2*)d_part, d_shard);
+  size_t t = s.tmp_bytes;
+  if (hipcub::DeviceScan::ExclusiveSum(s.d_tmp, t, s.d_hist, s.d_hoffs, (int)(s.nhist + 1), S(st)) != hipSuccess)
+    return -1;
+  hipLaunchKernelGGL(k_hpart_scatter, dim3((unsigned)s.chunks), dim3(CHUNK_THREADS), 0, S(st), s.d_q, s.d_chunk_q,
+                     (const int32_t*)s.d_hoffs, s.d_part);
+  hipLaunchKernelGGL(k_hbucket, dim3((unsigned)s.nbuckets), dim3(CHUNK_THREADS), 0, S(st), s.d_q, s.d_bq,
+                     (const int32_t*)s.d_hoffs, (const uint2*)s.d_part, s.d_shard);
   return rc(hipGetLastError());
 }
 
@@ -4767,34 +4764,30 @@ size_t host_part_tmp_bytes(int64_t nhist) {
   return t;
 }
 
-int launch_combine(const RankQ* d_q, int32_t nq, const ShardSum* d_shards, int32_t world, NormState* d_norm,
-                   void* st) {
-  hipLaunchKernelGGL(k_combine, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, S(st), d_q, nq, d_shards, world, d_norm);
+int launch_combine(const RankStep& s, void* st) {
+  hipLaunchKernelGGL(k_combine, dim3((unsigned)((s.nq + 63) / 64)), dim3(64), 0, S(st), s.d_q, s.nq, s.d_all, s.world,
+                     s.d_norm);
   return rc(hipGetLastError());
 }
 
-int launch_score(const RankQ* d_q, const int32_t* d_chunk_q, const int32_t* d_order, int32_t nq, int64_t total_chunks,
-                 int64_t seed_chunks, const NormState* d_norm, Cand* d_cand, int32_t* d_cand_cnt, int32_t kc,
-                 int32_t* d_redo, int32_t* d_nredo, unsigned long long* d_tq, void* d_qtab, void* st,
-                 void* ev_mid) {
+int launch_score(const RankStep& s, void* st, void* ev_mid) {
+  const int64_t total_chunks = s.chunks;
   if (total_chunks <= 0) {  // (the statistics' event is recorded all the same: its elapsed time is read)
     if (ev_mid) hipEventRecord(reinterpret_cast<hipEvent_t>(ev_mid), S(st));
     return 0;
   }
-  QTab* qt = reinterpret_cast<QTab*>(d_qtab);
-  hipLaunchKernelGGL(k_qtabs, dim3((unsigned)nq), dim3(256), 0, S(st), d_q, d_norm, qt);
-  // seed_chunks (0 < seed < total): the first chunks of `order` run as a launch of
-  // their own, so every later chunk starts with its query's threshold set
-  const int64_t s0 = (seed_chunks > 0 && seed_chunks < total_chunks) ? seed_chunks : total_chunks;
-  hipLaunchKernelGGL(k_score, dim3((unsigned)s0), dim3(CHUNK_THREADS), 0, S(st), d_q, d_chunk_q, d_order, d_norm,
-                     d_cand, d_cand_cnt, kc, d_redo, d_nredo, d_tq, (const QTab*)qt);
-  if (s0 < total_chunks)
-    hipLaunchKernelGGL(k_score, dim3((unsigned)(total_chunks - s0)), dim3(CHUNK_THREADS), 0, S(st), d_q, d_chunk_q,
-                       d_order + 2 * s0, d_norm, d_cand, d_cand_cnt, kc, d_redo, d_nredo, d_tq, (const QTab*)qt);
-  if (ev_mid) hipEventRecord(reinterpret_cast<hipEvent_t>(ev_mid), S(st));  // the k_score launches alone (statistics)
+  QTab* qt = reinterpret_cast<QTab*>(s.d_qtab);
+  hipLaunchKernelGGL(k_qtabs, dim3((unsigned)s.nq), dim3(256), 0, S(st), s.d_q, (const NormState*)s.d_norm, qt);
+  // one launch for all chunks (a separate launch of every query's first chunk, so
+  // that all later chunks start with a threshold, measured 39 + 86 us against
+  // 99 us for one launch: the seed launch is one round of full-length blocks)
+  hipLaunchKernelGGL(k_score, dim3((unsigned)total_chunks), dim3(CHUNK_THREADS), 0, S(st), s.d_q, s.d_chunk_q,
+                     s.d_order, (const NormState*)s.d_norm, s.d_cand, s.d_cand_cnt, s.kc, s.d_redo, s.d_nredo, s.d_tq,
+                     (const QTab*)qt);
+  if (ev_mid) hipEventRecord(reinterpret_cast<hipEvent_t>(ev_mid), S(st));  // the k_score launch alone (statistics)
   const unsigned g = (unsigned)std::min<int64_t>(total_chunks, 512);
-  hipLaunchKernelGGL(k_score_full, dim3(g), dim3(CHUNK_THREADS), 0, S(st), d_q, d_chunk_q, d_norm, d_cand,
-                     d_cand_cnt, kc, d_redo, d_nredo);
+  hipLaunchKernelGGL(k_score_full, dim3(g), dim3(CHUNK_THREADS), 0, S(st), s.d_q, s.d_chunk_q,
+                     (const NormState*)s.d_norm, s.d_cand, s.d_cand_cnt, s.kc, s.d_redo, s.d_nredo);
 #ifdef YRWI_PHASE_CLOCK
   {
     static std::vector<unsigned long long> h;
@@ -4840,9 +4833,8 @@ int launch_score(const RankQ* d_q, const int32_t* d_chunk_q, const int32_t* d_or
 int topq_capacity(int32_t keff) { return keff <= 2048 ? 4096 : 8192; }
 size_t score_qtab_bytes() { return sizeof(QTab); }
 
-int launch_topq(const int64_t* d_gbase, const int32_t* d_gn, const int32_t* d_gk, int64_t ngroups, const Cand* d_in,
-                const int32_t* d_in_cnt, int32_t in_stride, int32_t keff, Cand* d_out, int32_t* d_out_cnt, void* st) {
-  if (ngroups <= 0) return 0;
+int launch_topq(const TopqPass& p, void* st) {
+  if (p.ngroups <= 0) return 0;
   static bool attr = false;
   if (!attr) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_topq<4096>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -4852,12 +4844,12 @@ int launch_topq(const int64_t* d_gbase, const int32_t* d_gn, const int32_t* d_gk
       return YRWI_E_HIP;
     attr = true;
   }
-  if (topq_capacity(keff) == 4096)
-    hipLaunchKernelGGL(k_topq<4096>, dim3((unsigned)ngroups), dim3(TOPQ_THREADS), 2 * 4096 * sizeof(uint64_t), S(st),
-                       d_gbase, d_gn, d_gk, d_in, d_in_cnt, in_stride, keff, d_out, d_out_cnt);
+  if (topq_capacity(p.keff) == 4096)
+    hipLaunchKernelGGL(k_topq<4096>, dim3((unsigned)p.ngroups), dim3(TOPQ_THREADS), 2 * 4096 * sizeof(uint64_t), S(st),
+                       p.d_gbase, p.d_gn, p.d_gk, p.d_in, p.d_in_cnt, p.in_stride, p.keff, p.d_out, p.d_out_cnt);
   else
-    hipLaunchKernelGGL(k_topq<8192>, dim3((unsigned)ngroups), dim3(TOPQ_THREADS), 2 * 8192 * sizeof(uint64_t), S(st),
-                       d_gbase, d_gn, d_gk, d_in, d_in_cnt, in_stride, keff, d_out, d_out_cnt);
+    hipLaunchKernelGGL(k_topq<8192>, dim3((unsigned)p.ngroups), dim3(TOPQ_THREADS), 2 * 8192 * sizeof(uint64_t), S(st),
+                       p.d_gbase, p.d_gn, p.d_gk, p.d_in, p.d_in_cnt, p.in_stride, p.keff, p.d_out, p.d_out_cnt);
   return rc(hipGetLastError());
 }
 
@@ -4928,46 +4920,44 @@ int launch_reduce_i32(const int32_t* all, int world, int64_t n, int32_t* out, in
   return rc(hipGetLastError());
 }
 
-int launch_pull(const RankQ* d_q, int32_t nq, const yrwi_hit* d_stack, const int32_t* d_scnt, int32_t kint,
-                int only_dd, int32_t kmax, yrwi_hit* d_hits, int32_t* d_nout, void* st) {
-  if (nq <= 0) return 0;
-  hipLaunchKernelGGL(k_pull, dim3((unsigned)nq), dim3(64), 0, S(st), d_q, d_stack, d_scnt, kint, only_dd, kmax, d_hits,
-                     d_nout);
+int launch_pull(const RankStep& s, const HitList& stack, int only_dd, const HitList& dst, void* st) {
+  if (s.nq <= 0) return 0;
+  hipLaunchKernelGGL(k_pull, dim3((unsigned)s.nq), dim3(64), 0, S(st), s.d_q, (const yrwi_hit*)stack.hits,
+                     (const int32_t*)stack.cnt, stack.stride, only_dd, dst.stride, dst.hits, dst.cnt);
   return rc(hipGetLastError());
 }
 
-int launch_gmerge(const RankQ* d_q, const yrwi_hit* d_allh, const int32_t* d_alln, int world, int32_t nq, int32_t kint,
-                  uint32_t* d_slot, uint8_t* d_dup, yrwi_hit* d_stack, int32_t* d_scnt, void* st) {
-  if (nq <= 0) return 0;
+int launch_gmerge(const RankStep& s, const HitList& all, uint32_t* d_slot, uint8_t* d_dup, const HitList& stack,
+                  void* st) {
+  if (s.nq <= 0) return 0;
+  const int world = s.world;
+  const int32_t nq = s.nq, kint = all.stride;
   const int64_t n = (int64_t)nq * world * kint;
-  hipLaunchKernelGGL(k_gmerge_rank, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(st), d_allh, d_alln, world, nq,
-                     kint, d_slot, d_dup);
-  hipLaunchKernelGGL(k_gmerge_out, dim3((unsigned)nq), dim3(256), 0, S(st), d_q, d_allh, d_alln, world, nq, kint, d_slot,
-                     d_dup, d_stack, d_scnt);
+  hipLaunchKernelGGL(k_gmerge_rank, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(st), (const yrwi_hit*)all.hits,
+                     (const int32_t*)all.cnt, world, nq, kint, d_slot, d_dup);
+  hipLaunchKernelGGL(k_gmerge_out, dim3((unsigned)nq), dim3(256), 0, S(st), s.d_q, (const yrwi_hit*)all.hits,
+                     (const int32_t*)all.cnt, world, nq, kint, d_slot, d_dup, stack.hits, stack.cnt);
   return rc(hipGetLastError());
 }
 
-int launch_emit(const RankQ* d_q, int32_t nq, const Cand* const* d_final, const int32_t* const* d_final_cnt,
-                int32_t kmax, yrwi_hit* d_hits, int32_t* d_nout, int mode, void* st) {
-  hipLaunchKernelGGL(k_emit, dim3((unsigned)nq), dim3(256), 0, S(st), d_q, nq, d_final, d_final_cnt, kmax,
-                     d_hits, d_nout, mode);
+int launch_emit(const RankStep& s, const HitList& dst, int mode, void* st) {
+  hipLaunchKernelGGL(k_emit, dim3((unsigned)s.nq), dim3(256), 0, S(st), s.d_q, s.nq, s.d_final, s.d_final_cnt,
+                     dst.stride, dst.hits, dst.cnt, mode);
   return rc(hipGetLastError());
 }
 
-int launch_hit_rows(const RankQ* d_q, const HitRowQ* d_hq, int32_t nq, const Cand* const* d_final,
-                    const int32_t* const* d_final_cnt, const yrwi_hit* d_src_hits, const int32_t* d_src_cnt,
-                    int32_t kmax, yrwi_hit* d_hits, int32_t* d_nout, uint8_t* d_rows, void* st) {
-  if (nq <= 0) return 0;
-  hipLaunchKernelGGL(k_hit_rows, dim3((unsigned)nq), dim3(256), 0, S(st), d_q, d_hq, d_final, d_final_cnt, d_src_hits,
-                     d_src_cnt, kmax, d_hits, d_nout, d_rows);
+int launch_hit_rows(const RankStep& s, const HitRowQ* d_hq, const HitList& src, const HitList& dst, uint8_t* d_rows,
+                    void* st) {
+  if (s.nq <= 0) return 0;
+  hipLaunchKernelGGL(k_hit_rows, dim3((unsigned)s.nq), dim3(256), 0, S(st), s.d_q, d_hq, s.d_final, s.d_final_cnt,
+                     (const yrwi_hit*)src.hits, (const int32_t*)src.cnt, dst.stride, dst.hits, dst.cnt, d_rows);
   return rc(hipGetLastError());
 }
 
-int launch_score_all(const RankQ* d_q, const int32_t* d_chunk_q, int32_t nq, int64_t total_chunks,
-                     const NormState* d_norm, int64_t* d_scores, void* st) {
-  if (total_chunks <= 0) return 0;
-  hipLaunchKernelGGL(k_score_all, dim3((unsigned)total_chunks), dim3(256), 0, S(st), d_q, d_chunk_q, d_norm,
-                     d_scores);
+int launch_score_all(const RankStep& s, void* st) {
+  if (s.chunks <= 0) return 0;
+  hipLaunchKernelGGL(k_score_all, dim3((unsigned)s.chunks), dim3(256), 0, S(st), s.d_q, s.d_chunk_q,
+                     (const NormState*)s.d_norm, s.d_scores);
   return rc(hipGetLastError());
 }
 
