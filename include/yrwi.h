@@ -396,6 +396,69 @@ typedef struct yrwi_dump_stats {
 int yrwi_dump_heap(yrwi_ctx* ctx, const char* path, const uint8_t* terms12, int32_t nterms,
                    int64_t now_ms, yrwi_dump_stats* st);
 
+/* ---- DHT send path (yrwi_dht.hip): select, split and remove containers on the device ----
+ * Dispatcher.selectContainersEnqueueToBuffer: selectContainers walks the term order from a start
+ * hash and takes whole containers up to a container and a reference count, IndexCell.remove(termHash)
+ * takes them out of the index, and splitContainers / splitContainer divide each one by
+ * Distribution.verticalDHTPosition(urlhash) into 2^e partitions, which Transmission sends to the
+ * partitions' target peers.
+ * Three things here are UNVERIFIED against the reference source (written from memory):
+ *   - Word.isPrivate(termHash): the hash starts with the two bytes YRWI_DHT_PRIVATE0/1 ("_C");
+ *   - the first container is taken even when its term is >= limit;
+ *   - after a wrap the term is still compared with a plain `< limit`. */
+#define YRWI_DHT_ROT 1           /* referenceContainerIterator(hash, rot = true): wrap to the smallest term */
+#define YRWI_DHT_REMOVE 2        /* remove the selected lists from the index once their rows have landed */
+#define YRWI_DHT_SKIP_PRIVATE 4  /* Word.isPrivate(termHash) containers are passed over, uncounted */
+#define YRWI_DHT_COUNT_ONLY 8    /* dry run: fill st only, change nothing */
+#define YRWI_DHT_MAX_EXPONENT 8
+#define YRWI_DHT_PRIVATE0 '_'    /* UNVERIFIED, see above */
+#define YRWI_DHT_PRIVATE1 'C'
+typedef struct yrwi_dht_stats {
+  int64_t terms, postings;      /* containers selected, rows in them (also the capacities a retry needs) */
+  int64_t skipped_private;
+  int64_t removed;              /* postings removed from the index */
+  int32_t wrapped;              /* the walk passed the end of the term order and went on at the smallest term */
+  int64_t windows;
+  int32_t launches, syncs;      /* functions of postings / window size and 2^e, never of the number of terms */
+  int64_t t_pack_ns, t_total_ns;
+} yrwi_dht_stats;
+/* Selection: the context's non-empty lists in Base64Order of their term hashes, from the first term
+ * >= start; with YRWI_DHT_ROT the walk goes on at the smallest term after the largest and stops after
+ * one full cycle (no term twice), without it at the end.  The next list is taken while
+ * selected < max_containers, refs < max_refs, and nothing is selected yet or its term is < limit
+ * (a plain key comparison, also after a wrap): so the first container is taken whatever `limit` is,
+ * the last one may push refs past max_refs, and max_containers <= 0 or max_refs <= 0 select nothing
+ * (rc 0).  With YRWI_DHT_SKIP_PRIVATE a private term is passed over: it does not count and does not
+ * end the walk.  There is no time limit.
+ * Split: P = 2^partition_exponent (0 .. YRWI_DHT_MAX_EXPONENT); a posting's partition is the top e
+ * bits of its 72-bit url key -- for e <= 6 the shard rule of yrwi_open_shard.
+ * Output, T the number of selected terms: terms12_out receives the T term hashes in selection order;
+ * part_off (room for P * cap_terms + 1 entries) receives P * T + 1 non-decreasing row offsets in
+ * partition-major order: the rows of term j in partition p are rows40_out + 40 * part_off[p * T + j]
+ * up to part_off[p * T + j + 1], in url-hash order and byte-identical to what yrwi_get_list returns;
+ * part_off[P * T] == st->postings.  rows40_out may be yrwi_host_alloc memory: when it is and is
+ * 8-byte aligned the rows land in it directly, else through a pinned window.
+ * The boundaries of every (list, partition) are searched in one launch and summed in one device
+ * scan; the rows are packed in windows of YRWI_DHT_WINDOW_ROWS rows (environment, read per call;
+ * default 1,048,576, at least 16, at most 2^24), two device and two pinned windows shared with
+ * yrwi_dump_heap.  Extra device memory is the windows, the job table and the P * T cells.
+ * Every failure leaves the index unchanged and writes no output buffer, st excepted where said:
+ * cap_terms < T or cap_rows < postings: YRWI_E_ARG, st->terms and st->postings filled for a retry;
+ * an ill-formed start or limit: YRWI_E_HASH; e out of range or unknown flag bits: YRWI_E_ARG;
+ * YRWI_E_NOMEM, YRWI_E_HIP (rows of windows already landed may have been written).
+ * With YRWI_DHT_REMOVE the lists are erased only after the last row has landed, as
+ * yrwi_remove_hosts erases a list it empties; their memory is reclaimed by the next repack.  The
+ * caller puts back what it could not send with yrwi_add_postings(YRWI_ADD_KEEP).
+ * YRWI_DHT_COUNT_ONLY fills st with what the same call would select and touches neither the buffers
+ * (which may be NULL) nor the index.  The call waits for the batches in flight, as yrwi_put_list
+ * does.  A sharded context selects from the lists it holds, its url range of each term: no
+ * collective is involved, and the cells of partitions outside its range come out empty.
+ * st may be NULL. */
+int yrwi_dht_select(yrwi_ctx* ctx, const uint8_t start[12], const uint8_t limit[12],
+                    int32_t max_containers, int64_t max_refs, int32_t partition_exponent, int32_t flags,
+                    uint8_t* terms12_out, int32_t cap_terms, int64_t* part_off,
+                    uint8_t* rows40_out, int64_t cap_rows, yrwi_dht_stats* st);
+
 /* ---- query hot path ---- */
 /* TermSearch + joinExcludeContainers + normalizeWith + cardinal + rwiStack top-k
  * (SearchEvent.RWIProcess.run :612-631 -> addRWIs :673-836), canonical

@@ -335,6 +335,73 @@ JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_dumpHeap(JNIEnv* 
   return res;
 }
 
+/* The DHT send path (Dispatcher.selectContainersEnqueueToBuffer): yrwi_dht_select, sized by a dry
+ * run (YRWI_DHT_COUNT_ONLY).  start, limit: 12-byte term hashes; flags: YRWI_DHT_*.  Returns
+ * Object[3] {byte[] terms (T * 12), long[] partOff (2^e * T + 1), byte[] rows (postings * 40)} and
+ * fills stats (long[10] or null) with {terms, postings, skipped_private, removed, wrapped, windows,
+ * launches, syncs, t_pack_ns, t_total_ns}; NULL when the call failed. */
+JNIEXPORT jobjectArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_dhtSelect(JNIEnv* env, jclass c, jlong ctx,
+                                                                          jbyteArray start, jbyteArray limit,
+                                                                          jint maxContainers, jlong maxRefs,
+                                                                          jint exponent, jint flags,
+                                                                          jlongArray stats) {
+  uint8_t* s = copy_in(env, start, 12);
+  if (!s) return NULL;
+  uint8_t* l = copy_in(env, limit, 12);
+  if (!l) {
+    free(s);
+    return NULL;
+  }
+  yrwi_ctx* x = (yrwi_ctx*)(intptr_t)ctx;
+  yrwi_dht_stats st;
+  memset(&st, 0, sizeof(st));
+  jobjectArray res = NULL;
+  uint8_t *terms = NULL, *rows = NULL;
+  int64_t* off = NULL;
+  int rc = yrwi_dht_select(x, s, l, maxContainers, maxRefs, exponent, (flags | YRWI_DHT_COUNT_ONLY) & ~YRWI_DHT_REMOVE,
+                           NULL, 0, NULL, NULL, 0, &st);
+  const int64_t T = st.terms, n = st.postings;
+  const int64_t noff = rc == 0 ? (((int64_t)1 << exponent) * T + 1) : 0;
+  /* a Java array holds at most 2^31 - 1 elements */
+  if (rc == 0 && (n * 40 > 2147483647LL || noff > 2147483647LL || T * 12 > 2147483647LL)) rc = YRWI_E_LIMIT;
+  if (rc == 0 && !(flags & YRWI_DHT_COUNT_ONLY)) {
+    terms = (uint8_t*)malloc((size_t)(T > 0 ? T * 12 : 1));
+    off = (int64_t*)malloc((size_t)noff * sizeof(int64_t));
+    rows = (uint8_t*)malloc((size_t)(n > 0 ? n * 40 : 1));
+    if (!terms || !off || !rows) rc = YRWI_E_NOMEM;
+    if (rc == 0) rc = yrwi_dht_select(x, s, l, maxContainers, maxRefs, exponent, flags, terms, (int32_t)T, off, rows, n, &st);
+    if (rc == 0) {
+      jclass oc = (*env)->FindClass(env, "java/lang/Object");
+      jbyteArray jt = (*env)->NewByteArray(env, (jsize)(T * 12));
+      jlongArray jo = (*env)->NewLongArray(env, (jsize)noff);
+      jbyteArray jr = (*env)->NewByteArray(env, (jsize)(n * 40));
+      if (oc && jt && jo && jr) res = (*env)->NewObjectArray(env, 3, oc, NULL);
+      if (res) {
+        (*env)->SetByteArrayRegion(env, jt, 0, (jsize)(T * 12), (const jbyte*)terms);
+        (*env)->SetLongArrayRegion(env, jo, 0, (jsize)noff, (const jlong*)off);
+        (*env)->SetByteArrayRegion(env, jr, 0, (jsize)(n * 40), (const jbyte*)rows);
+        (*env)->SetObjectArrayElement(env, res, 0, jt);
+        (*env)->SetObjectArrayElement(env, res, 1, jo);
+        (*env)->SetObjectArrayElement(env, res, 2, jr);
+      }
+    }
+  } else if (rc == 0) { /* the dry run alone: empty arrays */
+    jclass oc = (*env)->FindClass(env, "java/lang/Object");
+    if (oc) res = (*env)->NewObjectArray(env, 3, oc, NULL);
+  }
+  if (rc == 0 && stats && (*env)->GetArrayLength(env, stats) >= 10) {
+    const jlong v[10] = {st.terms,   st.postings, st.skipped_private, st.removed,   st.wrapped,
+                         st.windows, st.launches, st.syncs,           st.t_pack_ns, st.t_total_ns};
+    (*env)->SetLongArrayRegion(env, stats, 0, 10, v);
+  }
+  free(terms);
+  free(off);
+  free(rows);
+  free(s);
+  free(l);
+  return res;
+}
+
 /* SearchEvent.addRWIs constraints + pullOneRWI(skipDoubleDom): query with a yrwi_filter.
  * constraint: 4 Bitfield bytes or null; site / altSite: 6-byte host hashes or null;
  * siteExcludes: n*6 bytes; urlHashes: n*12 bytes; flagCount: int[32] out or null. */

@@ -15,6 +15,7 @@
 //   search/query/SearchEvent.java:612-631,651  -> GpuRWI.eventAddLocal(...) (the local container into a GpuRWIStack event, device to device)
 //   kelondro/rwi/IndexCell.java:353-386        -> GpuRWI.loadHeaps(...) (BLOB heaps into HBM)
 //   kelondro/rwi/IndexCell.java:131-166        -> GpuRWI.dumpHeap(...) (the FlushThread dump: HBM into a BLOB heap)
+//   peers/Dispatcher.selectContainersEnqueueToBuffer -> GpuRWI.dhtSelect(...) (select, remove and split containers for the DHT)
 //
 // Java level: 1.8, YaCy's own (build.properties javacSource/javacTarget, pom.xml
 // maven.compiler.source/target).  No API newer than Java 8 is used here or in the
@@ -233,6 +234,59 @@ public final class GpuRWI implements AutoCloseable {
         final long[] st = dumpHeap(this.ctx, path, nterms == 0 ? new byte[0] : flatten(terms), nterms, nowMs);
         if (st == null) throw new IllegalStateException("yrwi_dump_heap failed");
         return st;
+    }
+
+    /** yrwi_dht_select flags. */
+    public static final int DHT_ROT = 1, DHT_REMOVE = 2, DHT_SKIP_PRIVATE = 4, DHT_COUNT_ONLY = 8;
+
+    /** What dhtSelect returns: the containers Dispatcher.selectContainers takes, split as
+     *  Dispatcher.splitContainers splits them.  Cell (p, j) -- the postings of terms[j] that go to
+     *  vertical partition p -- is rows[40 * partOff[p * T + j] .. 40 * partOff[p * T + j + 1]), T the
+     *  number of terms, in url-hash order. */
+    public static final class DhtSelection {
+        public final byte[][] terms;   // T term hashes in selection order
+        public final long[] partOff;   // 2^e * T + 1 row offsets, partition-major
+        public final byte[] rows;      // every selected posting, 40 bytes each, cell after cell
+        public final int partitions;   // 2^e
+        /** {terms, postings, skippedPrivate, removed, wrapped, windows, launches, syncs, packNanos, totalNanos} */
+        public final long[] stats;
+
+        DhtSelection(final byte[][] terms, final long[] partOff, final byte[] rows, final int partitions,
+                     final long[] stats) {
+            this.terms = terms;
+            this.partOff = partOff;
+            this.rows = rows;
+            this.partitions = partitions;
+            this.stats = stats;
+        }
+
+        /** the postings of terms[j] for partition p, 40 bytes each */
+        public byte[] cell(final int p, final int j) {
+            final int c = p * this.terms.length + j;
+            return java.util.Arrays.copyOfRange(this.rows, (int) (40 * this.partOff[c]), (int) (40 * this.partOff[c + 1]));
+        }
+    }
+
+    /** The DHT send path, Dispatcher.selectContainersEnqueueToBuffer on the device (yrwi_dht_select):
+     *  selectContainers from the first term >= start -- whole containers in term order while fewer
+     *  than maxContainers are taken, fewer than maxRefs references, and the term is below limit (the
+     *  first one whatever it is); with DHT_ROT on from the smallest term after the largest --, the
+     *  split of each by Distribution.verticalDHTPosition into 2^partitionExponent partitions, and with
+     *  DHT_REMOVE IndexCell.remove(termHash) of what was selected.  Transmission sends each
+     *  partition's cells to its target peers; what could not be sent goes back through
+     *  addPostings(..., ADD_KEEP).  DHT_COUNT_ONLY: only stats are filled. */
+    public synchronized DhtSelection dhtSelect(final byte[] start, final byte[] limit, final int maxContainers,
+                                               final long maxRefs, final int partitionExponent, final int flags) {
+        final long[] stats = new long[10];
+        final Object[] r = dhtSelect(this.ctx, start, limit, maxContainers, maxRefs, partitionExponent, flags, stats);
+        if (r == null) throw new IllegalStateException("yrwi_dht_select failed");
+        if ((flags & DHT_COUNT_ONLY) != 0) {
+            return new DhtSelection(new byte[0][], new long[] {0L}, new byte[0], 1 << partitionExponent, stats);
+        }
+        final byte[] flat = (byte[]) r[0];
+        final byte[][] terms = new byte[flat.length / 12][];
+        for (int j = 0; j < terms.length; j++) terms[j] = java.util.Arrays.copyOfRange(flat, 12 * j, 12 * j + 12);
+        return new DhtSelection(terms, (long[]) r[1], (byte[]) r[2], 1 << partitionExponent, stats);
     }
 
     /** query(...) under SearchEvent.addRWIs constraints (SearchEvent.java:736-806) and,
@@ -479,6 +533,8 @@ public final class GpuRWI implements AutoCloseable {
                                        int k, int[] profile32, String language, long nowMillis, long[] stats);
     private static native long[] loadHeaps(long ctx, String[] paths, int byName);
     private static native long[] dumpHeap(long ctx, String path, byte[] terms, int nterms, long nowMs);
+    private static native Object[] dhtSelect(long ctx, byte[] start, byte[] limit, int maxContainers, long maxRefs,
+                                             int partitionExponent, int flags, long[] stats);
     private static native byte[] queryFiltered(long ctx, byte[] incl, int nincl, byte[] excl, int nexcl,
                                                int maxDistance, int k, int[] profile32, String language,
                                                long nowMillis, byte[] constraint, boolean allOf, int contentdom,

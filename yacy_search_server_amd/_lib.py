@@ -151,6 +151,18 @@ class CDumpStats(ctypes.Structure):
          ("t_total_ns", ctypes.c_int64)]
 
 
+DHT_ROT, DHT_REMOVE, DHT_SKIP_PRIVATE, DHT_COUNT_ONLY = 1, 2, 4, 8  # YRWI_DHT_* flags of yrwi_dht_select
+DHT_MAX_EXPONENT = 8
+DHT_WINDOW_ROWS_DEFAULT = 1 << 20  # yrwi_dht_select's window without YRWI_DHT_WINDOW_ROWS (rows)
+
+
+class CDhtStats(ctypes.Structure):
+    _fields_ = [("terms", ctypes.c_int64), ("postings", ctypes.c_int64), ("skipped_private", ctypes.c_int64),
+                ("removed", ctypes.c_int64), ("wrapped", ctypes.c_int32), ("windows", ctypes.c_int64),
+                ("launches", ctypes.c_int32), ("syncs", ctypes.c_int32), ("t_pack_ns", ctypes.c_int64),
+                ("t_total_ns", ctypes.c_int64)]
+
+
 # every symbol include/yrwi.h declares, with its ctypes signature
 _VP = ctypes.c_void_p
 SIGNATURES = {
@@ -204,6 +216,9 @@ SIGNATURES = {
                                        ctypes.POINTER(CLoadStats)]),
     "yrwi_dump_heap": (ctypes.c_int, [_VP, ctypes.c_char_p, _VP, ctypes.c_int32, ctypes.c_int64,
                                       ctypes.POINTER(CDumpStats)]),
+    "yrwi_dht_select": (ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32, ctypes.c_int64,
+                                       ctypes.c_int32, ctypes.c_int32, _VP, ctypes.c_int32, _VP, _VP, ctypes.c_int64,
+                                       ctypes.POINTER(CDhtStats)]),
     "yrwi_score_nodes": (ctypes.c_int, [_VP, ctypes.POINTER(CNode), ctypes.c_int64, ctypes.POINTER(CProfile),
                                         ctypes.c_char_p, ctypes.c_int32, _VP]),
     "yrwi_event_open": (ctypes.c_int, [_VP, ctypes.POINTER(CProfile), ctypes.c_char_p, ctypes.c_int64,

@@ -152,15 +152,6 @@ __global__ __launch_bounds__(PACK_THREADS) void k_dump_pack(const int64_t* __res
   }
 }
 
-// the 12 characters of a term key (inverse of key_of)
-void key_chars(const KeyT& k, uint8_t* out) {
-  static const char* A = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789-_";
-  const uint64_t x = k.hi >> 4;
-  for (int j = 0; j < 10; j++) out[j] = (uint8_t)A[(x >> (6 * (9 - j))) & 63];
-  out[10] = (uint8_t)A[((k.hi & 15) << 2) | (k.lo >> 6)];
-  out[11] = (uint8_t)A[k.lo & 63];
-}
-
 int64_t window_bytes() {
   int64_t w = DEFAULT_WINDOW;
   const char* e = getenv("YRWI_DUMP_WINDOW");  // read per call: tests force window boundaries with it
@@ -279,23 +270,7 @@ extern "C" int yrwi_dump_heap(yrwi_ctx* ctx, const char* path, const uint8_t* te
     if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
     S.syncs++;
     // ---- two device and two pinned windows, allocated on the first dump and kept
-    if (ctx->dump_cap < (size_t)W) {
-      note_realloc("dump windows", 4 * (size_t)W);
-      if (ctx->dump_dev) hipFree(ctx->dump_dev);
-      if (ctx->dump_host) hipHostFree(ctx->dump_host);
-      ctx->dump_dev = ctx->dump_host = nullptr;
-      ctx->dump_cap = 0;
-      if (hipMalloc(reinterpret_cast<void**>(&ctx->dump_dev), 2 * (size_t)W) != hipSuccess) {
-        ctx->dump_dev = nullptr;
-        return ctx->fail(YRWI_E_NOMEM, "device allocation (dump windows)");
-      }
-      if (hipHostMalloc(reinterpret_cast<void**>(&ctx->dump_host), 2 * (size_t)W, hipHostMallocDefault) != hipSuccess) {
-        hipFree(ctx->dump_dev);
-        ctx->dump_dev = ctx->dump_host = nullptr;
-        return ctx->fail(YRWI_E_HIP, "pinned host allocation (dump windows)");
-      }
-      ctx->dump_cap = (size_t)W;
-    }
+    if (int rc = ctx->reserve_windows((size_t)W)) return rc;
     const size_t bufstep = ctx->dump_cap;
     int64_t* d_off = arena_alloc<int64_t>(L, nj + 1);
     DumpJob* d_jobs = arena_alloc<DumpJob>(L, nj);

@@ -63,6 +63,15 @@ inline bool key_of(const uint8_t* h, KeyT* k) {
   return true;
 }
 
+// the 12 characters of a key (inverse of key_of)
+inline void key_chars(const KeyT& k, uint8_t* out) {
+  static const char* A = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789-_";
+  const uint64_t x = k.hi >> 4;
+  for (int j = 0; j < 10; j++) out[j] = (uint8_t)A[(x >> (6 * (9 - j))) & 63];
+  out[10] = (uint8_t)A[((k.hi & 15) << 2) | (k.lo >> 6)];
+  out[11] = (uint8_t)A[k.lo & 63];
+}
+
 // Java int arithmetic
 inline int32_t add32(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); }
 inline int32_t mul32(int32_t a, int32_t b) { return (int32_t)((uint32_t)a * (uint32_t)b); }
@@ -463,11 +472,31 @@ struct CtxBase {
   };
   std::vector<LocalBlock*> local_blocks;
   size_t local_bytes = 0;  // of local_blocks
-  // yrwi_dump_heap (yrwi_dump.hip): two device and two pinned windows of dump_cap bytes each,
-  // allocated on the first dump and kept
+  // yrwi_dump_heap (yrwi_dump.hip) and yrwi_dht_select (yrwi_dht.hip): two device and two pinned
+  // windows of dump_cap bytes each, allocated on first use and kept
   uint8_t* dump_dev = nullptr;
   uint8_t* dump_host = nullptr;
   size_t dump_cap = 0;
+  // windows of at least `bytes` each (contents dropped on growth; nothing of them in flight)
+  int reserve_windows(size_t bytes) {
+    if (dump_cap >= bytes) return 0;
+    note_realloc("staging windows", 4 * bytes);
+    if (dump_dev) hipFree(dump_dev);
+    if (dump_host) hipHostFree(dump_host);
+    dump_dev = dump_host = nullptr;
+    dump_cap = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&dump_dev), 2 * bytes) != hipSuccess) {
+      dump_dev = nullptr;
+      return fail(YRWI_E_NOMEM, "device allocation (staging windows)");
+    }
+    if (hipHostMalloc(reinterpret_cast<void**>(&dump_host), 2 * bytes, hipHostMallocDefault) != hipSuccess) {
+      hipFree(dump_dev);
+      dump_dev = dump_host = nullptr;
+      return fail(YRWI_E_HIP, "pinned host allocation (staging windows)");
+    }
+    dump_cap = bytes;
+    return 0;
+  }
 
   int fail(int code, const std::string& m) {
     err = m;

@@ -288,6 +288,22 @@ def _hashes(hs: Sequence[bytes]) -> bytes:
     return out
 
 
+class DhtSelection:
+    """What RWIIndex.dht_select returns: terms (the T selected term hashes in selection order),
+    part_off (P * T + 1 row offsets, partition-major), rows (every selected posting as one
+    (n, 40) uint8 array, cell after cell), partitions (P) and stats (yrwi_dht_stats as a dict)."""
+
+    def __init__(self, terms: List[bytes], part_off: np.ndarray, rows: np.ndarray, partitions: int, stats: dict):
+        self.terms, self.part_off, self.rows, self.partitions, self.stats = terms, part_off, rows, partitions, stats
+
+    def cell(self, p: int, j: int) -> np.ndarray:
+        """the rows of term j that go to partition p, in url-hash order"""
+        if not (0 <= p < self.partitions and 0 <= j < len(self.terms)):
+            raise IndexError("no such cell")
+        c = p * len(self.terms) + j
+        return self.rows[self.part_off[c]:self.part_off[c + 1]]
+
+
 class RWIIndex:
     """A device-resident reverse word index (one GPU, or one URL-hash shard).
 
@@ -426,6 +442,48 @@ class RWIIndex:
         _check(self._h, _lib.lib().yrwi_dump_heap(self._h, os.fsencode(path), tb.ctypes.data if len(tb) else None,
                                                   len(tb) // 12, now_ms, ctypes.byref(st)))
         return {f: getattr(st, f) for f, _ in _lib.CDumpStats._fields_}
+
+    def dht_select_raw(self, start: bytes, limit: bytes, max_containers: int, max_refs: int, partition_exponent: int,
+                       flags: int, terms_out, cap_terms: int, part_off, rows_out, cap_rows: int) -> Tuple[int, dict]:
+        """yrwi_dht_select as it is: the buffers are ctypes arrays, numpy arrays, addresses or
+        None.  Returns (rc, the call's yrwi_dht_stats as a dict) and raises nothing."""
+        st = _lib.CDhtStats()
+        rc = _lib.lib().yrwi_dht_select(self._h, bytes(start), bytes(limit), max_containers, max_refs,
+                                        partition_exponent, flags, _address(terms_out), cap_terms, _address(part_off),
+                                        _address(rows_out), cap_rows, ctypes.byref(st))
+        return rc, {f: getattr(st, f) for f, _ in _lib.CDhtStats._fields_}
+
+    def dht_select(self, start: bytes, limit: bytes, max_containers: int, max_refs: int, partition_exponent: int = 4,
+                   rot: bool = True, remove: bool = False, skip_private: bool = True, count_only: bool = False,
+                   rows_out=None) -> "DhtSelection":
+        """The DHT send path (yrwi_dht_select; Dispatcher.selectContainersEnqueueToBuffer): whole
+        containers in term order from the first term >= start, up to max_containers containers
+        and max_refs references, while their terms are < limit (the first one whatever it is);
+        each split by the top partition_exponent bits of the url key; with remove=True taken out
+        of the index.  A dry run sizes the buffers.  rows_out: a buffer for the rows (a
+        host_array(ctypes.c_uint8, n) lands them without a staging copy) of at least 40 bytes per
+        selected posting; None: a numpy array.  count_only=True: the stats of the dry run alone."""
+        flags = (_lib.DHT_ROT if rot else 0) | (_lib.DHT_SKIP_PRIVATE if skip_private else 0)
+        rc, st = self.dht_select_raw(start, limit, max_containers, max_refs, partition_exponent,
+                                     flags | _lib.DHT_COUNT_ONLY, None, 0, None, None, 0)
+        _check(self._h, rc)
+        T, n, P = st["terms"], st["postings"], 1 << partition_exponent
+        if count_only:
+            return DhtSelection([], np.zeros(1, dtype=np.int64), np.zeros((0, 40), dtype=np.uint8), P, st)
+        terms = np.zeros((max(1, T), 12), dtype=np.uint8)
+        part_off = np.zeros(P * T + 1, dtype=np.int64)
+        if rows_out is None:
+            rows = np.zeros((max(1, n), 40), dtype=np.uint8)
+        else:
+            rows = np.ctypeslib.as_array(rows_out) if not isinstance(rows_out, np.ndarray) else rows_out
+            rows = rows.reshape(-1).view(np.uint8)
+            if rows.size < 40 * n:
+                raise ValueError("rows_out is smaller than the selection")
+            rows = rows[:40 * n].reshape(-1, 40)
+        rc, st = self.dht_select_raw(start, limit, max_containers, max_refs, partition_exponent,
+                                     flags | (_lib.DHT_REMOVE if remove else 0), terms, T, part_off, rows, n)
+        _check(self._h, rc)
+        return DhtSelection([terms[j].tobytes() for j in range(T)], part_off, rows[:n], P, st)
 
     def build_url_ids(self) -> None:
         """Bring the url dictionary up to date now (else the next query does)."""
