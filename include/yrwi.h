@@ -288,6 +288,45 @@ int yrwi_remove_hosts(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, con
  * it holds. */
 int yrwi_count_hosts(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uint8_t* hosts6,
                      int32_t nhosts, int64_t* counts, int64_t* lists_hit);
+/* Census of the hosts: which hosts have postings in the selected lists, and how many each (the front end of
+ * yrwi_remove_hosts: the index-wide form of the per-container ConcurrentScoreMap.inc per host hash that
+ * ReferenceOrder.doms keeps.  UNVERIFIED against a reference line: the reference has no single method that
+ * groups the whole RWI by host).  The selection is yrwi_count_hosts': nterms == 0 every list, otherwise the
+ * named lists, duplicates once, unknown terms ignored, an ill-formed term YRWI_E_HASH; the call waits for the
+ * batches in flight and changes nothing in the context.  The result is the hosts with at least
+ * max(min_postings, 1) postings in the selected lists, in `order`; the first min(hosts_passing, cap) of them
+ * are written: hosts6_out + 6 i receives the six characters of the host hash (as yrwi_filter.sitehash),
+ * counts_out[i] its postings -- what yrwi_count_hosts returns for that host over the same selection -- and
+ * *nout the number written.  cap < hosts_passing is not an error (the top N); cap == 0 with NULL buffers
+ * only fills st.  `order` outside the two values, cap < 0, or cap > 0 with a NULL buffer: YRWI_E_ARG; on any
+ * error no output buffer is written.  st and nout may be NULL.
+ * No list is read back: one streaming pass over the 9 key bytes of every selected posting (k_census, grid and
+ * spans as the marking pass of yrwi_remove_hosts) groups them by host, per workgroup in an LDS table of
+ * YRWI_CENSUS_LDS_SLOTS slots (environment, read per call, a power of two from 64 to 4096, default 2048) and
+ * then in a device table of open addressing (16 B per slot); a posting whose lane finds no place in the LDS
+ * table is added to the device table directly (lds_bypass).  The device table starts with the smaller of the
+ * next power of two of twice the selected postings and YRWI_CENSUS_SLOTS (environment, read per call, rounded
+ * down to a power of two, at least 64, default 4,194,304); a pass that finds no place for a host (within
+ * 128 probes) is run again with four times the slots (passes), up to 2^30 slots, beyond which, or when the
+ * table cannot be allocated, the call returns YRWI_E_NOMEM.  The hosts that pass are compacted and sorted on
+ * the device and only the first min(hosts_passing, cap) cross PCIe.  A sharded context counts what it holds:
+ * no collective is involved, every rank is asked the same thing, the ranks' counts of a host add up and the
+ * caller merges them.  Per-host distinct url counts and per-host list counts are not part of this. */
+#define YRWI_CENSUS_BY_HOST 0   /* ascending host hash (Base64Order of the 6 characters = the 36-bit key order) */
+#define YRWI_CENSUS_BY_COUNT 1  /* postings descending; equal counts by ascending host hash */
+typedef struct yrwi_census_stats {
+  int64_t lists, postings;  /* selected non-empty lists, rows in them: the counts of ALL hosts add up to postings */
+  int64_t hosts;            /* distinct hosts in them */
+  int64_t hosts_passing;    /* of which with at least min_postings postings: what a cap must hold to get all */
+  int64_t table_slots;      /* slots of the device table in the last counting pass */
+  int32_t passes;           /* counting passes: 1 + the times the table overflowed and was enlarged */
+  int64_t lds_bypass;       /* postings counted straight into the device table (their workgroup's LDS table had no place); last pass */
+  int32_t launches, syncs;  /* functions of `passes` (and of `order`: BY_COUNT sorts twice) alone, never of lists, hosts or postings */
+  int64_t t_count_ns;       /* device time of the counting passes' k_census launches (HIP events) */
+  int64_t t_total_ns;
+} yrwi_census_stats;
+int yrwi_host_census(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, int32_t order, int64_t min_postings,
+                     uint8_t* hosts6_out, int64_t* counts_out, int64_t cap, int64_t* nout, yrwi_census_stats* st);
 /* Brings the url dictionary (url hash -> order-preserving 32-bit url id, the
  * join key in HBM) up to date now instead of at the next query.  The first
  * build sorts every key; later put_list / removal / load_heaps changes are

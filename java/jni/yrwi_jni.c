@@ -141,6 +141,38 @@ JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_countHosts(JNIEnv
   return res;
 }
 
+/* yrwi_host_census as long[12 + nout]: nout, then yrwi_census_stats (lists, postings, hosts, hosts_passing,
+ * table_slots, passes, lds_bypass, launches, syncs, t_count_ns, t_total_ns), then the nout counts; the hosts
+ * (6 bytes each) go into hosts6 (at least 6 * cap bytes); NULL when the call failed */
+JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_hostCensus(JNIEnv* env, jclass c, jlong ctx,
+                                                                         jbyteArray terms, jint nterms, jint order,
+                                                                         jlong min_postings, jlong cap,
+                                                                         jbyteArray hosts6) {
+  if (cap < 0 || (cap > 0 && (!hosts6 || (jlong)(*env)->GetArrayLength(env, hosts6) < 6 * cap))) return NULL;
+  uint8_t* t = copy_in(env, terms, (int64_t)nterms * 12);
+  if (!t) return NULL;
+  uint8_t* h = (uint8_t*)malloc((size_t)cap * 6 + 1);
+  jlong* v = (jlong*)calloc((size_t)cap + 12, sizeof(jlong));
+  yrwi_census_stats st;
+  int64_t n = 0;
+  int rc = h && v ? yrwi_host_census((yrwi_ctx*)(intptr_t)ctx, t, nterms, order, min_postings, cap ? h : NULL,
+                                     cap ? (int64_t*)(v + 12) : NULL, cap, &n, &st)
+                  : YRWI_E_NOMEM;
+  free(t);
+  jlongArray res = NULL;
+  if (rc == 0) {
+    const jlong s[12] = {n, st.lists, st.postings, st.hosts, st.hosts_passing, st.table_slots, st.passes,
+                         st.lds_bypass, st.launches, st.syncs, st.t_count_ns, st.t_total_ns};
+    memcpy(v, s, sizeof(s));
+    if (n > 0) (*env)->SetByteArrayRegion(env, hosts6, 0, (jsize)(6 * n), (const jbyte*)h);
+    res = (*env)->NewLongArray(env, (jsize)(12 + n));
+    if (res) (*env)->SetLongArrayRegion(env, res, 0, (jsize)(12 + n), v);
+  }
+  free(h);
+  free(v);
+  return res;
+}
+
 JNIEXPORT jbyteArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_joinExclude(JNIEnv* env, jclass c, jlong ctx,
                                                                           jbyteArray incl, jint nincl, jbyteArray excl,
                                                                           jint nexcl, jint maxd, jlong now) {

@@ -151,6 +151,53 @@ public final class GpuRWI implements AutoCloseable {
         return counts;
     }
 
+    /** Orders of hostCensus (YRWI_CENSUS_BY_*). */
+    public static final int CENSUS_BY_HOST = 0;   // ascending host hash (Base64Order)
+    public static final int CENSUS_BY_COUNT = 1;  // postings descending, equal counts by ascending host hash
+
+    /** What hostCensus returns: hosts[i] (6 bytes, url-hash characters 6..11) has counts[i] postings in
+     *  the selected lists; stats = {lists, postings, hosts, hostsPassing, tableSlots, passes, ldsBypass,
+     *  launches, syncs, tCountNs, tTotalNs} (yrwi_census_stats). */
+    public static final class HostCensus {
+        public final byte[][] hosts;
+        public final long[] counts;
+        public final long[] stats;
+        HostCensus(final byte[][] hosts, final long[] counts, final long[] stats) {
+            this.hosts = hosts;
+            this.counts = counts;
+            this.stats = stats;
+        }
+    }
+
+    /** Which hosts have postings in the lists of `terms` (terms == null or empty: in every list) and how
+     *  many each (yrwi_host_census): the hosts with at least minPostings postings in `order`, the first
+     *  `top` of them, or all of them with top &lt; 0 (a first call asks how many pass).  The counts are
+     *  those countHosts gives for the same hosts and terms; no list crosses to the host.  The front end
+     *  of removeHosts: the index-wide form of the per-container host counts of ReferenceOrder.doms. */
+    public synchronized HostCensus hostCensus(final byte[][] terms, final int order, final long minPostings,
+                                              final long top) {
+        final int nterms = terms == null ? 0 : terms.length;
+        final byte[] t = nterms == 0 ? new byte[0] : flatten(terms);
+        long cap = top;
+        if (cap < 0) {
+            final long[] r = hostCensus(this.ctx, t, nterms, order, minPostings, 0L, new byte[0]);
+            if (r == null) throw new IllegalStateException("yrwi_host_census failed");
+            cap = r[4];  // hostsPassing
+        }
+        if (6L * cap > Integer.MAX_VALUE) throw new IllegalArgumentException("more hosts than a byte[] holds: give top");
+        final byte[] h6 = new byte[(int) (6L * cap)];
+        final long[] r = hostCensus(this.ctx, t, nterms, order, minPostings, cap, h6);
+        if (r == null) throw new IllegalStateException("yrwi_host_census failed");
+        final int n = (int) r[0];
+        final byte[][] hosts = new byte[n][];
+        final long[] counts = new long[n];
+        for (int i = 0; i < n; i++) {
+            hosts[i] = java.util.Arrays.copyOfRange(h6, 6 * i, 6 * i + 6);
+            counts[i] = r[12 + i];
+        }
+        return new HostCensus(hosts, counts, java.util.Arrays.copyOfRange(r, 1, 12));
+    }
+
     /** Index.size(termHash) of each term on the GPU index (yrwi_list_size; 0: no list). */
     public synchronized long[] listSizes(final byte[][] terms) {
         return listSizes(this.ctx, flatten(terms), terms.length);
@@ -521,6 +568,9 @@ public final class GpuRWI implements AutoCloseable {
     private static native long[] removePostings(long ctx, byte[] terms, int nterms, byte[] urls, int nurls);
     private static native long[] removeHosts(long ctx, byte[] terms, int nterms, byte[] hosts6, int nhosts);
     private static native long[] countHosts(long ctx, byte[] terms, int nterms, byte[] hosts6, int nhosts);
+    // {nout, the 11 statistics, counts[0 .. nout)}; hosts6Out (6 * cap bytes) receives the hosts; null: failed
+    private static native long[] hostCensus(long ctx, byte[] terms, int nterms, int order, long minPostings, long cap,
+                                            byte[] hosts6Out);
     private static native byte[] joinExclude(long ctx, byte[] incl, int nincl, byte[] excl, int nexcl,
                                              int maxDistance, long nowMillis);
     private static native long[] normalizeScore(long ctx, byte[] rows, int m, int[] profile32, String language,

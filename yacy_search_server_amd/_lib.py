@@ -141,8 +141,20 @@ ADD_POLICIES = {"replace": 0, "keep": 1, "recent": 2}
 
 HOST_LDS_MAX = 2048  # YRWI_HOST_LDS_MAX: the largest host set yrwi_remove_hosts / yrwi_count_hosts search in LDS
 
+CENSUS_BY_HOST, CENSUS_BY_COUNT = 0, 1  # YRWI_CENSUS_BY_*: the orders of yrwi_host_census
+CENSUS_ORDERS = {"host": CENSUS_BY_HOST, "count": CENSUS_BY_COUNT}
+CENSUS_SLOTS_DEFAULT = 1 << 22  # yrwi_host_census's largest first device table without YRWI_CENSUS_SLOTS (slots)
+CENSUS_LDS_SLOTS_DEFAULT = 2048  # a workgroup's LDS table without YRWI_CENSUS_LDS_SLOTS (slots)
 
-DUMP_WINDOW_DEFAULT = 32 << 20  # yrwi_dump_heap's window without YRWI_DUMP_WINDOW (bytes)
+
+class CCensusStats(ctypes.Structure):
+    _fields_ = [("lists", ctypes.c_int64), ("postings", ctypes.c_int64), ("hosts", ctypes.c_int64),
+                ("hosts_passing", ctypes.c_int64), ("table_slots", ctypes.c_int64), ("passes", ctypes.c_int32),
+                ("lds_bypass", ctypes.c_int64), ("launches", ctypes.c_int32), ("syncs", ctypes.c_int32),
+                ("t_count_ns", ctypes.c_int64), ("t_total_ns", ctypes.c_int64)]
+
+
+DUMP_WINDOW_DEFAULT = 32 << 20 # yrwi_dump_heap's window without YRWI_DUMP_WINDOW (bytes)
 
 
 class CDumpStats(ctypes.Structure):
@@ -185,6 +197,9 @@ SIGNATURES = {
                                          ctypes.POINTER(CUpdateStats)]),
     "yrwi_count_hosts": (ctypes.c_int, [_VP, _VP, ctypes.c_int32, _VP, ctypes.c_int32, _VP,
                                         ctypes.POINTER(ctypes.c_int64)]),
+    "yrwi_host_census": (ctypes.c_int, [_VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _VP, _VP,
+                                        ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                                        ctypes.POINTER(CCensusStats)]),
     "yrwi_build_url_ids": (ctypes.c_int, [_VP]),
     "yrwi_list_size": (ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]),
     "yrwi_get_list": (ctypes.c_int, [_VP, ctypes.c_char_p, _VP, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),

@@ -37,6 +37,24 @@
 // chunk, with no host wait between chunks: launches and syncs depend on the number of chunks
 // alone, and nothing stops at 2^31 postings.
 //
+// yrwi_host_census: which hosts the selected lists hold and how many postings each, the index-wide
+// form of the per-container host counts of ReferenceOrder.doms (UNVERIFIED against a reference
+// line: the reference has no single method that groups the whole RWI by host).  The same streaming
+// pass over the 9 key bytes of every selected posting, grid and spans as k_host_mark, but a group-by
+// with an unknown key set instead of a lookup in a given one (k_census): every workgroup sums in an
+// LDS table of YRWI_CENSUS_LDS_SLOTS slots (12 B each: key host36 + 1, 0 = empty, and a 32-bit
+// count; a wave whose live lanes carry one host makes one LDS add, else every lane inserts with at
+// most 64 probes) and adds its slots into the device table at the end of its span, one global
+// atomic per host per workgroup; a posting whose lane finds no place in LDS goes straight to the
+// device table, equal keys of the wave as one add (lds_bypass).  The device table is open
+// addressing with linear probing, 16 B per slot, 64-bit atomicCAS / atomicAdd; an insert that finds
+// no place within 128 probes sets an overflow word and drops the posting (the waves then leave
+// the pass at their next step), and the host runs the
+// pass again with four times the slots.  The table's hosts with at least min_postings are flagged,
+// scanned, compacted and radix-sorted on the device (by the 36-bit key; BY_COUNT: then stably by
+// count descending), and only the first min(hosts_passing, cap) cross PCIe.  All scratch is the
+// lane's arena; 5 launches and one sync per counting pass, 5 or 6 launches and one sync after them.
+//
 // A changed list is a new list in index memory (the old copy is dead until repack_index,
 // reached through ensure_url_ids) and goes through index_changed like a replaced list.
 
@@ -1055,4 +1073,299 @@ extern "C" int yrwi_remove_hosts(yrwi_ctx* ctx, const uint8_t* terms12, int32_t 
   }
   put_stats(st, S, T);
   return 0;
+}
+
+// ---------------------------------------------------------------- census of the hosts
+namespace {
+
+constexpr int64_t CENSUS_SLOTS_DEFAULT = (int64_t)1 << 22;  // device table slots a call starts with at most (YRWI_CENSUS_SLOTS)
+constexpr int64_t CENSUS_SLOTS_MAX = (int64_t)1 << 30;      // 16 GiB of table; the scan counts in int
+constexpr int CENSUS_LDS_DEFAULT = 2048;                    // slots of a workgroup's LDS table (YRWI_CENSUS_LDS_SLOTS)
+constexpr int CENSUS_LDS_PROBES = 64;                       // places a lane tries in the LDS table (all of a 64-slot table)
+constexpr int CENSUS_PROBES = 128;                          // places an insert tries in the device table (at most all)
+enum { CEN_OVERFLOW = 0, CEN_BYPASS = 1, CEN_HOSTS = 2, CEN_PASSING = 3, CEN_WORDS = 4 };
+
+__device__ __forceinline__ uint64_t census_hash(uint64_t key1) { return key1 * 0x9E3779B97F4A7C15ull; }
+
+// tab[2 p] = host36 + 1 (0: empty, as htab_insert's tables), tab[2 p + 1] = postings; linear probing from
+// the key's place.  No place within the probes (or the pass has overflowed already): the overflow word is
+// set and the postings are dropped; the host runs the pass again with a larger table.
+__device__ __forceinline__ void census_add(unsigned long long* __restrict__ tab, uint64_t mask, uint64_t key1,
+                                           unsigned long long n, unsigned long long* __restrict__ ctr) {
+  uint64_t p = (census_hash(key1) >> 24) & mask;
+  const uint64_t probes = std::min<uint64_t>(mask + 1, CENSUS_PROBES);
+  for (uint64_t k = 0; k < probes; k++, p = (p + 1) & mask) {
+    // a key never changes once set: only a slot read as empty needs the compare-and-swap
+    unsigned long long cur = __hip_atomic_load(&tab[2 * p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == 0) cur = atomicCAS(&tab[2 * p], 0ull, (unsigned long long)key1);
+    if (cur == 0 || cur == key1) {
+      atomicAdd(&tab[2 * p + 1], n);
+      return;
+    }
+    if ((k & 63) == 63 && __hip_atomic_load(&ctr[CEN_OVERFLOW], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+  }
+  atomicOr(&ctr[CEN_OVERFLOW], 1ull);
+}
+
+// n postings of key1 into the workgroup's table (keys lk[S], counts lc[S]); false: no place within the probes
+__device__ __forceinline__ bool census_lds_add(unsigned long long* lk, uint32_t* lc, uint32_t smask, uint64_t key1,
+                                               uint32_t n) {
+  uint32_t p = (uint32_t)(census_hash(key1) >> 52) & smask;
+  for (int k = 0; k < CENSUS_LDS_PROBES; k++, p = (p + 1) & smask) {
+    unsigned long long cur = *reinterpret_cast<volatile unsigned long long*>(&lk[p]);
+    if (cur == 0) cur = atomicCAS(&lk[p], 0ull, (unsigned long long)key1);
+    if (cur == 0 || cur == key1) {
+      atomicAdd(&lc[p], n);
+      return true;
+    }
+  }
+  return false;
+}
+
+// One step of a thread, as mark_tile's loads: postings base + 256 u + thread (u < 4) below end -> host36 + 1
+// (0: past end).  The four key loads are issued before the first use.
+__device__ __forceinline__ void census_tile(SegCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                            int nj, int64_t total, int64_t base, int64_t end, uint64_t key1[4]) {
+  uint64_t h[4];
+  uint32_t l[4];
+  bool live[4];
+#pragma unroll
+  for (int u = 0; u < 4; u++) {
+    const int64_t i = base + u * 256 + threadIdx.x;
+    live[u] = i < end;
+    h[u] = 0;
+    l[u] = 0;
+    if (live[u]) {
+      seg_seek(s, jobs, off, nj, total, i);
+      h[u] = s.kh[i - s.lo];
+      l[u] = s.kl[i - s.lo];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < 4; u++) key1[u] = live[u] ? host36(h[u], l[u]) + 1 : 0;
+}
+
+// Counting pass: a group-by of the selected postings on their host.  Grid and spans as k_host_mark.  Every
+// workgroup sums in an LDS table of S slots (dynamic shared memory: S 8-B keys, then S 4-B counts) and adds
+// its slots into the device table at the end of its span; a posting whose lane finds no place in LDS goes
+// straight to the device table, equal keys of the wave as one add (counted in ctr[CEN_BYPASS]).  Every wave
+// of a workgroup runs every step whole (the ballots); the only barriers are before the first and after the
+// last step.
+__global__ __launch_bounds__(256) void k_census(const RmJob* __restrict__ jobs, const int64_t* __restrict__ off, int nj,
+                                                int64_t total, int S, unsigned long long* __restrict__ tab,
+                                                uint64_t mask, unsigned long long* __restrict__ ctr) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char census_lds[];
+  unsigned long long* lk = reinterpret_cast<unsigned long long*>(census_lds);
+  uint32_t* lc = reinterpret_cast<uint32_t*>(census_lds + (size_t)S * 8);
+  for (int i = threadIdx.x; i < S; i += blockDim.x) {
+    lk[i] = 0;
+    lc[i] = 0;
+  }
+  __syncthreads();
+  const uint32_t smask = (uint32_t)S - 1;
+  const int lane = threadIdx.x & 63;
+  int64_t begin, end;
+  host_span(total, &begin, &end);
+  SegCursor cur;
+  unsigned long long bypass = 0;  // the same in every lane of the wave
+  for (int64_t base = begin; base < end; base += HOST_TILE) {
+    // the pass has overflowed and will be run again: the wave leaves (no barrier waits for it in here)
+    if (__any(__hip_atomic_load(&ctr[CEN_OVERFLOW], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) break;
+    uint64_t keys[4];
+    census_tile(cur, jobs, off, nj, total, base, end, keys);
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const uint64_t key1 = keys[u];
+      const bool live = key1 != 0;
+      const uint64_t act = __ballot(live);
+      // one host owns the wave's postings (a hot spot): one lane adds them all; else every lane its own
+      const int lead = act ? __ffsll((unsigned long long)act) - 1 : 0;
+      const uint64_t lkey = shfl64(key1, lead);
+      const bool uni = __ballot(live && key1 != lkey) == 0;
+      const uint32_t n = uni ? (uint32_t)__popcll(act) : 1u;
+      bool pend = false;  // this lane's postings found no place in LDS
+      if (uni ? (act && lane == lead) : live) pend = !census_lds_add(lk, lc, smask, key1, n);
+      uint64_t left = __ballot(pend);
+      while (left) {  // equal keys aggregated within the wave
+        const int pl = __ffsll((unsigned long long)left) - 1;
+        const uint64_t pk = shfl64(key1, pl);
+        const uint64_t same = __ballot(pend && key1 == pk);
+        const unsigned long long m = uni ? n : (unsigned long long)__popcll(same);
+        if (lane == pl) census_add(tab, mask, pk, m, ctr);
+        bypass += m;
+        left &= ~same;
+      }
+    }
+  }
+  if (bypass && lane == 0) atomicAdd(&ctr[CEN_BYPASS], bypass);
+  __syncthreads();
+  if (__hip_atomic_load(&ctr[CEN_OVERFLOW], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+  for (int i = threadIdx.x; i < S; i += blockDim.x)
+    if (lk[i]) census_add(tab, mask, lk[i], (unsigned long long)lc[i], ctr);
+}
+
+// flag[i] = slot i holds a host with at least minp postings; flag[slots] = 0 (the scan's last element);
+// ctr[CEN_HOSTS] += non-empty slots, ctr[CEN_PASSING] += flagged ones (one atomic each per wave)
+__global__ __launch_bounds__(256) void k_census_flag(const unsigned long long* __restrict__ tab, int64_t slots,
+                                                     unsigned long long minp, int32_t* __restrict__ flag,
+                                                     unsigned long long* __restrict__ ctr) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool used = false, pass = false;
+  if (i < slots) {
+    const ulonglong2 s = *reinterpret_cast<const ulonglong2*>(tab + 2 * i);
+    used = s.x != 0;
+    pass = used && s.y >= minp;
+  }
+  if (i <= slots) flag[i] = pass ? 1 : 0;
+  const uint64_t bu = __ballot(used), bp = __ballot(pass);
+  if ((threadIdx.x & 63) == 0) {
+    if (bu) atomicAdd(&ctr[CEN_HOSTS], (unsigned long long)__popcll(bu));
+    if (bp) atomicAdd(&ctr[CEN_PASSING], (unsigned long long)__popcll(bp));
+  }
+}
+
+__global__ void k_census_place(const unsigned long long* __restrict__ tab, int64_t slots,
+                               const int32_t* __restrict__ flag, const int64_t* __restrict__ px,
+                               uint64_t* __restrict__ okey, uint64_t* __restrict__ ocnt) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= slots || !flag[i]) return;
+  const ulonglong2 s = *reinterpret_cast<const ulonglong2*>(tab + 2 * i);
+  okey[px[i]] = s.x - 1;
+  ocnt[px[i]] = s.y;
+}
+
+int64_t pow2_floor(int64_t v) {
+  int64_t p = 1;
+  while (p <= v / 2) p *= 2;
+  return p;
+}
+
+// environment knob `name`, read per call (tests reach the overflow paths with them): rounded down to a power
+// of two within [lo, hi]
+int64_t census_knob(const char* name, int64_t dflt, int64_t lo, int64_t hi) {
+  const char* e = getenv(name);
+  const int64_t v = e ? atoll(e) : dflt;
+  return pow2_floor(std::min(std::max(v, lo), hi));
+}
+
+}  // namespace
+
+extern "C" int yrwi_host_census(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, int32_t order,
+                                int64_t min_postings, uint8_t* hosts6_out, int64_t* counts_out, int64_t cap,
+                                int64_t* nout, yrwi_census_stats* st) {
+  if (!ctx || nterms < 0 || (nterms > 0 && !terms12)) return YRWI_E_ARG;
+  if (order != YRWI_CENSUS_BY_HOST && order != YRWI_CENSUS_BY_COUNT) return ctx->fail(YRWI_E_ARG, "unknown census order");
+  if (cap < 0 || (cap > 0 && (!hosts6_out || !counts_out))) return ctx->fail(YRWI_E_ARG, "census capacity without buffers");
+  const auto t_begin = std::chrono::steady_clock::now();
+  yrwi_census_stats S;
+  std::memset(&S, 0, sizeof(S));
+  Tally T;
+  HostPass P;
+  if (int rc = host_select(ctx, terms12, nterms, nullptr, 0, &P)) return rc;
+  auto finish = [&](int64_t n) {
+    S.launches = T.launches;
+    S.syncs = T.syncs;
+    S.t_total_ns =
+        std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_begin).count();
+    if (nout) *nout = n;
+    if (st) *st = S;
+    return 0;
+  };
+  if (P.jobs.empty()) return finish(0);
+  const int nj = (int)P.jobs.size();
+  const int64_t total = P.total;
+  const unsigned long long minp = (unsigned long long)std::max<int64_t>(min_postings, 1);
+  S.lists = nj;
+  S.postings = total;
+  Lane* L = ctx->lanes[0];
+  if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
+  T.syncs++;
+  P.d_jobs = arena_alloc<RmJob>(L, nj);
+  P.d_off = arena_alloc<int64_t>(L, nj);
+  if (!P.d_jobs || !P.d_off) return ctx->fail(YRWI_E_NOMEM, "device allocation (host census)");
+  if (int rc = upload(L, P.d_jobs, P.jobs, P.d_off, P.off)) return ctx->take(L, rc);
+  T.launches++;
+  // ---- counting passes: the table sized and zeroed, one launch over the flattened keys, the table's
+  //      hosts flagged and scanned, the four counters read back; on overflow again with four times the slots
+  const int lds = (int)census_knob("YRWI_CENSUS_LDS_SLOTS", CENSUS_LDS_DEFAULT, 64, 4096);
+  int64_t want = 1;
+  while (want < 2 * total && want < CENSUS_SLOTS_MAX) want *= 2;
+  int64_t slots = std::min(want, census_knob("YRWI_CENSUS_SLOTS", CENSUS_SLOTS_DEFAULT, 64, CENSUS_SLOTS_MAX));
+  unsigned long long* tab = nullptr;
+  int32_t* flag = nullptr;
+  int64_t* px = nullptr;
+  int64_t ctr[CEN_WORDS] = {0, 0, 0, 0};
+  for (;; slots *= 4) {
+    if (slots > CENSUS_SLOTS_MAX) return ctx->fail(YRWI_E_NOMEM, "host census table beyond 2^30 slots");
+    // the counters sit in front of the table: one memset zeroes both
+    unsigned long long* blk = arena_alloc<unsigned long long>(L, CEN_WORDS + 2 * slots);
+    flag = arena_alloc<int32_t>(L, slots + 1);
+    px = arena_alloc<int64_t>(L, slots + 1);
+    size_t tb = 0;
+    HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, flag, px, (int)(slots + 1), L->stream));
+    void* tmp = L->arena.alloc(tb);
+    if (!blk || !flag || !px || !tmp) return ctx->fail(YRWI_E_NOMEM, "device allocation (host census table)");
+    unsigned long long* d_ctr = blk;
+    tab = blk + CEN_WORDS;  // 32 B into a 256-B aligned block: 16-B slots
+    HIPCHK(ctx, hipMemsetAsync(blk, 0, (size_t)(CEN_WORDS + 2 * slots) * 8, L->stream));
+    hipEvent_t e0 = L->event(), e1 = L->event();
+    HIPCHK(ctx, hipEventRecord(e0, L->stream));
+    hipLaunchKernelGGL(k_census, dim3(mark_blocks(total)), dim3(256), (size_t)lds * 12, L->stream, P.d_jobs, P.d_off, nj,
+                       total, lds, tab, (uint64_t)(slots - 1), d_ctr);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(e1, L->stream));
+    hipLaunchKernelGGL(k_census_flag, dim3(blocks(slots + 1)), dim3(256), 0, L->stream, tab, slots, minp, flag, d_ctr);
+    HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(tmp, tb, flag, px, (int)(slots + 1), L->stream));
+    HIPCHK(ctx, hipGetLastError());
+    const int64_t* h = reinterpret_cast<const int64_t*>(readback(L, &L->down_stage, d_ctr, CEN_WORDS, 8, 8));
+    if (!h) return ctx->take(L, YRWI_E_HIP);
+    T.launches += 5;
+    HIPCHK(ctx, lane_sync(L));
+    T.syncs++;
+    std::memcpy(ctr, h, sizeof(ctr));  // (the pinned landing buffer is reused below)
+    float msf = 0.f;
+    if (hipEventElapsedTime(&msf, e0, e1) == hipSuccess) S.t_count_ns += (int64_t)((double)msf * 1e6);
+    S.passes++;
+    S.table_slots = slots;
+    S.lds_bypass = ctr[CEN_BYPASS];
+    if (!ctr[CEN_OVERFLOW]) break;
+  }
+  S.hosts = ctr[CEN_HOSTS];
+  S.hosts_passing = ctr[CEN_PASSING];
+  // ---- the passing hosts compacted and sorted; the first min(hosts_passing, cap) cross to the host
+  const int64_t np = S.hosts_passing, nw = std::min(np, cap);
+  const int ns = (int)std::max<int64_t>(np, 1);  // (no host passes: the sorts run over one unused element)
+  uint64_t* okey = arena_alloc<uint64_t>(L, np);
+  uint64_t* ocnt = arena_alloc<uint64_t>(L, np);
+  uint64_t* skey = arena_alloc<uint64_t>(L, np);
+  uint64_t* scnt = arena_alloc<uint64_t>(L, np);
+  int cbits = 1;  // bits of a count: no host has more than `total` postings
+  while (cbits < 64 && ((int64_t)1 << cbits) <= total) cbits++;
+  size_t t1 = 0, t2 = 0;
+  HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, t1, okey, skey, ocnt, scnt, ns, 0, 36, L->stream));
+  HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairsDescending(nullptr, t2, scnt, ocnt, skey, okey, ns, 0, cbits, L->stream));
+  void* stmp = L->arena.alloc(std::max(t1, t2));
+  if (!okey || !ocnt || !skey || !scnt || !stmp) return ctx->fail(YRWI_E_NOMEM, "device allocation (host census sort)");
+  hipLaunchKernelGGL(k_census_place, dim3(blocks(slots)), dim3(256), 0, L->stream, tab, slots, flag, px, okey, ocnt);
+  HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairs(stmp, t1, okey, skey, ocnt, scnt, ns, 0, 36, L->stream));
+  const uint64_t *rkey = skey, *rcnt = scnt;
+  if (order == YRWI_CENSUS_BY_COUNT) {  // stable: equal counts stay in host order
+    HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairsDescending(stmp, t2, scnt, ocnt, skey, okey, ns, 0, cbits, L->stream));
+    rkey = okey;
+    rcnt = ocnt;
+    T.launches++;
+  }
+  HIPCHK(ctx, hipGetLastError());
+  const uint64_t* hk = reinterpret_cast<const uint64_t*>(readback(L, &L->out_stage, rkey, nw, 8, 8));
+  const int64_t* hc = reinterpret_cast<const int64_t*>(readback(L, &L->down_stage, rcnt, nw, 8, 8));
+  if (!hk || !hc) return ctx->take(L, YRWI_E_HIP);
+  T.launches += 4;
+  HIPCHK(ctx, lane_sync(L));
+  T.syncs++;
+  static const char* A = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789-_";
+  for (int64_t i = 0; i < nw; i++) {
+    for (int j = 0; j < 6; j++) hosts6_out[i * 6 + j] = (uint8_t)A[(hk[i] >> (6 * (5 - j))) & 63];
+    counts_out[i] = hc[i];
+  }
+  return finish(nw);
 }

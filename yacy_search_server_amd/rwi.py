@@ -418,6 +418,35 @@ class RWIIndex:
                                                     counts.ctypes.data if len(counts) else None, ctypes.byref(hit)))
         return counts, hit.value
 
+    def host_census(self, terms: Optional[Sequence[bytes]] = None, order: str = "count", min_postings: int = 1,
+                    top: Optional[int] = None) -> Tuple[List[bytes], np.ndarray, dict]:
+        """Which hosts have postings in the lists of `terms`, or with terms=None in every list, and
+        how many each (yrwi_host_census): the hosts with at least min_postings postings, by
+        order="count" (postings descending, equal counts by host hash) or "host" (ascending host
+        hash), all of them or the first `top`.  Returns (6-byte host hashes, their postings as
+        int64 -- what count_hosts gives for them --, the call's yrwi_census_stats as a dict).  No
+        list leaves the device; with top=None a first call asks how many hosts pass (cap 0) and a
+        second one fetches them."""
+        o = _lib.CENSUS_ORDERS[order]
+        if top is not None and top < 0:
+            raise ValueError("top must not be negative")
+        tb = np.frombuffer(_hashes(terms or ()), dtype=np.uint8)
+        st = _lib.CCensusStats()
+        if terms is not None and len(terms) == 0:  # no term named (nterms == 0 would mean every list)
+            return [], np.zeros(0, dtype=np.int64), {f: 0 for f, _ in _lib.CCensusStats._fields_}
+        call = lambda hosts, counts, cap, n: _check(self._h, _lib.lib().yrwi_host_census(
+            self._h, tb.ctypes.data if len(tb) else None, len(tb) // 12, o, min_postings, hosts, counts, cap, n,
+            ctypes.byref(st)))
+        if top is None:
+            call(None, None, 0, None)
+            top = st.hosts_passing
+        hosts = np.zeros((top, 6), dtype=np.uint8)
+        counts = np.zeros(top, dtype=np.int64)
+        n = ctypes.c_int64()
+        call(hosts.ctypes.data if top else None, counts.ctypes.data if top else None, top, ctypes.byref(n))
+        return ([bytes(h) for h in hosts[:n.value]], counts[:n.value].copy(),
+                {f: getattr(st, f) for f, _ in _lib.CCensusStats._fields_})
+
     def load_heaps(self, paths: Sequence[str], order_by_name: bool = False) -> "_lib.CLoadStats":
         """Load YaCy BLOB heap files (IndexCell's ReferenceContainerArray) into the index;
         lists already present act as the RAM cache (the files' rows win)."""
