@@ -169,6 +169,13 @@ typedef struct yrwi_stats {
   int64_t n_chain_launches;
   int64_t t_chain_ns;
   int64_t bytes_chain;
+  /* identical queries of one pass of a batch part run once (YRWI_SHARE=0: every query
+     runs): the queries that took an earlier identical query's result, their share of postings_in and
+     of joined.  postings_in and joined keep their per-query meaning (a repeat counts its lists and its
+     representative's rows); every byte, launch and time field counts executed work only. */
+  int64_t queries_shared;
+  int64_t postings_shared;
+  int64_t joined_shared;
 } yrwi_stats;
 
 /* ---- profile helpers (RankingProfile.java) ---- */

@@ -11,6 +11,7 @@
 // Everything per posting runs on the GPU (yrwi_kernels.hip).
 
 #include "yrwi_host.h"
+#include "yrwi_share.h"
 
 using namespace yrwi;
 
@@ -954,6 +955,15 @@ static int run_batch_part_(const yrwi_ctx* ix, Lane* L, const yrwi_query_desc* q
   // through this lane's arena and staging)
   if (L->sharded && begin_pass(L)) return YRWI_E_HIP;
   if (int rc = plan_batch(L, all)) return rc;
+  // Identical queries of a pass run once (yrwi_share.h): group[i] names the part's earliest query
+  // with query i's key; a pass's first member of a group represents its later ones.  Not on a
+  // sharded context (the ranks resolve "now" apart, and the collectives count queries).
+  const bool share = !L->sharded && share_enabled();
+  std::vector<int32_t> group;
+  if (share && share_groups(all, &group) == 0) group.clear();  // no repeats: nothing to look up
+  for (size_t i = 0; i < group.size(); i++)
+    if (group[i] < 0) group[i] = (int32_t)i;
+  std::vector<int32_t> pass_rep(group.size(), -1);  // by group: its first member in the running pass
   tp = now_ns() - t0;
   const int64_t budget = scratch_budget(L);
   int npass = 0;
@@ -962,9 +972,20 @@ static int run_batch_part_(const yrwi_ctx* ix, Lane* L, const yrwi_query_desc* q
     int g1 = g0;
     int64_t need = 0;
     while (g1 < nq) {
-      const int64_t e = scratch_estimate(all[(size_t)g1]);
+      // a repeat joins and ranks nothing: the floor of the estimate
+      const bool repeat = !group.empty() && pass_rep[(size_t)group[(size_t)g1]] >= g0;
+      const int64_t e = repeat ? 4096 : scratch_estimate(all[(size_t)g1]);
       if (g1 > g0 && need + e > budget) break;
       need += e;
+      if (repeat) {
+        all[(size_t)g1].rep = pass_rep[(size_t)group[(size_t)g1]] - g0;
+        if (st) {
+          st->queries_shared++;
+          st->postings_shared += all[(size_t)g1].postings_in;
+        }
+      } else if (!group.empty()) {
+        pass_rep[(size_t)group[(size_t)g1]] = g1;
+      }
       g1++;
     }
     std::vector<Plan> plans(std::make_move_iterator(all.begin() + g0), std::make_move_iterator(all.begin() + g1));
@@ -1165,6 +1186,9 @@ extern "C" int yrwi_query_batch_rows(yrwi_ctx* ctx, const yrwi_query_desc* q, in
       st->n_chain_launches += p.n_chain_launches;
       st->t_chain_ns += p.t_chain_ns;
       st->bytes_chain += p.bytes_chain;
+      st->queries_shared += p.queries_shared;
+      st->postings_shared += p.postings_shared;
+      st->joined_shared += p.joined_shared;
     }
     st->t_total_ns = now_ns() - t0;
   }

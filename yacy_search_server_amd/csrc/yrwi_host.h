@@ -216,6 +216,9 @@ struct Plan {
   std::vector<KeyT> sel;
   std::vector<uint32_t> sel_uid;
   int64_t sel_ninc[YRWI_MAX_TERMS] = {0}, sel_nexc[YRWI_MAX_TERMS] = {0};
+  // an identical query earlier in the same pass (yrwi_share.h: its index among the pass's plans) or
+  // -1: this query joins nothing and ranks nothing, its hits and rows are the representative's
+  int32_t rep = -1;
 };
 
 

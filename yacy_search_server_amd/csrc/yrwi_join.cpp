@@ -796,7 +796,9 @@ int yrwi::run_join_phase(Lane* ctx, std::vector<Plan>& plans, yrwi_stats* st, Ti
   std::vector<int64_t> acc_g(nq, 0);  // global size of each query's accumulated container
   for (size_t qi = 0; qi < nq; qi++) {
     Plan& P = plans[qi];
-    if (P.empty) { P.cont = DList{nullptr, nullptr, nullptr, 0}; continue; }
+    // (a repeat of an earlier query of the pass, Plan::rep: no step, no chain, no exclusion -- its
+    // container stays empty here and the rank phase hands it its representative's)
+    if (P.empty || P.rep >= 0) { P.cont = DList{nullptr, nullptr, nullptr, 0}; continue; }
     P.cont = P.seq[0]->dl();  // (a single list under a url selection: restricted by pick_selections)
     acc_g[qi] = P.seq_ng[0];
   }

@@ -64,6 +64,37 @@ static void build_queries(RankPass& R) {
     Plan& P = R.plans[(size_t)qi];
     RankQ& Q = R.rq[(size_t)qi];
     std::memset(&Q, 0, sizeof(Q));
+    if (P.rep >= 0) {
+      // A repeat of an earlier query of the pass: no chunks, no pieces, no host table -- it is not
+      // normalised, scored or selected.  Its RankQ names the representative's container (key_at),
+      // upload_final gives it the representative's final list and rows, and k_emit / k_hit_rows
+      // write its own slots of the results.
+      const RankQ& Rq = R.rq[(size_t)P.rep];
+      Q.feat = Rq.feat;
+      Q.uid = Rq.uid;
+      Q.ekhi = Rq.ekhi;
+      Q.eklo = Rq.eklo;
+      Q.dkhi = Rq.dkhi;
+      Q.dklo = Rq.dklo;
+      Q.removed = Rq.removed;
+      Q.n = Rq.n;
+      Q.chunk_base = R.chunks;
+      R.chunk_base[(size_t)qi] = R.chunks;
+      Q.prof = Rq.prof;
+      Q.lang[0] = Rq.lang[0];
+      Q.lang[1] = Rq.lang[1];
+      Q.lang_ok = Rq.lang_ok;
+      Q.now_ms = Rq.now_ms;
+      Q.k = Rq.k;
+      Q.kout = Rq.kout;
+      Q.host_rec = Rq.host_rec;
+      R.slot_base[(size_t)qi] = R.nslots;
+      if (R.st) {  // per-query meaning: the rows of its result; no bytes, nobody read them again
+        R.st->joined += Q.n;
+        R.st->joined_shared += Q.n;
+      }
+      continue;
+    }
     Q.feat = P.cont.feat;
     Q.uid = P.cont.uid;
     Q.ekhi = P.cont.uid ? nullptr : P.cont.khi;
@@ -372,7 +403,9 @@ static int normalize(RankPass& R) {
   if (tm) tm->kreduce.push_back({sp, rmid});  // k_reduce alone: the population rocprofv3 averages
   if (R.st) {
     R.st->n_rank_passes++;
-    for (const RankQ& Q : R.rq) {
+    for (int qi = 0; qi < R.nq; qi++) {
+      const RankQ& Q = R.rq[(size_t)qi];
+      if (R.plans[(size_t)qi].rep >= 0) continue;  // a repeat: nothing of it is reduced or scored
       if (!Q.pieces) R.st->bytes_reduce += (int64_t)FEAT_BYTES * Q.n + (Q.removed ? Q.n : 0);
       R.st->bytes_score += (int64_t)FEAT_BYTES * Q.n + (Q.removed ? Q.n : 0);
     }
@@ -567,8 +600,7 @@ static int bind_dest(RankPass& R, RankDest* D) {
 // The final-list pointers go up.  Rows asked for: k_pull (doubledom, sharded) leaves its hits in
 // device memory, where k_hit_rows reads them, looks their rows up and forwards them to the pinned
 // destination.
-static int upload_final(RankPass& R, RankDest* D, const std::vector<const Cand*>& fptr,
-                        const std::vector<const int32_t*>& fcnt) {
+static int upload_final(RankPass& R, RankDest* D, std::vector<const Cand*>& fptr, std::vector<const int32_t*>& fcnt) {
   Lane* ctx = R.ctx;
   const int nq = R.nq;
   const Cand** d_fptr = arena_alloc<const Cand*>(ctx, nq);
@@ -576,6 +608,13 @@ static int upload_final(RankPass& R, RankDest* D, const std::vector<const Cand*>
   if (!d_fptr || !d_fcnt) return ctx->fail(YRWI_E_NOMEM, "arena");
   R.S.d_final = d_fptr;
   R.S.d_final_cnt = d_fcnt;
+  // a repeat's final list is its representative's (an earlier query of the pass)
+  for (int qi = 0; qi < nq; qi++) {
+    const int32_t r = R.plans[(size_t)qi].rep;
+    if (r < 0) continue;
+    fptr[(size_t)qi] = fptr[(size_t)r];
+    fcnt[(size_t)qi] = fcnt[(size_t)r];
+  }
   if (!D->h_rows) return upload(ctx, d_fptr, fptr, d_fcnt, fcnt) ? YRWI_E_HIP : 0;
   std::vector<HitRowQ> hq((size_t)nq);
   int own_shift = -1;
@@ -586,7 +625,8 @@ static int upload_final(RankPass& R, RankDest* D, const std::vector<const Cand*>
   for (int qi = 0; qi < nq; qi++) {
     const Plan& P = R.plans[(size_t)qi];
     HitRowQ& H = hq[(size_t)qi];
-    H.rows = P.empty ? nullptr : P.cont.rows;
+    const Plan& C = P.rep >= 0 ? R.plans[(size_t)P.rep] : P;  // whose container the hits were ranked from
+    H.rows = C.empty ? nullptr : C.cont.rows;
     H.now_ms = P.now_ms;
     H.src = R.shx || R.rq[(size_t)qi].doubledom ? HR_HITS : HR_CAND;
     H.own_shift = own_shift;
