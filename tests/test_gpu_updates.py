@@ -242,20 +242,47 @@ def test_policies(tiny, monkeypatch):
 
 
 # ------------------------------------------------------------------ 4: remove
-def test_remove(tiny, monkeypatch):
+def _set_chunk(monkeypatch, chunk):
+    """rows compacted at a time (None: the default, one chunk on this corpus)"""
+    if chunk is None:
+        monkeypatch.delenv("YRWI_RM_CHUNK", raising=False)
+    else:
+        monkeypatch.setenv("YRWI_RM_CHUNK", str(chunk))
+
+
+def _state(ix, lists, qs, st):
+    """what a removal leaves behind: every list, the url ids, the query hits, the counted stats"""
+    return ({t: ix.get_list(t).tobytes() for t in lists}, ix.check_url_ids(), _hits(ix, qs),
+            {k: st[k] for k in ("terms", "emptied_terms", "removed")})
+
+
+def _remove_steps(tiny, monkeypatch):
+    """the removals of test_remove, each checked against the reference; -> the state after each"""
     cfg, idx, lists, qs = tiny
     by_size = sorted(lists, key=lambda h: len(lists[h]))
     small, mid, big = by_size[0], by_size[len(by_size) // 2], by_size[-1]
+    # absent urls, duplicate urls, a duplicated term, an unknown term, a list emptied
+    urls = [bytes(r[:12]) for r in lists[small]] + [bytes(lists[mid][0, :12])] * 2 + [_url(5), _url(5)]
+    urls += [bytes(r[:12]) for r in lists[big][::5]]
+    # a named list that holds none of the urls
+    gone = set(urls)
+    quiet = next(t for t in by_size[1:] if not gone & {bytes(r[:12]) for r in lists[t]})
+    named = [small, mid, mid, big, quiet, _term(77)]
+    # on the reference alone: a list longer than 256 rows (a chunk of its own at YRWI_RM_CHUNK = 256)
+    # loses some but not all rows, a list is emptied, a named list loses nothing
+    ref, _ = ur.apply_remove(lists, urls, named)
+    assert len(lists[big]) > 256 and 0 < len(ref[big]) < len(lists[big])
+    assert small not in ref
+    assert ref[quiet] is lists[quiet] and quiet not in (small, mid, big)
+    states = []
     ix = _open(lists)
     try:
         ix.build_url_ids()
-        # absent urls, duplicate urls, a duplicated term, an unknown term, a list emptied
-        urls = [bytes(r[:12]) for r in lists[small]] + [bytes(lists[mid][0, :12])] * 2 + [_url(5), _url(5)]
-        urls += [bytes(r[:12]) for r in lists[big][::5]]
         n0 = ix.stats()[0]
-        cur, st = _remove(ix, lists, urls, [small, mid, mid, big, _term(77)])
+        cur, st = _remove(ix, lists, urls, named)
         assert st["emptied_terms"] >= 1 and ix.get_size(small) == 0 and ix.stats()[0] == n0 - st["emptied_terms"]
-        _verify(ix, cur, [small, mid, big], qs, monkeypatch)
+        _verify(ix, cur, [small, mid, big, quiet], qs, monkeypatch)
+        states.append(_state(ix, lists, qs, st))
         # Segment.removeAllUrlReferences: about 50 urls that occur in many lists, over the whole index
         count = {}
         for r in cur.values():
@@ -266,11 +293,50 @@ def test_remove(tiny, monkeypatch):
         cur2, st = _remove(ix, cur, common, None)
         assert st["removed"] == sum(count[x] for x in common)
         _verify(ix, cur2, list(cur), qs, monkeypatch)
+        states.append(_state(ix, lists, qs, st))
         # nothing to remove: nothing changes
         _, st = _remove(ix, cur2, common, None)
         assert st["removed"] == 0 and st["terms"] == 0
+        states.append(_state(ix, lists, qs, st))
     finally:
         ix.close()
+    return states
+
+
+def test_remove(tiny, monkeypatch):
+    _remove_steps(tiny, monkeypatch)
+
+
+def test_remove_at_chunk_sizes(tiny, monkeypatch):
+    """the compaction in one chunk, in chunks of 256 rows (every longer list a chunk of its own) and
+    of 4096 rows (runs of whole lists): the same lists, url ids, hits and counts"""
+    states = {}
+    for chunk in (None, 256, 4096):
+        _set_chunk(monkeypatch, chunk)
+        states[chunk] = _remove_steps(tiny, monkeypatch)
+    assert states[256] == states[None]
+    assert states[4096] == states[None]
+
+
+def test_more_chunks_more_launches(tiny, monkeypatch):
+    cfg, idx, lists, qs = tiny
+    big = max(lists, key=lambda h: len(lists[h]))
+    urls = [bytes(r[:12]) for r in lists[big][::5]]
+    ref = ur.apply_remove(lists, urls, None)
+    shrunk = [t for t in lists if t in ref[0] and len(ref[0][t]) < len(lists[t])]
+    assert len(shrunk) >= 2 and sum(len(lists[t]) for t in shrunk) > 256  # more than one chunk of 256 rows
+    st = {}
+    for chunk in (None, 256):
+        _set_chunk(monkeypatch, chunk)
+        ix = _open(lists)
+        try:
+            got = ix.remove_postings(urls, None)
+            assert {k: got[k] for k in STAT_KEYS} == ref[1], (got, ref[1])
+            st[chunk] = got
+        finally:
+            ix.close()
+    assert st[256]["launches"] > st[None]["launches"], st
+    assert st[256]["syncs"] == st[None]["syncs"], st  # no host wait per chunk
 
 
 # ------------------------------------------------------------------ 5: small updates stay incremental

@@ -11,8 +11,8 @@
 // k_dht_pack then writes the output, which is the cells' rows one after another, in windows of
 // YRWI_DHT_WINDOW_ROWS rows into a device window; a copy lands the window in the caller's buffer
 // (pinned and 8-byte aligned) or in a pinned window the host copies from, while the next window
-// is packed (two device and two pinned windows, shared with yrwi_dump_heap).  Launches and host
-// waits follow the number of windows, never the number of terms.
+// is packed (run_windows, yrwi_host.h).  Launches and host waits follow the number of windows,
+// never the number of terms.
 //
 // k_dht_pack: a workgroup takes a 16 KiB slice of the window, finds the cells holding the slice's
 // first and last row by binary search of the offsets (the last cell with off <= row: runs of
@@ -28,6 +28,7 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include "yrwi_device.h"
 #include "yrwi_host.h"
 
 using namespace yrwi;
@@ -49,20 +50,6 @@ struct DhtJob {  // one selected list
   int64_t n;
   int64_t pad;
 };
-
-// the row pointers come out of the job table: typed as global memory they load with global
-// instead of flat loads
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-#ifdef __HIP_DEVICE_COMPILE__
-typedef u32x4 __attribute__((address_space(1))) gmem_u4;
-typedef u32x2 __attribute__((address_space(1))) gmem_u2;
-typedef uint64_t __attribute__((address_space(1))) gmem_u64;
-#else
-typedef uint64_t gmem_u64;
-typedef u32x4 gmem_u4;
-typedef u32x2 gmem_u2;
-#endif
 
 // Cell (p, j), index p * T + j: srow = the first row of list j whose key's top e bits are >= p
 // (the lower bound of p << (64 - e) in khi), cnt = its rows in partition p.  cnt has ncell + 1
@@ -102,15 +89,6 @@ __global__ __launch_bounds__(256) void k_dht_bounds(const DhtJob* __restrict__ j
   cnt[c] = b[1] - b[0];
 }
 
-// last c in [lo, hi] with off[c] <= g (off[lo] <= g); off[c + 1] > g then, so the cell is not empty
-__device__ __forceinline__ int64_t cell_of(const int64_t* __restrict__ off, int64_t lo, int64_t hi, int64_t g) {
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 // the address of row g's byte 8 k, g a row of the non-empty cell c
 __device__ __forceinline__ const uint8_t* src_of(const DhtJob* __restrict__ jobs, const int32_t* __restrict__ srow,
                                                  const int64_t* __restrict__ off, int64_t T, int64_t c, int64_t g,
@@ -118,6 +96,8 @@ __device__ __forceinline__ const uint8_t* src_of(const DhtJob* __restrict__ jobs
   return jobs[c % T].rows + ((int64_t)srow[c] + (g - off[c])) * ROW + 8 * k;
 }
 
+// The cell of a row is the last one whose offset is <= the row (seg_of): the next offset is above
+// it then, so the cell is not empty.
 // Rows [w0, w0 + wrows) of the output -> dst (16-B aligned, room for 40 wrows rounded up to 16).
 // off: ncell + 1 row offsets, off[ncell] = the total; w0 + wrows <= total.
 __global__ __launch_bounds__(PACK_THREADS) void k_dht_pack(const int64_t* __restrict__ off,
@@ -129,8 +109,8 @@ __global__ __launch_bounds__(PACK_THREADS) void k_dht_pack(const int64_t* __rest
   const int64_t s0 = (int64_t)blockIdx.x * SLICE;  // slice start in the window (< wbytes by the grid)
   if (threadIdx.x == 0) {
     const int64_t last = (s0 + SLICE < wbytes ? s0 + SLICE : wbytes) - 1;
-    s_c[0] = cell_of(off, 0, ncell - 1, w0 + s0 / ROW);
-    s_c[1] = cell_of(off, s_c[0], ncell - 1, w0 + last / ROW);
+    s_c[0] = seg_of(off, (int64_t)0, ncell - 1, w0 + s0 / ROW);
+    s_c[1] = seg_of(off, s_c[0], ncell - 1, w0 + last / ROW);
   }
   __syncthreads();
   int64_t c = s_c[0];
@@ -144,7 +124,7 @@ __global__ __launch_bounds__(PACK_THREADS) void k_dht_pack(const int64_t* __rest
     const int k = (int)(u - 5 * r);
     const int64_t g = w0 + r;                 // the row of the piece's first half (< w0 + wrows)
     const int64_t g1 = k == 4 ? g + 1 : g;    // and of its second half
-    c = cell_of(off, c, chi, g);
+    c = seg_of(off, c, chi, g);
     const uint8_t* s = src_of(jobs, srow, off, T, c, g, k);
     u32x4 o;
     if (g1 < off[c + 1]) {
@@ -160,7 +140,7 @@ __global__ __launch_bounds__(PACK_THREADS) void k_dht_pack(const int64_t* __rest
       const u32x2 a = *(const gmem_u2*)(uintptr_t)s;
       u32x2 b = u32x2{0u, 0u};
       if (g1 < w0 + wrows) {  // a row of this slice: its cell is at most chi
-        const int64_t c1 = cell_of(off, c + 1, chi, g1);
+        const int64_t c1 = seg_of(off, c + 1, chi, g1);
         b = *(const gmem_u2*)(uintptr_t)src_of(jobs, srow, off, T, c1, g1, 0);
       }
       o = u32x4{a.x, a.y, b.x, b.y};
@@ -204,14 +184,9 @@ extern "C" int yrwi_dht_select(yrwi_ctx* ctx, const uint8_t start[12], const uin
   yrwi_dht_stats S;
   std::memset(&S, 0, sizeof(S));
   if (st) std::memset(st, 0, sizeof(*st));
-  hipSetDevice(ctx->device);
-  drain(ctx);  // like yrwi_put_list: no batch in flight
   // ---- selectContainers: the non-empty lists in key order from the first term >= start
-  std::vector<std::pair<KeyT, const ListRec*>> all;
-  all.reserve(ctx->lists.size());
-  for (auto& kv : ctx->lists)
-    if (kv.second.n > 0) all.emplace_back(kv.first, &kv.second);
-  std::sort(all.begin(), all.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+  ListSel all;
+  if (int rc = select_lists(ctx, nullptr, 0, true, &all)) return rc;
   const size_t N = all.size();
   std::vector<size_t> sel;
   {
@@ -267,8 +242,6 @@ extern "C" int yrwi_dht_select(yrwi_ctx* ctx, const uint8_t start[12], const uin
   const int64_t W = window_rows();
   const int64_t nwin = (total + W - 1) / W;
   const size_t wneed = ((size_t)W * ROW + 255) & ~(size_t)255;
-  if (int rc = ctx->reserve_windows(wneed)) return rc;  // two device and two pinned, shared with yrwi_dump_heap
-  const size_t bufstep = ctx->dump_cap;
   DhtJob* d_jobs = arena_alloc<DhtJob>(L, T);
   int32_t* d_srow = arena_alloc<int32_t>(L, ncell);
   int64_t* d_cnt = arena_alloc<int64_t>(L, ncell + 1);
@@ -290,47 +263,27 @@ extern "C" int yrwi_dht_select(yrwi_ctx* ctx, const uint8_t start[12], const uin
   if (h_off[0] != 0 || h_off[ncell] != total) return ctx->fail(YRWI_E_HIP, "dht offsets do not add up to the selection");
   // ---- the rows, window by window
   const bool direct = ((uintptr_t)rows40_out & 7) == 0 && ctx->hostreg.contains(rows40_out, (size_t)total * ROW);
-  hipEvent_t done[2] = {L->event(), L->event()};
-  hipEvent_t k0[2] = {L->event(), L->event()}, k1[2] = {L->event(), L->event()};
-  // window i has landed: its pack time, and its rows to the caller's buffer if they were staged
-  auto land = [&](int64_t i) -> int {
-    const int k = (int)(i & 1);
-    HIPCHK(ctx, hipEventSynchronize(done[k]));
-    S.syncs++;
-    float msf = 0.f;
-    if (hipEventElapsedTime(&msf, k0[k], k1[k]) == hipSuccess) S.t_pack_ns += (int64_t)((double)msf * 1e6);
-    const int64_t len = std::min(W, total - i * W);
-    if (!direct) std::memcpy(rows40_out + (size_t)(i * W) * ROW, ctx->dump_host + (size_t)k * bufstep, (size_t)len * ROW);
-    return 0;
-  };
-  int rc = 0;
-  int64_t enq = 0;  // windows enqueued
-  for (int64_t i = 0; i < nwin && rc == 0; i++) {
-    const int k = (int)(i & 1);
-    const int64_t w0 = i * W, len = std::min(W, total - w0);
-    uint8_t* dwin = ctx->dump_dev + (size_t)k * bufstep;
-    uint8_t* hwin = direct ? rows40_out + (size_t)w0 * ROW : ctx->dump_host + (size_t)k * bufstep;
-    hipEventRecord(k0[k], L->stream);
-    hipLaunchKernelGGL(k_dht_pack, dim3((unsigned)((len * ROW + SLICE - 1) / SLICE)), dim3(PACK_THREADS), 0, L->stream,
-                       d_off, d_srow, d_jobs, ncell, T, w0, len, dwin);
-    hipEventRecord(k1[k], L->stream);
-    hipError_t he = hipGetLastError();
-    if (he == hipSuccess) he = hipMemcpyAsync(hwin, dwin, (size_t)len * ROW, hipMemcpyDeviceToHost, L->stream);
-    if (he == hipSuccess) he = hipEventRecord(done[k], L->stream);
-    if (he != hipSuccess) {
-      rc = ctx->fail(YRWI_E_HIP, std::string("dht window: ") + hipGetErrorString(he));
-      break;
-    }
-    enq = i + 1;
-    S.launches += 2;
-    if (i > 0) rc = land(i - 1);
-  }
-  if (rc == 0) rc = land(nwin - 1);
-  if (rc != 0) {
-    if (enq > 0) hipStreamSynchronize(L->stream);  // nothing of the call stays in flight
-    return rc;
-  }
-  S.windows = nwin;
+  WindowTally WT;
+  const int wrc = run_windows(
+      ctx, L, wneed, nwin, "dht", &WT,
+      [&](int64_t i, uint8_t* dwin) {
+        const int64_t w0 = i * W, len = std::min(W, total - w0);
+        hipLaunchKernelGGL(k_dht_pack, dim3((unsigned)((len * ROW + SLICE - 1) / SLICE)), dim3(PACK_THREADS), 0,
+                           L->stream, d_off, d_srow, d_jobs, ncell, T, w0, len, dwin);
+      },
+      [&](int64_t i, uint8_t* pinned, size_t* bytes) {
+        *bytes = (size_t)std::min(W, total - i * W) * ROW;
+        return direct ? rows40_out + (size_t)(i * W) * ROW : pinned;
+      },
+      [&](int64_t i, const uint8_t* p, size_t bytes) {  // staged rows to the caller's buffer
+        if (!direct) std::memcpy(rows40_out + (size_t)(i * W) * ROW, p, bytes);
+        return 0;
+      });
+  S.launches += WT.launches;
+  S.syncs += WT.syncs;
+  S.t_pack_ns = WT.t_pack_ns;
+  S.windows = WT.windows;
+  if (wrc) return wrc;
   for (int64_t j = 0; j < T; j++) key_chars(all[sel[(size_t)j]].first, terms12_out + (size_t)j * 12);
   std::memcpy(part_off, h_off, (size_t)(ncell + 1) * sizeof(int64_t));
   // ---- IndexCell.remove(termHash): the last row has landed; the bookkeeping of an emptied list

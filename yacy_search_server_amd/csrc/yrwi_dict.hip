@@ -19,6 +19,7 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include "yrwi_device.h"
 #include "yrwi_host.h"
 #include "yrwi_bitmap.h"
 
@@ -115,20 +116,6 @@ __global__ void k_dict_keys(const uint32_t* __restrict__ flag, const uint32_t* _
 
 unsigned nb(int64_t n) { return (unsigned)((n + 255) / 256); }
 
-// 72-bit key order: (hi, lo) lexicographic
-__device__ __forceinline__ bool key_less(uint64_t ah, uint8_t al, uint64_t bh, uint8_t bl) {
-  return ah < bh || (ah == bh && al < bl);
-}
-__device__ __forceinline__ int64_t dict_lower_bound(const uint64_t* __restrict__ dh, const uint8_t* __restrict__ dl,
-                                                    int64_t n, uint64_t h, uint8_t l) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (key_less(dh[mid], dl[mid], h, l)) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 // distinct sorted keys: key j (a run start) -> slot rank1[j] - 1
 __global__ void k_cand_compact(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ rank1,
                                const uint64_t* __restrict__ kh, const uint8_t* __restrict__ kl,
@@ -146,7 +133,7 @@ __global__ void k_dict_lookup(const uint64_t* __restrict__ ch, const uint8_t* __
                               uint32_t* __restrict__ ins, uint32_t* __restrict__ isnew) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
-  const int64_t p = dict_lower_bound(dh, dl, nd, ch[c], cl[c]);
+  const int64_t p = lb_key(dh, dl, 0, nd, ch[c], cl[c]);
   ins[c] = (uint32_t)p;
   isnew[c] = (p < nd && dh[p] == ch[c] && dl[p] == cl[c]) ? 0u : 1u;
 }
@@ -189,20 +176,12 @@ struct UidSeg {
   const uint64_t* khi;
   const uint8_t* klo;
 };
-__device__ __forceinline__ int seg_of(const int64_t* __restrict__ off, int nseg, int64_t i) {
-  int lo = 0, hi = nseg - 1;  // last segment with off <= i
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 // unchanged lists: ids shift by the new keys before them
 __global__ void k_uid_remap(const UidSeg* __restrict__ segs, const int64_t* __restrict__ off, int nseg, int64_t n,
                             const uint32_t* __restrict__ delta) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const int s = seg_of(off, nseg, i);
+  const int s = seg_of(off, 0, nseg - 1, i);
   uint32_t* u = segs[s].uid + (i - off[s]);
   *u += delta[*u];
 }
@@ -211,18 +190,18 @@ __global__ void k_uid_assign(const UidSeg* __restrict__ segs, const int64_t* __r
                              const uint64_t* __restrict__ dh, const uint8_t* __restrict__ dl, int64_t nd) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const int s = seg_of(off, nseg, i);
+  const int s = seg_of(off, 0, nseg - 1, i);
   const int64_t j = i - off[s];
-  segs[s].uid[j] = (uint32_t)dict_lower_bound(dh, dl, nd, segs[s].khi[j], segs[s].klo[j]);
+  segs[s].uid[j] = (uint32_t)lb_key(dh, dl, 0, nd, segs[s].khi[j], segs[s].klo[j]);
 }
 // consistency: every posting's id names its key, ids ascend within a list, the dictionary ascends
 __global__ void k_uid_check(const UidSeg* __restrict__ segs, const int64_t* __restrict__ off, int nseg, int64_t n,
                             const uint64_t* __restrict__ dh, const uint8_t* __restrict__ dl, int64_t nd,
                             unsigned long long* __restrict__ bad) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nd && i > 0 && !key_less(dh[i - 1], dl[i - 1], dh[i], dl[i])) atomicAdd(bad, 1ull);
+  if (i < nd && i > 0 && !key_lt(dh[i - 1], dl[i - 1], dh[i], dl[i])) atomicAdd(bad, 1ull);
   if (i >= n) return;
-  const int s = seg_of(off, nseg, i);
+  const int s = seg_of(off, 0, nseg - 1, i);
   const int64_t j = i - off[s];
   const uint32_t u = segs[s].uid[j];
   bool ok = (int64_t)u < nd && dh[u] == segs[s].khi[j] && dl[u] == segs[s].klo[j];
@@ -782,7 +761,7 @@ __global__ void k_host_stamp(const StampSeg* __restrict__ segs, const int64_t* _
                              const uint32_t* __restrict__ hid) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const int s = seg_of(off, nseg, i);
+  const int s = seg_of(off, 0, nseg - 1, i);
   const int64_t j = i - off[s];
   uint64_t* w3 = segs[s].feat + j * FEAT_WORDS + 3;
   *w3 = (*w3 & 0x3FFFFFFFFull) | (uint64_t)hid[segs[s].uid[j]] << 34;

@@ -7,10 +7,10 @@
 // of 40 B as stored].  Its image never exists in one piece: it is produced in fixed-size
 // windows of the byte stream.  One job table (the selected terms in key order: row pointer, n,
 // term hash, and the int64 file offset of every record, a prefix sum over 30 + 40 n) is uploaded
-// in one copy; k_dump_pack then writes one window's bytes into a device staging buffer, a copy
-// brings it to pinned memory, and the host writes window i - 1 to the file while window i is
-// packed and copied (two device and two pinned windows).  Launches follow the bytes and the
-// window size, never the number of terms; the host waits once per window plus a constant.
+// in one copy; k_dump_pack then writes one window's bytes into a device window, and the host
+// writes window i - 1 to the file while window i is packed and copied (run_windows,
+// yrwi_host.h).  Launches follow the bytes and the window size, never the number of terms; the
+// host waits once per window plus a constant.
 //
 // k_dump_pack: a workgroup takes a 16 KiB slice of the window, finds the record holding the
 // slice start by binary search of the offset table and walks on from there.  Every thread
@@ -29,6 +29,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include "yrwi_device.h"
 #include "yrwi_host.h"
 
 using namespace yrwi;
@@ -53,15 +54,6 @@ struct DumpJob {  // one record of the file
   uint32_t pad;
 };
 
-// the row pointers come out of the job table, so the compiler cannot know their address space:
-// typed as global memory they load with global instead of flat loads
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-#ifdef __HIP_DEVICE_COMPILE__
-typedef u32x4 __attribute__((address_space(1))) gmem_u4;
-#else
-typedef u32x4 gmem_u4;
-#endif
-
 // byte h (0 .. 29) of a record's reclen, key and export header
 __device__ __forceinline__ uint32_t hdr_byte(const DumpJob& J, int h, uint32_t days) {
   const uint32_t n = (uint32_t)J.n;
@@ -73,15 +65,6 @@ __device__ __forceinline__ uint32_t hdr_byte(const DumpJob& J, int h, uint32_t d
   return n >> (8 * (29 - h)) & 255u;                          // orderbound
 }
 
-// last j in [lo, hi] with off[j] <= c (off[lo] <= c)
-__device__ __forceinline__ int64_t rec_of(const int64_t* __restrict__ off, int64_t lo, int64_t hi, int64_t c) {
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= c) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 // Window [w0, w0 + wlen) of the file image -> dst (16-B aligned, room for wlen rounded up to 16).
 // off: nj + 1 record offsets (off[nj] = total, the file size); w0 is a multiple of 16.
 __global__ __launch_bounds__(PACK_THREADS) void k_dump_pack(const int64_t* __restrict__ off,
@@ -90,7 +73,7 @@ __global__ __launch_bounds__(PACK_THREADS) void k_dump_pack(const int64_t* __res
                                                             uint8_t* __restrict__ dst) {
   __shared__ int64_t s_j0;
   const int64_t s0 = (int64_t)blockIdx.x * SLICE;  // slice start in the window (< wlen by the grid)
-  if (threadIdx.x == 0) s_j0 = rec_of(off, 0, nj - 1, w0 + s0);
+  if (threadIdx.x == 0) s_j0 = seg_of(off, (int64_t)0, nj - 1, w0 + s0);
   __syncthreads();
   int64_t j = s_j0;
   const int64_t jhi = j + SLICE_RECS < nj - 1 ? j + SLICE_RECS : nj - 1;
@@ -99,7 +82,7 @@ __global__ __launch_bounds__(PACK_THREADS) void k_dump_pack(const int64_t* __res
     const int64_t ci = s0 + ((int64_t)it * PACK_THREADS + threadIdx.x) * PIECE;
     if (ci >= wlen) break;
     const int64_t c = w0 + ci;  // < total
-    j = rec_of(off, j, jhi, c);
+    j = seg_of(off, j, jhi, c);
     const int64_t r = c - off[j];
     uint4 o;
     if (r >= REC_HDR && c + PIECE <= off[j + 1]) {
@@ -205,31 +188,10 @@ extern "C" int yrwi_dump_heap(yrwi_ctx* ctx, const char* path, const uint8_t* te
   yrwi_dump_stats S;
   std::memset(&S, 0, sizeof(S));
   if (st) std::memset(st, 0, sizeof(*st));
-  // ---- the selection, each term once (checked before anything is written)
-  std::vector<KeyT> sel;
-  {
-    std::unordered_set<KeyT, KeyHash> seen;
-    for (int32_t i = 0; i < nterms; i++) {
-      KeyT tk;
-      if (!key_of(terms12 + (size_t)i * 12, &tk)) return ctx->fail(YRWI_E_HASH, "term hash is not well-formed Base64");
-      if (seen.insert(tk).second) sel.push_back(tk);
-    }
-  }
-  hipSetDevice(ctx->device);
-  drain(ctx);  // like yrwi_get_list: no batch in flight
-  // ---- job table: the non-empty selected lists in key order, offsets a prefix sum over 30 + 40 n
-  std::vector<std::pair<KeyT, const ListRec*>> recs;
-  if (nterms == 0) {
-    recs.reserve(ctx->lists.size());
-    for (auto& kv : ctx->lists)
-      if (kv.second.n > 0) recs.emplace_back(kv.first, &kv.second);
-  } else {
-    for (const KeyT& tk : sel) {
-      auto it = ctx->lists.find(tk);
-      if (it != ctx->lists.end() && it->second.n > 0) recs.emplace_back(tk, &it->second);
-    }
-  }
-  std::sort(recs.begin(), recs.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+  // ---- job table: the non-empty selected lists in key order (the selection is checked before
+  //      anything is written), offsets a prefix sum over 30 + 40 n
+  ListSel recs;
+  if (int rc = select_lists(ctx, terms12, nterms, true, &recs)) return rc;
   const int64_t nj = (int64_t)recs.size();
   std::vector<DumpJob> jobs((size_t)nj);
   std::vector<int64_t> off((size_t)nj + 1);
@@ -269,55 +231,31 @@ extern "C" int yrwi_dump_heap(yrwi_ctx* ctx, const char* path, const uint8_t* te
     Lane* L = ctx->lanes[0];
     if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
     S.syncs++;
-    // ---- two device and two pinned windows, allocated on the first dump and kept
-    if (int rc = ctx->reserve_windows((size_t)W)) return rc;
-    const size_t bufstep = ctx->dump_cap;
     int64_t* d_off = arena_alloc<int64_t>(L, nj + 1);
     DumpJob* d_jobs = arena_alloc<DumpJob>(L, nj);
     if (!d_off || !d_jobs) return ctx->fail(YRWI_E_NOMEM, "device allocation (dump job table)");
     if (int rc = upload(L, d_off, off, d_jobs, jobs)) return ctx->take(L, rc);
     S.launches++;
-    hipEvent_t done[2] = {L->event(), L->event()};
-    hipEvent_t k0[2] = {L->event(), L->event()}, k1[2] = {L->event(), L->event()};
-    // window i - 1 has landed in pinned memory: its pack time, then its bytes to the file
-    auto land = [&](int64_t i) -> int {
-      const int k = (int)(i & 1);
-      HIPCHK(ctx, hipEventSynchronize(done[k]));
-      S.syncs++;
-      float msf = 0.f;
-      if (hipEventElapsedTime(&msf, k0[k], k1[k]) == hipSuccess) S.t_pack_ns += (int64_t)((double)msf * 1e6);
-      const int64_t len = std::min(W, total - i * W);
-      if (write_all(F.fd, ctx->dump_host + (size_t)k * bufstep, (size_t)len) != 0) return io_fail(ctx, "cannot write", F.tmp);
-      return 0;
-    };
-    int rc = 0;
-    int64_t enq = 0;  // windows enqueued
-    for (int64_t i = 0; i < nwin && rc == 0; i++) {
-      const int k = (int)(i & 1);
-      const int64_t w0 = i * W, len = std::min(W, total - w0);
-      uint8_t* dwin = ctx->dump_dev + (size_t)k * bufstep;
-      hipEventRecord(k0[k], L->stream);
-      hipLaunchKernelGGL(k_dump_pack, dim3((unsigned)((len + SLICE - 1) / SLICE)), dim3(PACK_THREADS), 0, L->stream,
-                         d_off, d_jobs, nj, w0, len, total, days, dwin);
-      hipEventRecord(k1[k], L->stream);
-      hipError_t e = hipGetLastError();
-      if (e == hipSuccess)
-        e = hipMemcpyAsync(ctx->dump_host + (size_t)k * bufstep, dwin, (size_t)len, hipMemcpyDeviceToHost, L->stream);
-      if (e == hipSuccess) e = hipEventRecord(done[k], L->stream);
-      if (e != hipSuccess) {
-        rc = ctx->fail(YRWI_E_HIP, std::string("dump window: ") + hipGetErrorString(e));
-        break;
-      }
-      enq = i + 1;
-      S.launches += 2;
-      if (i > 0) rc = land(i - 1);
-    }
-    if (rc == 0) rc = land(nwin - 1);
-    if (rc != 0) {
-      if (enq > 0) hipStreamSynchronize(L->stream);  // nothing of the call stays in flight
-      return rc;
-    }
-    S.windows = nwin;
+    WindowTally T;
+    const int rc = run_windows(
+        ctx, L, (size_t)W, nwin, "dump", &T,
+        [&](int64_t i, uint8_t* dwin) {
+          const int64_t w0 = i * W, len = std::min(W, total - w0);
+          hipLaunchKernelGGL(k_dump_pack, dim3((unsigned)((len + SLICE - 1) / SLICE)), dim3(PACK_THREADS), 0, L->stream,
+                             d_off, d_jobs, nj, w0, len, total, days, dwin);
+        },
+        [&](int64_t i, uint8_t* pinned, size_t* bytes) {
+          *bytes = (size_t)std::min(W, total - i * W);
+          return pinned;
+        },
+        [&](int64_t, const uint8_t* p, size_t bytes) {  // a landed window's bytes to the file
+          return write_all(F.fd, p, bytes) != 0 ? io_fail(ctx, "cannot write", F.tmp) : 0;
+        });
+    S.launches += T.launches;
+    S.syncs += T.syncs;
+    S.t_pack_ns = T.t_pack_ns;
+    S.windows = T.windows;
+    if (rc) return rc;
   }
   if (F.commit() != 0) return io_fail(ctx, "cannot finish", F.path);
   S.t_total_ns =

@@ -402,8 +402,8 @@ extern "C" void yrwi_close(yrwi_ctx* ctx) {
   }
   ctx->local_blocks.clear();
   ctx->local_bytes = 0;
-  if (ctx->dump_dev) hipFree(ctx->dump_dev);
-  if (ctx->dump_host) hipHostFree(ctx->dump_host);
+  if (ctx->win_dev) hipFree(ctx->win_dev);
+  if (ctx->win_host) hipHostFree(ctx->win_host);
   if (ctx->host_key) hipFree(ctx->host_key);
   ctx->index_mem.release();
   if (ctx->uid_all) hipFree(ctx->uid_all);
@@ -1097,6 +1097,31 @@ extern "C" int yrwi_settle_scratch(yrwi_ctx* ctx) {
 // wait until no asynchronous batch is in flight (their statuses stay recorded)
 void yrwi::drain(CtxBase* ctx) {
   for (Lane* L : ctx->lanes) L->wait();
+}
+
+int yrwi::select_lists(CtxBase* ctx, const uint8_t* terms12, int32_t nterms, bool sorted, ListSel* sel) {
+  std::vector<KeyT> tks;
+  std::unordered_set<KeyT, KeyHash> seen;
+  for (int32_t i = 0; i < nterms; i++) {
+    KeyT tk;
+    if (!key_of(terms12 + (size_t)i * 12, &tk)) return ctx->fail(YRWI_E_HASH, "term hash is not well-formed Base64");
+    if (seen.insert(tk).second) tks.push_back(tk);
+  }
+  hipSetDevice(ctx->device);
+  drain(ctx);
+  sel->clear();
+  if (nterms == 0) {
+    sel->reserve(ctx->lists.size());
+    for (auto& kv : ctx->lists)
+      if (kv.second.n > 0) sel->emplace_back(kv.first, &kv.second);
+  } else {
+    for (const KeyT& tk : tks) {
+      auto it = ctx->lists.find(tk);
+      if (it != ctx->lists.end() && it->second.n > 0) sel->emplace_back(tk, &it->second);
+    }
+  }
+  if (sorted) std::sort(sel->begin(), sel->end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+  return 0;
 }
 
 // an authority profile in the batch (ReferenceOrder.cardinal, coeff_authority > 12)

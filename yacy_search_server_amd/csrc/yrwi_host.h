@@ -31,13 +31,14 @@ namespace yrwi {
 
 constexpr int64_t MAX_LIST = 53687091;  // RowSet.importRowSet: 2^31 bytes of 40-byte rows
 
-// Base64Order.enhancedCoder alphabet index (Base64Order.java:38,54), -1 if not in it
+// Base64Order.enhancedCoder's alphabet (Base64Order.java:38,54)
+inline constexpr char ALPHA[] = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789-_";
+// a character's index in it, -1 if not in it
 struct AhpTable {
   int8_t v[256];
   constexpr AhpTable() : v() {
-    const char* a = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789-_";
     for (int i = 0; i < 256; i++) v[i] = -1;
-    for (int i = 0; i < 64; i++) v[(uint8_t)a[i]] = (int8_t)i;
+    for (int i = 0; i < 64; i++) v[(uint8_t)ALPHA[i]] = (int8_t)i;
   }
 };
 inline constexpr AhpTable AHP_T{};
@@ -65,11 +66,10 @@ inline bool key_of(const uint8_t* h, KeyT* k) {
 
 // the 12 characters of a key (inverse of key_of)
 inline void key_chars(const KeyT& k, uint8_t* out) {
-  static const char* A = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789-_";
   const uint64_t x = k.hi >> 4;
-  for (int j = 0; j < 10; j++) out[j] = (uint8_t)A[(x >> (6 * (9 - j))) & 63];
-  out[10] = (uint8_t)A[((k.hi & 15) << 2) | (k.lo >> 6)];
-  out[11] = (uint8_t)A[k.lo & 63];
+  for (int j = 0; j < 10; j++) out[j] = (uint8_t)ALPHA[(x >> (6 * (9 - j))) & 63];
+  out[10] = (uint8_t)ALPHA[((k.hi & 15) << 2) | (k.lo >> 6)];
+  out[11] = (uint8_t)ALPHA[k.lo & 63];
 }
 
 // Java int arithmetic
@@ -475,29 +475,29 @@ struct CtxBase {
   };
   std::vector<LocalBlock*> local_blocks;
   size_t local_bytes = 0;  // of local_blocks
-  // yrwi_dump_heap (yrwi_dump.hip) and yrwi_dht_select (yrwi_dht.hip): two device and two pinned
-  // windows of dump_cap bytes each, allocated on first use and kept
-  uint8_t* dump_dev = nullptr;
-  uint8_t* dump_host = nullptr;
-  size_t dump_cap = 0;
+  // run_windows (yrwi_dump_heap, yrwi_dht_select): two device and two pinned windows of win_cap
+  // bytes each, allocated on first use and kept
+  uint8_t* win_dev = nullptr;
+  uint8_t* win_host = nullptr;
+  size_t win_cap = 0;
   // windows of at least `bytes` each (contents dropped on growth; nothing of them in flight)
   int reserve_windows(size_t bytes) {
-    if (dump_cap >= bytes) return 0;
+    if (win_cap >= bytes) return 0;
     note_realloc("staging windows", 4 * bytes);
-    if (dump_dev) hipFree(dump_dev);
-    if (dump_host) hipHostFree(dump_host);
-    dump_dev = dump_host = nullptr;
-    dump_cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&dump_dev), 2 * bytes) != hipSuccess) {
-      dump_dev = nullptr;
+    if (win_dev) hipFree(win_dev);
+    if (win_host) hipHostFree(win_host);
+    win_dev = win_host = nullptr;
+    win_cap = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&win_dev), 2 * bytes) != hipSuccess) {
+      win_dev = nullptr;
       return fail(YRWI_E_NOMEM, "device allocation (staging windows)");
     }
-    if (hipHostMalloc(reinterpret_cast<void**>(&dump_host), 2 * bytes, hipHostMallocDefault) != hipSuccess) {
-      hipFree(dump_dev);
-      dump_dev = dump_host = nullptr;
+    if (hipHostMalloc(reinterpret_cast<void**>(&win_host), 2 * bytes, hipHostMallocDefault) != hipSuccess) {
+      hipFree(win_dev);
+      win_dev = win_host = nullptr;
       return fail(YRWI_E_HIP, "pinned host allocation (staging windows)");
     }
-    dump_cap = bytes;
+    win_cap = bytes;
     return 0;
   }
 
@@ -656,6 +656,74 @@ inline int begin_pass(Lane* ctx) {
   ctx->probe_ratio = e ? std::max<int64_t>(1, atoll(e)) : (int64_t)8;
   const char* b = getenv("YRWI_BAND_ORDER");  // 0: job-order tile schedule (A/B measurements; same results)
   ctx->band_order = !(b && b[0] == '0');
+  return 0;
+}
+
+// ---- the lists an index-maintenance call works on (yrwi_host.cpp)
+using ListSel = std::vector<std::pair<KeyT, const ListRec*>>;
+// The non-empty lists among the nterms named ones, each once, in the caller's order; nterms == 0:
+// every non-empty list; sorted: in key order.  YRWI_E_HASH for a term hash that is not well formed,
+// before anything else; then sets the device and waits for the batches in flight (they read the
+// list table).
+int select_lists(CtxBase* ctx, const uint8_t* terms12, int32_t nterms, bool sorted, ListSel* sel);
+
+// ---- a byte stream produced on the device and landed on the host window by window
+struct WindowTally {  // what run_windows enqueued and waited for
+  int32_t launches = 0, syncs = 0;
+  int64_t windows = 0, t_pack_ns = 0;
+};
+
+// nwin windows of at most wbytes each through the context's two device and two pinned windows in
+// turn: window i is packed and copied while the host deals with window i - 1.
+//   pack(i, dwin)             enqueues on L->stream the launch that writes window i to the device window
+//   dest(i, pinned, &bytes)   window i's length and where its copy lands: `pinned`, or a place in a
+//                             pinned buffer of the caller's
+//   land(i, p, bytes)         window i has landed at p; non-zero: the call's error, the loop ends
+// Two launches (pack, copy) and one host wait per window; the pack kernels' time is summed from events.
+// On an error the stream is synchronised before returning: nothing of the call stays in flight.
+template <class Pack, class Dest, class Land>
+int run_windows(CtxBase* ctx, Lane* L, size_t wbytes, int64_t nwin, const char* what, WindowTally* T, Pack pack,
+                Dest dest, Land land) {
+  if (int rc = ctx->reserve_windows(wbytes)) return rc;
+  const size_t step = ctx->win_cap;
+  hipEvent_t done[2] = {L->event(), L->event()};
+  hipEvent_t k0[2] = {L->event(), L->event()}, k1[2] = {L->event(), L->event()};
+  uint8_t* hwin[2] = {nullptr, nullptr};
+  size_t len[2] = {0, 0};
+  auto landed = [&](int64_t i) -> int {
+    const int k = (int)(i & 1);
+    HIPCHK(ctx, hipEventSynchronize(done[k]));
+    T->syncs++;
+    float msf = 0.f;
+    if (hipEventElapsedTime(&msf, k0[k], k1[k]) == hipSuccess) T->t_pack_ns += (int64_t)((double)msf * 1e6);
+    return land(i, hwin[k], len[k]);
+  };
+  int rc = 0;
+  int64_t enq = 0;  // windows enqueued
+  for (int64_t i = 0; i < nwin && rc == 0; i++) {
+    const int k = (int)(i & 1);
+    uint8_t* dwin = ctx->win_dev + (size_t)k * step;
+    hwin[k] = dest(i, ctx->win_host + (size_t)k * step, &len[k]);
+    hipEventRecord(k0[k], L->stream);
+    pack(i, dwin);
+    hipEventRecord(k1[k], L->stream);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(hwin[k], dwin, len[k], hipMemcpyDeviceToHost, L->stream);
+    if (e == hipSuccess) e = hipEventRecord(done[k], L->stream);
+    if (e != hipSuccess) {
+      rc = ctx->fail(YRWI_E_HIP, std::string(what) + " window: " + hipGetErrorString(e));
+      break;
+    }
+    enq = i + 1;
+    T->launches += 2;
+    if (i > 0) rc = landed(i - 1);
+  }
+  if (rc == 0 && nwin > 0) rc = landed(nwin - 1);
+  if (rc != 0) {
+    if (enq > 0) hipStreamSynchronize(L->stream);
+    return rc;
+  }
+  T->windows = nwin;
   return 0;
 }
 

@@ -32,29 +32,12 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include "yrwi_device.h"
 #include "yrwi_host.h"
 
 using namespace yrwi;
 
 namespace {
-
-__device__ __forceinline__ int64_t lb_key(const uint64_t* __restrict__ kh, const uint8_t* __restrict__ kl, int64_t n,
-                                          uint64_t h, uint32_t l) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    const uint64_t mh = kh[mid];
-    if (mh < h || (mh == h && (uint32_t)kl[mid] < l)) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ void copy_row(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src) {
-  const uint64_t* s = reinterpret_cast<const uint64_t*>(src);  // rows are 8-byte aligned (40 B, 256 B bases)
-  uint64_t* d = reinterpret_cast<uint64_t*>(dst);
-#pragma unroll
-  for (int i = 0; i < 5; i++) d[i] = s[i];
-}
 
 // B rows: slot in A (lower bound) and whether B's key is absent from A (kept)
 __global__ void k_union_b(DList A, DList B, int64_t* __restrict__ lbA, int32_t* __restrict__ keep) {
@@ -62,7 +45,7 @@ __global__ void k_union_b(DList A, DList B, int64_t* __restrict__ lbA, int32_t* 
   if (j >= B.n) return;
   const uint64_t h = B.khi[j];
   const uint32_t l = B.klo[j];
-  const int64_t p = lb_key(A.khi, A.klo, A.n, h, l);
+  const int64_t p = lb_key(A.khi, A.klo, 0, A.n, h, l);
   lbA[j] = p;
   keep[j] = (p < A.n && A.khi[p] == h && (uint32_t)A.klo[p] == l) ? 0 : 1;
 }
@@ -74,7 +57,7 @@ __global__ void k_union_a(DList A, DList B, const int64_t* __restrict__ rB, uint
   if (i >= A.n) return;
   const uint64_t h = A.khi[i];
   const uint32_t l = A.klo[i];
-  const int64_t pos = i + rB[lb_key(B.khi, B.klo, B.n, h, l)];
+  const int64_t pos = i + rB[lb_key(B.khi, B.klo, 0, B.n, h, l)];
   okh[pos] = h;
   okl[pos] = (uint8_t)l;
   copy_row(orows + pos * YRWI_ROW_BYTES, A.rows + i * YRWI_ROW_BYTES);

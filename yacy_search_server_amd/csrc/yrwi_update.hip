@@ -15,7 +15,7 @@
 //
 // yrwi_remove_postings: k_rm_count looks every key of the named lists up in the sorted,
 // deduplicated url set and counts the hits per list (read back once); only the lists that
-// lose rows are flagged, scanned and compacted (k_rm_flag, one scan, k_rm_place).
+// lose rows are compacted (compact_commit below, flagged by k_rm_flag).
 //
 // yrwi_remove_hosts / yrwi_count_hosts: the predicate is the host hash, url-hash characters
 // 6..11 = the low 36 bits of the 72-bit key every list stores next to its rows (host36), so
@@ -30,12 +30,17 @@
 // lists ascend: it sums a list's hits over its steps and adds them on leaving the list); per host
 // (count_hosts only) in LDS per workgroup and then one global atomic per hit slot per
 // workgroup when the set is in LDS, else one global atomic per slot per wave.  The per-list
-// counts are read back once.  The lists that lose rows are compacted in chunks: runs of whole
-// lists of at most YRWI_RM_CHUNK rows in all (environment, read per call, at least 256,
-// default 2^26; a longer list is a chunk of its own), each flag -> scan -> place (k_host_flag,
-// one scan, k_rm_place) in the scratch of the chunk before it, 12 B per row of the largest
-// chunk, with no host wait between chunks: launches and syncs depend on the number of chunks
-// alone, and nothing stops at 2^31 postings.
+// counts are read back once; the lists that lose rows are compacted (compact_commit, flagged by
+// k_host_flag).
+//
+// compact_commit, the second half of both removals: from the per-list removed counts it plans the
+// lists that lose rows (an emptied list needs no compaction), takes their new lists from index
+// memory and compacts them in chunks: runs of whole lists of at most YRWI_RM_CHUNK rows in all
+// (environment, read per call, at least 256, default 2^26; a longer list is a chunk of its own),
+// each flag -> scan -> place (the caller's flag kernel, one scan, k_rm_place) in the scratch of
+// the chunk before it, 12 B per row of the largest chunk, with no host wait between chunks:
+// launches and syncs depend on the number of chunks alone, and nothing stops at 2^31 postings.
+// Then the bookkeeping of every list that lost rows.
 //
 // yrwi_host_census: which hosts the selected lists hold and how many postings each, the index-wide
 // form of the per-container host counts of ReferenceOrder.doms (UNVERIFIED against a reference
@@ -60,6 +65,7 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include "yrwi_device.h"
 #include "yrwi_host.h"
 
 using namespace yrwi;
@@ -90,36 +96,6 @@ struct RmJob {
   uint8_t* oklo;
   uint8_t* orows;
 };
-
-__device__ __forceinline__ bool key_lt(uint64_t ah, uint32_t al, uint64_t bh, uint32_t bl) {
-  return ah < bh || (ah == bh && al < bl);
-}
-
-__device__ __forceinline__ int64_t lb_key(const uint64_t* __restrict__ kh, const uint8_t* __restrict__ kl, int64_t lo,
-                                          int64_t hi, uint64_t h, uint32_t l) {
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (key_lt(kh[mid], kl[mid], h, l)) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// last segment whose offset is <= i
-__device__ __forceinline__ int seg_of(const int64_t* __restrict__ off, int nseg, int64_t i) {
-  int lo = 0, hi = nseg - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ void copy_row(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src) {
-  const uint64_t* s = reinterpret_cast<const uint64_t*>(src);  // rows are 8-byte aligned (40 B, 256 B bases)
-  uint64_t* d = reinterpret_cast<uint64_t*>(dst);
-#pragma unroll
-  for (int i = 0; i < 5; i++) d[i] = s[i];
-}
 
 __device__ __forceinline__ uint64_t shfl64(uint64_t v, int lane) {
   const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, lane, 64);
@@ -235,7 +211,7 @@ __global__ __launch_bounds__(256) void k_upd_old(const UpdJob* __restrict__ jobs
   const uint8_t* srcp = nullptr;
   uint8_t* dstp = nullptr;
   if (i < total) {
-    const int c = seg_of(aoff, ncj, i);
+    const int c = seg_of(aoff, 0, ncj - 1, i);
     const UpdJob J = jobs[cj[c]];
     const int64_t k = i - aoff[c];
     const uint64_t h = J.akhi[k];
@@ -281,17 +257,19 @@ __global__ void k_rm_count(const RmJob* __restrict__ jobs, const int64_t* __rest
                            unsigned long long* __restrict__ jrem) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
-  const int c = seg_of(off, nj, i);
+  const int c = seg_of(off, 0, nj - 1, i);
   const int64_t k = i - off[c];
   if (in_set(ukh, ukl, nu, jobs[c].khi[k], jobs[c].klo[k])) atomicAdd(&jrem[c], 1ull);
 }
 
+// keep[i] = posting i of the chunk's flattened lists stays; keep[total] = 0 (the scan's last element)
 __global__ void k_rm_flag(const RmJob* __restrict__ jobs, const int64_t* __restrict__ off, int nj, int64_t total,
                           const uint64_t* __restrict__ ukh, const uint8_t* __restrict__ ukl, int64_t nu,
                           int32_t* __restrict__ keep) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) keep[total] = 0;
   if (i >= total) return;
-  const int c = seg_of(off, nj, i);
+  const int c = seg_of(off, 0, nj - 1, i);
   const int64_t k = i - off[c];
   keep[i] = in_set(ukh, ukl, nu, jobs[c].khi[k], jobs[c].klo[k]) ? 0 : 1;
 }
@@ -303,7 +281,7 @@ __global__ __launch_bounds__(256) void k_rm_place(const RmJob* __restrict__ jobs
   const uint8_t* srcp = nullptr;
   uint8_t* dstp = nullptr;
   if (i < total && keep[i]) {
-    const int c = seg_of(off, nj, i);
+    const int c = seg_of(off, 0, nj - 1, i);
     const RmJob J = jobs[c];
     const int64_t k = i - off[c];
     const int64_t pos = kx[i] - kx[off[c]];
@@ -316,8 +294,6 @@ __global__ __launch_bounds__(256) void k_rm_place(const RmJob* __restrict__ jobs
 }
 
 // ---------------------------------------------------------------- hosts
-// url-hash chars 6..11 (the host hash) = the key's low 36 bits (key_host36, yrwi_kernels.hip)
-__device__ __forceinline__ uint64_t host36(uint64_t hi, uint32_t lo) { return ((hi & 0xFFFFFFFull) << 8) | (lo & 0xFFu); }
 
 // slot of h in the ascending set hs[0, nh), -1: not in it
 __device__ __forceinline__ int host_slot(const uint64_t* __restrict__ hs, int nh, uint64_t h) {
@@ -342,7 +318,8 @@ struct SegCursor {
 __device__ __forceinline__ void seg_seek(SegCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
                                          int nj, int64_t total, int64_t i) {
   if (i < s.hi) return;
-  s.c += 1 + seg_of(off + s.c + 1, nj - s.c - 1, i);  // (i < total: a list above c holds it)
+  const int above = nj - s.c - 1;  // lists above c (i < total: one of them holds it)
+  s.c += 1 + seg_of(off + s.c + 1, 0, above - 1, i);
   s.lo = off[s.c];
   s.hi = s.c + 1 < nj ? off[s.c + 1] : total;
   s.kh = jobs[s.c].khi;
@@ -520,6 +497,116 @@ void put_stats(yrwi_update_stats* st, const yrwi_update_stats& S, const Tally& T
   *st = S;
   st->launches = T.launches;
   st->syncs = T.syncs;
+}
+
+// ---- what the removals, the host counts and the census start from: the selected lists, flattened
+struct RmTable {
+  std::vector<KeyT> jkey;
+  std::vector<RmJob> jobs;
+  std::vector<int64_t> off;  // list j's first posting among the flattened ones
+  int64_t total = 0;
+};
+
+void rm_table(const ListSel& sel, RmTable* t) {
+  for (const auto& s : sel) {
+    const ListRec& R = *s.second;
+    t->jkey.push_back(s.first);
+    t->jobs.push_back(RmJob{R.khi, R.klo, R.rows, R.n, nullptr, nullptr, nullptr});
+    t->off.push_back(t->total);
+    t->total += R.n;
+  }
+}
+
+// rows compacted at a time: YRWI_RM_CHUNK, read per call (tests force chunk boundaries with it)
+int64_t rm_chunk() {
+  const char* e = getenv("YRWI_RM_CHUNK");
+  const int64_t v = e ? atoll(e) : RM_CHUNK_DEFAULT;
+  return std::min<int64_t>(std::max<int64_t>(v, 256), (int64_t)INT32_MAX - 1);
+}
+
+// List j of t loses rem[j] postings (counted by the caller's marking pass): the lists that lose
+// some but not all are compacted into new lists from index memory, in chunks of whole lists, and
+// every list that lost rows is committed to the context.  flag(jobs, off, nj, n, keep) enqueues
+// the caller's flag kernel for one chunk (keep[i] = posting i stays, keep[n] = 0).  One upload,
+// three launches per chunk and one wait; none of them if no list needs compaction.
+template <class Flag>
+int compact_commit(yrwi_ctx* ctx, Lane* L, RmTable& t, const std::vector<int64_t>& rem, const char* nomem, Flag flag,
+                   yrwi_update_stats* S, Tally* T) {
+  const int nj = (int)t.jobs.size();
+  std::vector<int> lose;
+  std::vector<RmJob> cjobs;
+  std::vector<int64_t> coff;            // offsets within the list's chunk
+  std::vector<std::pair<int, int>> ch;  // chunks: [first, last) of cjobs
+  const int64_t cap = rm_chunk();
+  int64_t ctotal = 0, maxc = 0;
+  for (int j = 0; j < nj; j++) {
+    if (rem[(size_t)j] == 0) continue;
+    lose.push_back(j);
+    if (rem[(size_t)j] == t.jobs[(size_t)j].n) continue;
+    RmJob& J = t.jobs[(size_t)j];
+    const size_t nn = (size_t)(J.n - rem[(size_t)j]);
+    J.orows = ctx->index_mem.alloc(nn * 40);
+    J.okhi = reinterpret_cast<uint64_t*>(ctx->index_mem.alloc(nn * 8));
+    J.oklo = ctx->index_mem.alloc(nn);
+    if (!J.orows || !J.okhi || !J.oklo) return ctx->fail(YRWI_E_NOMEM, "device index allocation failed");
+    if (ch.empty() || ctotal + J.n > cap) {  // (a list longer than the cap: a chunk of its own)
+      ch.push_back({(int)cjobs.size(), (int)cjobs.size()});
+      ctotal = 0;
+    }
+    cjobs.push_back(J);
+    coff.push_back(ctotal);
+    ctotal += J.n;
+    ch.back().second = (int)cjobs.size();
+    maxc = std::max(maxc, ctotal);
+  }
+  if (!ch.empty()) {
+    RmJob* d_cjobs = arena_alloc<RmJob>(L, (int64_t)cjobs.size());
+    int64_t* d_coff = arena_alloc<int64_t>(L, (int64_t)cjobs.size());
+    int32_t* keep = arena_alloc<int32_t>(L, maxc + 1);
+    int64_t* kx = arena_alloc<int64_t>(L, maxc + 1);
+    size_t tb = 0;
+    HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, keep, kx, (int)(maxc + 1), L->stream));
+    void* tmp = L->arena.alloc(tb);
+    if (!d_cjobs || !d_coff || !keep || !kx || !tmp) return ctx->fail(YRWI_E_NOMEM, nomem);
+    if (int rc = upload(L, d_cjobs, cjobs, d_coff, coff)) return ctx->take(L, rc);
+    T->launches++;
+    for (const auto& c : ch) {  // flag -> scan -> place, each chunk in the scratch of the one before
+      const int ncj = c.second - c.first;
+      const int64_t n = coff[(size_t)c.second - 1] + cjobs[(size_t)c.second - 1].n;
+      const RmJob* dj = d_cjobs + c.first;
+      const int64_t* doff = d_coff + c.first;
+      flag(dj, doff, ncj, n, keep);
+      size_t tbc = tb;
+      HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(tmp, tbc, keep, kx, (int)(n + 1), L->stream));
+      hipLaunchKernelGGL(k_rm_place, dim3(blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, keep, kx);
+      HIPCHK(ctx, hipGetLastError());
+      T->launches += 3;
+    }
+    HIPCHK(ctx, lane_sync(L));
+    T->syncs++;
+  }
+  // ---- bookkeeping: the removed postings are the dictionary churn
+  for (int j : lose) {
+    const RmJob& J = t.jobs[(size_t)j];
+    auto it = ctx->lists.find(t.jkey[(size_t)j]);
+    S->removed += rem[(size_t)j];
+    S->terms++;
+    ctx->npostings -= rem[(size_t)j];
+    if (rem[(size_t)j] == J.n) {  // as yrwi_put_list(n = 0) leaves things
+      index_changed(ctx, t.jkey[(size_t)j], J.n, false);
+      ctx->lists.erase(it);
+      S->emptied_terms++;
+    } else {
+      ListRec R;
+      R.khi = J.okhi;
+      R.klo = J.oklo;
+      R.rows = J.orows;
+      R.n = J.n - rem[(size_t)j];
+      it->second = R;
+      index_changed(ctx, t.jkey[(size_t)j], rem[(size_t)j], true);
+    }
+  }
+  return 0;
 }
 
 }  // namespace
@@ -712,36 +799,12 @@ extern "C" int yrwi_remove_postings(yrwi_ctx* ctx, const uint8_t* terms12, int32
     if (!key_of(urls12 + i * 12, &uk[(size_t)i])) return ctx->fail(YRWI_E_HASH, "url hash is not well-formed Base64");
   std::sort(uk.begin(), uk.end());
   uk.erase(std::unique(uk.begin(), uk.end()), uk.end());
-  std::vector<KeyT> tks;
-  {
-    std::unordered_set<KeyT, KeyHash> seen;
-    for (int32_t i = 0; i < nterms; i++) {
-      KeyT tk;
-      if (!key_of(terms12 + (size_t)i * 12, &tk)) return ctx->fail(YRWI_E_HASH, "term hash is not well-formed Base64");
-      if (seen.insert(tk).second) tks.push_back(tk);
-    }
-  }
-  hipSetDevice(ctx->device);
-  drain(ctx);
-  std::vector<KeyT> jkey;
-  std::vector<RmJob> jobs;
-  std::vector<int64_t> off;
-  int64_t total = 0;
-  auto take = [&](const KeyT& tk, const ListRec& R) {
-    if (R.n == 0) return;
-    jkey.push_back(tk);
-    jobs.push_back(RmJob{R.khi, R.klo, R.rows, R.n, nullptr, nullptr, nullptr});
-    off.push_back(total);
-    total += R.n;
-  };
-  if (nterms == 0) {
-    for (auto& kv : ctx->lists) take(kv.first, kv.second);
-  } else {
-    for (const KeyT& tk : tks) {
-      auto it = ctx->lists.find(tk);
-      if (it != ctx->lists.end()) take(tk, it->second);
-    }
-  }
+  ListSel sel;
+  if (int rc = select_lists(ctx, terms12, nterms, false, &sel)) return rc;
+  RmTable t;
+  rm_table(sel, &t);
+  const std::vector<RmJob>& jobs = t.jobs;
+  const int64_t total = t.total;
   if (uk.empty() || jobs.empty()) return 0;
   Lane* L = ctx->lanes[0];
   if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
@@ -761,7 +824,7 @@ extern "C" int yrwi_remove_postings(yrwi_ctx* ctx, const uint8_t* terms12, int32
   unsigned long long* jrem = arena_alloc<unsigned long long>(L, nj);
   if (!ukh || !ukl || !d_jobs || !d_off || !jrem) return ctx->fail(YRWI_E_NOMEM, "device allocation (remove_postings)");
   // ---- one marking pass over the named lists' keys, the per-list counts read back once
-  if (int rc = upload(L, ukh, h_ukh, ukl, h_ukl, d_jobs, jobs, d_off, off)) return ctx->take(L, rc);
+  if (int rc = upload(L, ukh, h_ukh, ukl, h_ukl, d_jobs, jobs, d_off, t.off)) return ctx->take(L, rc);
   HIPCHK(ctx, hipMemsetAsync(jrem, 0, (size_t)nj * 8, L->stream));
   hipLaunchKernelGGL(k_rm_count, dim3(blocks(total)), dim3(256), 0, L->stream, d_jobs, d_off, nj, total, ukh, ukl, nu,
                      jrem);
@@ -771,77 +834,12 @@ extern "C" int yrwi_remove_postings(yrwi_ctx* ctx, const uint8_t* terms12, int32
   T.launches += 4;
   HIPCHK(ctx, lane_sync(L));
   T.syncs++;
-  // ---- compaction of only the lists that lost rows (an emptied list needs none)
-  std::vector<int> lose;
-  std::vector<RmJob> cjobs;
-  std::vector<int64_t> coff;
-  std::vector<int64_t> rem((size_t)nj);
-  int64_t ctotal = 0;
-  for (int j = 0; j < nj; j++) {
-    rem[(size_t)j] = hrem[j];  // (the pinned landing buffer is reused below)
-    if (rem[(size_t)j] == 0) continue;
-    lose.push_back(j);
-    if (rem[(size_t)j] == jobs[(size_t)j].n) continue;
-    RmJob J = jobs[(size_t)j];
-    const size_t nn = (size_t)(J.n - rem[(size_t)j]);
-    J.orows = ctx->index_mem.alloc(nn * 40);
-    J.okhi = reinterpret_cast<uint64_t*>(ctx->index_mem.alloc(nn * 8));
-    J.oklo = ctx->index_mem.alloc(nn);
-    if (!J.orows || !J.okhi || !J.oklo) return ctx->fail(YRWI_E_NOMEM, "device index allocation failed");
-    jobs[(size_t)j] = J;
-    cjobs.push_back(J);
-    coff.push_back(ctotal);
-    ctotal += J.n;
-  }
-  if (lose.empty()) {
-    put_stats(st, S, T);
-    return 0;
-  }
-  if (!cjobs.empty()) {
-    if (ctotal > (int64_t)INT32_MAX - 1) return ctx->fail(YRWI_E_LIMIT, "more than 2^31 postings in the lists to compact");
-    const int ncj = (int)cjobs.size();
-    RmJob* d_cjobs = arena_alloc<RmJob>(L, ncj);
-    int64_t* d_coff = arena_alloc<int64_t>(L, ncj);
-    int32_t* keep = arena_alloc<int32_t>(L, ctotal + 1);
-    int64_t* kx = arena_alloc<int64_t>(L, ctotal + 1);
-    size_t tb = 0;
-    HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, keep, kx, (int)(ctotal + 1), L->stream));
-    void* tmp = L->arena.alloc(tb);
-    if (!d_cjobs || !d_coff || !keep || !kx || !tmp)
-      return ctx->fail(YRWI_E_NOMEM, "device allocation (remove_postings compaction)");
-    if (int rc = upload(L, d_cjobs, cjobs, d_coff, coff)) return ctx->take(L, rc);
-    HIPCHK(ctx, hipMemsetAsync(keep + ctotal, 0, 4, L->stream));
-    hipLaunchKernelGGL(k_rm_flag, dim3(blocks(ctotal)), dim3(256), 0, L->stream, d_cjobs, d_coff, ncj, ctotal, ukh, ukl,
-                       nu, keep);
-    HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(tmp, tb, keep, kx, (int)(ctotal + 1), L->stream));
-    hipLaunchKernelGGL(k_rm_place, dim3(blocks(ctotal)), dim3(256), 0, L->stream, d_cjobs, d_coff, ncj, ctotal, keep,
-                       kx);
-    HIPCHK(ctx, hipGetLastError());
-    T.launches += 5;
-    HIPCHK(ctx, lane_sync(L));
-    T.syncs++;
-  }
-  // ---- bookkeeping: the removed postings are the dictionary churn
-  for (int j : lose) {
-    const RmJob& J = jobs[(size_t)j];
-    auto it = ctx->lists.find(jkey[(size_t)j]);
-    S.removed += rem[(size_t)j];
-    S.terms++;
-    ctx->npostings -= rem[(size_t)j];
-    if (rem[(size_t)j] == J.n) {  // as yrwi_put_list(n = 0) leaves things
-      index_changed(ctx, jkey[(size_t)j], J.n, false);
-      ctx->lists.erase(it);
-      S.emptied_terms++;
-    } else {
-      ListRec R;
-      R.khi = J.okhi;
-      R.klo = J.oklo;
-      R.rows = J.orows;
-      R.n = J.n - rem[(size_t)j];
-      it->second = R;
-      index_changed(ctx, jkey[(size_t)j], rem[(size_t)j], true);
-    }
-  }
+  // ---- compaction of only the lists that lost rows, and the bookkeeping
+  const std::vector<int64_t> rem(hrem, hrem + nj);  // (the pinned landing buffer may be reused)
+  auto flag = [&](const RmJob* dj, const int64_t* doff, int ncj, int64_t n, int32_t* keep) {
+    hipLaunchKernelGGL(k_rm_flag, dim3(blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, ukh, ukl, nu, keep);
+  };
+  if (int rc = compact_commit(ctx, L, t, rem, "device allocation (remove_postings compaction)", flag, &S, &T)) return rc;
   put_stats(st, S, T);
   return 0;
 }
@@ -850,13 +848,9 @@ extern "C" int yrwi_remove_postings(yrwi_ctx* ctx, const uint8_t* terms12, int32
 namespace {
 
 // what both host calls start from: the host set and the selected lists, flattened
-struct HostPass {
+struct HostPass : RmTable {
   std::vector<uint64_t> in;  // the 36-bit key of every host given, in the caller's order
   std::vector<uint64_t> hk;  // the set: sorted, each once
-  std::vector<KeyT> jkey;
-  std::vector<RmJob> jobs;
-  std::vector<int64_t> off;
-  int64_t total = 0;
   uint64_t* d_hk = nullptr;
   RmJob* d_jobs = nullptr;
   int64_t* d_off = nullptr;
@@ -879,32 +873,9 @@ int host_select(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uin
   P->hk = P->in;
   std::sort(P->hk.begin(), P->hk.end());
   P->hk.erase(std::unique(P->hk.begin(), P->hk.end()), P->hk.end());
-  std::vector<KeyT> tks;
-  {
-    std::unordered_set<KeyT, KeyHash> seen;
-    for (int32_t i = 0; i < nterms; i++) {
-      KeyT tk;
-      if (!key_of(terms12 + (size_t)i * 12, &tk)) return ctx->fail(YRWI_E_HASH, "term hash is not well-formed Base64");
-      if (seen.insert(tk).second) tks.push_back(tk);
-    }
-  }
-  hipSetDevice(ctx->device);
-  drain(ctx);
-  auto take = [&](const KeyT& tk, const ListRec& R) {
-    if (R.n == 0) return;
-    P->jkey.push_back(tk);
-    P->jobs.push_back(RmJob{R.khi, R.klo, R.rows, R.n, nullptr, nullptr, nullptr});
-    P->off.push_back(P->total);
-    P->total += R.n;
-  };
-  if (nterms == 0) {
-    for (auto& kv : ctx->lists) take(kv.first, kv.second);
-  } else {
-    for (const KeyT& tk : tks) {
-      auto it = ctx->lists.find(tk);
-      if (it != ctx->lists.end()) take(tk, it->second);
-    }
-  }
+  ListSel sel;
+  if (int rc = select_lists(ctx, terms12, nterms, false, &sel)) return rc;
+  rm_table(sel, P);
   return 0;
 }
 
@@ -944,13 +915,6 @@ int host_mark(yrwi_ctx* ctx, Lane* L, HostPass* P, bool count, Tally* T) {
   return 0;
 }
 
-// rows compacted at a time: YRWI_RM_CHUNK, read per call (tests force chunk boundaries with it)
-int64_t rm_chunk() {
-  const char* e = getenv("YRWI_RM_CHUNK");
-  const int64_t v = e ? atoll(e) : RM_CHUNK_DEFAULT;
-  return std::min<int64_t>(std::max<int64_t>(v, 256), (int64_t)INT32_MAX - 1);
-}
-
 }  // namespace
 
 extern "C" int yrwi_count_hosts(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uint8_t* hosts6,
@@ -986,91 +950,14 @@ extern "C" int yrwi_remove_hosts(yrwi_ctx* ctx, const uint8_t* terms12, int32_t 
   if (P.hk.empty() || P.jobs.empty()) return 0;
   Lane* L = ctx->lanes[0];
   if (int rc = host_mark(ctx, L, &P, false, &T)) return rc;
-  const int nj = (int)P.jobs.size(), nh = (int)P.hk.size();
-  const std::vector<int64_t>& rem = P.res;
-  // ---- the lists that lose rows (an emptied list needs no compaction), in chunks of whole lists
-  std::vector<int> lose;
-  std::vector<RmJob> cjobs;
-  std::vector<int64_t> coff;            // offsets within the list's chunk
-  std::vector<std::pair<int, int>> ch;  // chunks: [first, last) of cjobs
-  const int64_t cap = rm_chunk();
-  int64_t ctotal = 0, maxc = 0;
-  for (int j = 0; j < nj; j++) {
-    if (rem[(size_t)j] == 0) continue;
-    lose.push_back(j);
-    if (rem[(size_t)j] == P.jobs[(size_t)j].n) continue;
-    RmJob J = P.jobs[(size_t)j];
-    const size_t nn = (size_t)(J.n - rem[(size_t)j]);
-    J.orows = ctx->index_mem.alloc(nn * 40);
-    J.okhi = reinterpret_cast<uint64_t*>(ctx->index_mem.alloc(nn * 8));
-    J.oklo = ctx->index_mem.alloc(nn);
-    if (!J.orows || !J.okhi || !J.oklo) return ctx->fail(YRWI_E_NOMEM, "device index allocation failed");
-    P.jobs[(size_t)j] = J;
-    if (ch.empty() || ctotal + J.n > cap) {  // (a list longer than the cap: a chunk of its own)
-      ch.push_back({(int)cjobs.size(), (int)cjobs.size()});
-      ctotal = 0;
-    }
-    cjobs.push_back(J);
-    coff.push_back(ctotal);
-    ctotal += J.n;
-    ch.back().second = (int)cjobs.size();
-    maxc = std::max(maxc, ctotal);
-  }
-  if (lose.empty()) {
-    put_stats(st, S, T);
-    return 0;
-  }
-  if (!ch.empty()) {
-    RmJob* d_cjobs = arena_alloc<RmJob>(L, (int64_t)cjobs.size());
-    int64_t* d_coff = arena_alloc<int64_t>(L, (int64_t)cjobs.size());
-    int32_t* keep = arena_alloc<int32_t>(L, maxc + 1);
-    int64_t* kx = arena_alloc<int64_t>(L, maxc + 1);
-    size_t tb = 0;
-    HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, keep, kx, (int)(maxc + 1), L->stream));
-    void* tmp = L->arena.alloc(tb);
-    if (!d_cjobs || !d_coff || !keep || !kx || !tmp)
-      return ctx->fail(YRWI_E_NOMEM, "device allocation (remove_hosts compaction)");
-    if (int rc = upload(L, d_cjobs, cjobs, d_coff, coff)) return ctx->take(L, rc);
-    T.launches++;
-    for (const auto& c : ch) {  // flag -> scan -> place, each chunk in the scratch of the one before
-      const int ncj = c.second - c.first;
-      const int64_t n = coff[(size_t)c.second - 1] + cjobs[(size_t)c.second - 1].n;
-      const RmJob* dj = d_cjobs + c.first;
-      const int64_t* doff = d_coff + c.first;
-      if (nh <= HOST_LDS_MAX)
-        hipLaunchKernelGGL((k_host_flag<true>), dim3(mark_blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, P.d_hk, nh, keep);
-      else
-        hipLaunchKernelGGL((k_host_flag<false>), dim3(mark_blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, P.d_hk, nh, keep);
-      size_t tbc = tb;
-      HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(tmp, tbc, keep, kx, (int)(n + 1), L->stream));
-      hipLaunchKernelGGL(k_rm_place, dim3(blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, keep, kx);
-      HIPCHK(ctx, hipGetLastError());
-      T.launches += 3;
-    }
-    HIPCHK(ctx, lane_sync(L));
-    T.syncs++;
-  }
-  // ---- bookkeeping, as yrwi_remove_postings: the removed postings are the dictionary churn
-  for (int j : lose) {
-    const RmJob& J = P.jobs[(size_t)j];
-    auto it = ctx->lists.find(P.jkey[(size_t)j]);
-    S.removed += rem[(size_t)j];
-    S.terms++;
-    ctx->npostings -= rem[(size_t)j];
-    if (rem[(size_t)j] == J.n) {
-      index_changed(ctx, P.jkey[(size_t)j], J.n, false);
-      ctx->lists.erase(it);
-      S.emptied_terms++;
-    } else {
-      ListRec R;
-      R.khi = J.okhi;
-      R.klo = J.oklo;
-      R.rows = J.orows;
-      R.n = J.n - rem[(size_t)j];
-      it->second = R;
-      index_changed(ctx, P.jkey[(size_t)j], rem[(size_t)j], true);
-    }
-  }
+  const int nh = (int)P.hk.size();
+  auto flag = [&](const RmJob* dj, const int64_t* doff, int ncj, int64_t n, int32_t* keep) {
+    if (nh <= HOST_LDS_MAX)
+      hipLaunchKernelGGL((k_host_flag<true>), dim3(mark_blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, P.d_hk, nh, keep);
+    else
+      hipLaunchKernelGGL((k_host_flag<false>), dim3(mark_blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, P.d_hk, nh, keep);
+  };
+  if (int rc = compact_commit(ctx, L, P, P.res, "device allocation (remove_hosts compaction)", flag, &S, &T)) return rc;
   put_stats(st, S, T);
   return 0;
 }
@@ -1362,9 +1249,8 @@ extern "C" int yrwi_host_census(yrwi_ctx* ctx, const uint8_t* terms12, int32_t n
   T.launches += 4;
   HIPCHK(ctx, lane_sync(L));
   T.syncs++;
-  static const char* A = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789-_";
   for (int64_t i = 0; i < nw; i++) {
-    for (int j = 0; j < 6; j++) hosts6_out[i * 6 + j] = (uint8_t)A[(hk[i] >> (6 * (5 - j))) & 63];
+    for (int j = 0; j < 6; j++) hosts6_out[i * 6 + j] = (uint8_t)ALPHA[(hk[i] >> (6 * (5 - j))) & 63];
     counts_out[i] = hc[i];
   }
   return finish(nw);
