@@ -33,26 +33,55 @@ def compress_index(container: Sequence[bytes], exclude: Optional[Sequence[bytes]
     return b"{" + b",".join(parts) + b"}"
 
 
+_BASE64 = frozenset(b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789-_")
+
+
 def decompress_index(ci: bytes, peerhash: bytes) -> Dict[bytes, Set[bytes]]:
     """WordReferenceFactory.decompressIndex (:125-155) for texts of the form
     compressIndex writes; url -> {peer}.  A text that is not of that form
-    raises ValueError (the reference reads past the end of its buffer then)."""
+    raises ValueError: inside a segment the loop parses, a url run that is not a
+    multiple of 6 characters (the reference reads past the end of its buffer
+    then) or a host or url byte outside the Base64 alphabet (no url hash).  What
+    lies behind the point where the loop stops is not looked at.  Linear in the
+    text: i walks the body [1, end)."""
     target: Dict[bytes, Set[bytes]] = {}
-    if len(ci) < 2 or ci[0:1] != b"{" or ci[-1:] != b"}":
+    ci = bytes(ci)
+    if len(ci) < 2 or ci[0] != 0x7B or ci[-1] != 0x7D:  # '{' ... '}'
         return target
-    ci = ci[1:-1]
-    while len(ci) >= 13 and ci[6:7] == b":":
-        dom = ci[0:6]
-        ci = ci[7:]
-        while ci and ci[0:1] != b",":
-            if len(ci) < 6:
+    i, end = 1, len(ci) - 1
+    while end - i >= 13 and ci[i + 6] == 0x3A:  # ':'
+        dom = ci[i:i + 6]
+        if not _BASE64.issuperset(dom):
+            raise ValueError("host is not Base64")
+        i += 7
+        while i < end and ci[i] != 0x2C:  # ','
+            if end - i < 6:
                 raise ValueError("url run is not a multiple of 6 characters")
-            url = ci[0:6] + dom
-            ci = ci[6:]
-            target.setdefault(url, set()).add(peerhash)
-        if ci[0:1] == b",":
-            ci = ci[1:]
+            pre = ci[i:i + 6]
+            if not _BASE64.issuperset(pre):
+                raise ValueError("url run is not Base64 (or not a multiple of 6 characters)")
+            i += 6
+            target.setdefault(pre + dom, set()).add(peerhash)
+        if i < end and ci[i] == 0x2C:
+            i += 1
     return target
+
+
+def join_order(sizes: Sequence[int]) -> List[int]:
+    """The fold order of SetTools.joinConstructive (:76-116) over maps of these
+    sizes (index = count, the position in the collection): the TreeMap's key is
+    Long.valueOf(size * 1000 + count), an int product that wraps as a Java int
+    (2,147,484 * 1000 is negative); an equal key replaces the earlier map.  An
+    empty map ends the join at once: []."""
+    order: Dict[int, int] = {}
+    for count, size in enumerate(sizes):
+        if size == 0:
+            return []
+        k = (size * 1000 + count) & 0xFFFFFFFF
+        if k >= 1 << 31:
+            k -= 1 << 32
+        order[k] = count
+    return [order[k] for k in sorted(order)]
 
 
 class SecondarySearch:
@@ -84,23 +113,15 @@ class SecondarySearch:
         maps ordered by Long.valueOf(size * 1000 + count) (an int product, TreeMap
         put: an equal key replaces the earlier map), folded smallest first by
         joinConstructiveByTest; Set values are not Strings, so the running
-        result's value is kept."""
-        order: Dict[int, Dict[bytes, Set[bytes]]] = {}
-        for count, m in enumerate(maps):
-            if not m:
-                return {}
-            k = (len(m) * 1000 + count) & 0xFFFFFFFF
-            if k >= 1 << 31:
-                k -= 1 << 32
-            order[k] = m
-        if not order:
+        result's value is kept.  The order is join_order's."""
+        fold = join_order([len(m) for m in maps])
+        if not fold:
             return {}
-        keys = sorted(order)
-        res = order[keys[0]]
-        for k in keys[1:]:
+        res = maps[fold[0]]
+        for w in fold[1:]:
             if not res:
                 break
-            nxt = order[k]
+            nxt = maps[w]
             res = {u: v for u, v in res.items() if u in nxt}
         return dict(res)
 

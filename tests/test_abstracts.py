@@ -7,7 +7,12 @@ SetTools.joinConstructive (:76-116) and prepareSecondarySearch (:117-196).
 
 CPU: the restatement (oracle/abstracts.py) against hand-derived values.
 GPU: yrwi_index_abstracts and yrwi_secondary_search against the restatement,
-byte-exact, on synthetic lists and abstracts from several peers."""
+byte-exact, on synthetic lists and abstracts from several peers.
+
+These inputs are random and well-formed.  The directed ones -- parser alignment,
+stop rules, refusals, fold order, the int wrap of `size * 1000`, capacities --
+are in tests/abstract_cases.py, shown on the CPU by tests/test_abstract_cases_ref.py
+and run on the device by tests/test_gpu_abstracts_adversarial.py."""
 
 import numpy as np
 import pytest
