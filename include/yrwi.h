@@ -390,7 +390,11 @@ int yrwi_hostx_selftest(const uint8_t id[128], int world, int rank, int64_t npar
  * (ArrayStack.java:182-229); otherwise `paths` is taken as oldest first.
  * Malformed records are skipped as HeapReader does; a term whose RowSet export
  * is inconsistent (importRowSet's SpaceExceededException) keeps only its RAM
- * list, as does a term with malformed rows; both are counted in dropped_terms. */
+ * list, as does a term with malformed rows (a url hash outside the alphabet, an
+ * empty language cell, or rows that claim to be sorted, orderbound >= size, and do
+ * not ascend strictly; rows past orderbound are sorted, the first of equal url
+ * hashes stays, and every one of them is checked); both are counted in
+ * dropped_terms. */
 #define YRWI_LOAD_ORDER_BY_NAME 1
 typedef struct yrwi_load_stats {
   int64_t files, records, free_records, bad_keys;

@@ -302,7 +302,9 @@ extern "C" int yrwi_load_heaps(yrwi_ctx* ctx, const char* const* paths, int32_t 
       if (ob < size) {  // unsorted tail: stable sort, first of equal url hashes kept
         std::vector<std::pair<KeyT, int64_t>> ks((size_t)size);
         for (int64_t i = 0; i < size; i++) {
-          if (!key_of(s.rows + i * 40, &ks[(size_t)i].first)) { poisoned = true; break; }
+          const uint8_t* r = s.rows + i * 40;
+          // (the language cell is checked here too: k_validate never sees a row that loses to an equal hash)
+          if (!key_of(r, &ks[(size_t)i].first) || (r[22] == 0 && r[23] == 0)) { poisoned = true; break; }
           ks[(size_t)i].second = i;
         }
         if (poisoned) break;
