@@ -650,9 +650,11 @@ typedef struct yrwi_event_info {
 /* Where each url entered the event's doublecheck set (SearchEvent.urlhashes,
  * :736-805: the first posting of the url that passed the constraints):
  * arrival[i] = its yrwi_event_add arrival (1 = the event's first), row[i] = its row
- * in that arrival's rows; arrival 0 = seeded by the filter's urlhashes; -1 = not in
- * the set.  A caller that keeps the arrivals' rows (GpuRWIStack) turns a pulled hit
- * back into its posting. */
+ * in that arrival's rows; arrival 0 (row 0) = seeded by the filter's urlhashes; -1
+ * (row -1) = not in the set.  The numbers count the arrivals that were applied: an
+ * empty arrival (n = 0) and a rejected one (rc != 0) use none up, as an empty
+ * yrwi_event_add_local join.  A caller that keeps the rows of the arrivals it got
+ * applied (GpuRWIStack) turns a pulled hit back into its posting. */
 int yrwi_event_source(yrwi_ctx* ctx, yrwi_event* ev, const uint8_t* urls12, int32_t n, int32_t* arrival,
                       int32_t* row);
 /* The stack in rwiStack order (best first), up to maxn entries. */

@@ -120,6 +120,7 @@ def _check_event(ix, arrivals, profile_fields=None, kw=None, k=100, language="en
         hits, info = ev.results()
     exp = ref.stack()[:k]
     assert [(h.urlhash, h.score) for h in hits] == exp
+    assert [h.tiebreak for h in hits] == [jl.bytearray_hashcode(u) for u, _ in exp]
     assert list(info.flagcount) == lf.flagcount
     assert info.postings_in == total
     assert info.admitted_remote == ref.remote_available

@@ -214,7 +214,8 @@ class SearchEvent:
 
     def source(self, urlhashes: Sequence[bytes]) -> List[Tuple[int, int]]:
         """(arrival, row) of each url's admitted posting (yrwi_event_source): arrival 1 is
-        the event's first add_rwis arrival, 0 a seeded doublecheck url, -1 not admitted."""
+        the event's first applied add_rwis arrival (empty and rejected arrivals are not
+        counted), 0 a seeded doublecheck url, -1 not admitted."""
         n = len(urlhashes)
         a = np.zeros(max(1, n), dtype=np.int32)
         r = np.zeros(max(1, n), dtype=np.int32)
