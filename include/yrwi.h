@@ -777,6 +777,53 @@ int yrwi_join_exclude(yrwi_ctx* ctx, const uint8_t* incl, int32_t nincl, const u
  * and filter unused): the joined and excluded container's rows, as
  * yrwi_join_exclude writes them. */
 int yrwi_term_search(yrwi_ctx* ctx, const yrwi_query_desc* q, uint8_t* rows40_out, int64_t cap_rows, int64_t* m);
+/* TermSearch.joined() of nq descriptors in one pass: the containers are planned and joined
+ * together (as yrwi_query_batch joins a batch), the rows an exclusion removes are dropped on the
+ * device, and what remains lands in rows40_out as one packed image.  row_off[0] = 0, the
+ * offsets never decrease, and the rows of query i are rows40_out + 40 row_off[i] up to
+ * row_off[i + 1]: byte for byte what yrwi_term_search(ctx, q + i, ...) writes for that
+ * descriptor (one include term: the rows as stored; two or more: the joined record re-encoded
+ * with that descriptor's own now_ms; exclusions, max_distance and urlselection honoured; k,
+ * profile, language and filter unused).  An absent include term, an empty join or a fully
+ * excluded container is an empty range, not an error; identical descriptors each get their
+ * own range.
+ *   Capacity: rows40_out == NULL only counts (cap_rows is ignored; row_off and st are filled;
+ * returns 0).  Otherwise, when row_off[nq] > cap_rows the call returns YRWI_E_ARG with row_off
+ * filled completely -- row_off[nq] is the capacity a retry needs -- and no byte of rows40_out
+ * written: the pack kernel compares the total with cap_rows on the device before it stores a
+ * row.  An upper bound that needs no extra pass: the sum over the queries of the smallest
+ * include list (yrwi_list_size) -- a conjunction is no longer than its shortest list.
+ *   Errors: planning errors (YRWI_E_HASH, the YRWI_E_UNSUPPORTED urlselection cases of
+ * yrwi_query_desc, YRWI_E_ARG, YRWI_E_NOMEM) return before anything is written -- row_off and
+ * rows40_out untouched -- and yrwi_last_error starts with "query <index>: ".  nq == 0 returns
+ * 0 with row_off[0] = 0; nq < 0, or a NULL q or row_off with nq > 0, returns YRWI_E_ARG.  A
+ * context of a shard group (world > 1) returns YRWI_E_UNSUPPORTED, as yrwi_event_add_local.
+ * Waits for the batches in flight and changes nothing in the context; scratch comes from
+ * lane 0's arena (no device allocation once it has its size).  st may be NULL.
+ *   Where the rows go: rows40_out from yrwi_host_alloc and 8-byte aligned is written by the
+ * pack kernel directly (st->direct = 1), as yrwi_dht_select and the hit rows of
+ * yrwi_query_batch_rows are.  Any other buffer: the rows are packed in device scratch and leave
+ * with one copy of exactly 40 row_off[nq] bytes (direct = 0).  Either way no row crosses PCIe
+ * twice and an excluded row never crosses it.
+ *   Shape of the call: after the join phase one upload, three kernels (k_local_count,
+ * k_tsb_scan, k_tsb_pack) and the readback of the nq + 1 offsets -- launches_tail = 5 and one
+ * host wait on the direct path; 6 and two waits on the pageable one (the copy is sized by the
+ * total, so it follows the first wait).  Neither depends on nq or on the list lengths, nor do
+ * the join phase's own waits (it writes its tile-group tables on the device, as for
+ * yrwi_event_add_local).  A call whose containers are all empty before the exclusion enqueues
+ * nothing after the join phase. */
+typedef struct yrwi_tsb_stats {
+  int64_t rows_joined, rows_out;   /* before / after exclusion, summed over the call (a chained fold excludes
+                                      within its join: those rows are gone from rows_joined too) */
+  int64_t bytes_h2d, bytes_d2h;    /* everything the call moved over PCIe */
+  int32_t launches_tail;           /* launches, copies, memsets enqueued after the join phase */
+  int32_t syncs;                   /* host waits on the device in the whole call */
+  int32_t direct;                  /* 1: rows were stored straight into rows40_out */
+  int64_t device_allocs;           /* yrwi_realloc_events of the call */
+  int64_t t_pack_ns, t_total_ns;   /* HIP events around the pack launches; wall time */
+} yrwi_tsb_stats;
+int yrwi_term_search_batch(yrwi_ctx* ctx, const yrwi_query_desc* q, int32_t nq, uint8_t* rows40_out,
+                           int64_t cap_rows, int64_t* row_off /* nq + 1 */, yrwi_tsb_stats* st);
 int yrwi_normalize_score(yrwi_ctx* ctx, const uint8_t* rows40, int64_t m, const yrwi_profile* prof,
                          const char* language, int64_t now_ms, int64_t* score_out);
 

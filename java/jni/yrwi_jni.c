@@ -232,6 +232,83 @@ JNIEXPORT jbyteArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_termSearch(JNIEnv
   return res;
 }
 
+/* TermSearch.joined() of nq queries in one pass (yrwi_term_search_batch).  The term and url
+ * hashes of all queries lie back to back in incl / excl / sel (12 bytes each), nincl[i] /
+ * nexcl[i] / nsel[i] of them belong to query i (sel and nsel may be NULL: no selection).
+ * Returns the packed rows of all queries (rowOff[nq] * 40 bytes) and fills rowOff (nq + 1):
+ * query i owns rows rowOff[i] .. rowOff[i + 1].  The buffer is sized by the sum of each
+ * query's smallest include list, so no counting call comes first.  NULL on error. */
+JNIEXPORT jbyteArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_termSearchBatch(
+    JNIEnv* env, jclass c, jlong ctx, jint nq, jbyteArray incl, jintArray nincl, jbyteArray excl, jintArray nexcl,
+    jbyteArray sel, jintArray nsel, jintArray maxd, jlongArray now, jlongArray rowOff) {
+  yrwi_ctx* x = (yrwi_ctx*)(intptr_t)ctx;
+  if (nq < 0 || !incl || !nincl || !excl || !nexcl || !maxd || !now || !rowOff || (sel && !nsel) ||
+      (*env)->GetArrayLength(env, nincl) < nq || (*env)->GetArrayLength(env, nexcl) < nq ||
+      (*env)->GetArrayLength(env, maxd) < nq || (*env)->GetArrayLength(env, now) < nq ||
+      (*env)->GetArrayLength(env, rowOff) < nq + 1 || (sel && (*env)->GetArrayLength(env, nsel) < nq))
+    return NULL;
+  jint* ni = (*env)->GetIntArrayElements(env, nincl, NULL);
+  jint* ne = (*env)->GetIntArrayElements(env, nexcl, NULL);
+  jint* ns = sel ? (*env)->GetIntArrayElements(env, nsel, NULL) : NULL;
+  jint* md = (*env)->GetIntArrayElements(env, maxd, NULL);
+  jlong* nw = (*env)->GetLongArrayElements(env, now, NULL);
+  int64_t ti = 0, te = 0, ts = 0;
+  int ok = 1;
+  for (jint i = 0; i < nq; i++) {
+    if (ni[i] < 0 || ne[i] < 0 || (ns && ns[i] < 0)) ok = 0;
+    ti += ni[i];
+    te += ne[i];
+    ts += ns ? ns[i] : 0;
+  }
+  uint8_t* ib = ok ? copy_in(env, incl, ti * 12) : NULL;
+  uint8_t* eb = ib ? copy_in(env, excl, te * 12) : NULL;
+  uint8_t* sb = eb && sel ? copy_in(env, sel, ts * 12) : NULL;
+  yrwi_query_desc* q = (yrwi_query_desc*)calloc((size_t)nq + 1, sizeof(yrwi_query_desc));
+  int64_t* off = (int64_t*)calloc((size_t)nq + 1, sizeof(int64_t));
+  uint8_t* out = NULL;
+  int rc = ib && eb && (!sel || sb) && q && off ? 0 : YRWI_E_NOMEM;
+  int64_t cap = 0;
+  if (rc == 0) {
+    int64_t oi = 0, oe = 0, os = 0;
+    for (jint i = 0; i < nq; i++) {
+      q[i].incl = ib + 12 * oi; q[i].nincl = ni[i];
+      q[i].excl = eb + 12 * oe; q[i].nexcl = ne[i];
+      q[i].max_distance = md[i]; q[i].k = 1; q[i].now_ms = nw[i];
+      if (ns && ns[i] > 0) { q[i].urlselection = sb + 12 * os; q[i].nurlselection = ns[i]; }
+      int64_t least = 0, n;  /* a conjunction is no longer than its shortest include list */
+      for (int t = 0; t < ni[i]; t++) {
+        n = 0;
+        yrwi_list_size(x, q[i].incl + 12 * t, &n);
+        if (t == 0 || n < least) least = n;
+      }
+      cap += least;
+      oi += ni[i]; oe += ne[i]; os += ns ? ns[i] : 0;
+    }
+    out = (uint8_t*)malloc((size_t)(cap > 0 ? cap : 1) * 40);
+    rc = out ? yrwi_term_search_batch(x, q, nq, out, cap, off, NULL) : YRWI_E_NOMEM;
+  }
+  (*env)->ReleaseIntArrayElements(env, nincl, ni, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, nexcl, ne, JNI_ABORT);
+  if (ns) (*env)->ReleaseIntArrayElements(env, nsel, ns, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, maxd, md, JNI_ABORT);
+  (*env)->ReleaseLongArrayElements(env, now, nw, JNI_ABORT);
+  jbyteArray res = NULL;
+  if (rc == 0 && off[nq] * 40 <= 0x7FFFFFFF) {
+    res = (*env)->NewByteArray(env, (jsize)(off[nq] * 40));
+    if (res) {
+      (*env)->SetByteArrayRegion(env, res, 0, (jsize)(off[nq] * 40), (const jbyte*)out);
+      (*env)->SetLongArrayRegion(env, rowOff, 0, nq + 1, (const jlong*)off);
+    }
+  }
+  free(ib);
+  free(eb);
+  free(sb);
+  free(q);
+  free(off);
+  free(out);
+  return res;
+}
+
 /* joinExclude into a direct ByteBuffer the caller owns and reuses (no JNI array copy
  * of the joined container): returns m (rows written, 40 bytes each) or the (negative)
  * error code -- YRWI_E_ARG when the container holds more rows than capacity / 40. */

@@ -229,6 +229,30 @@ public final class GpuRWI implements AutoCloseable {
         return rows;
     }
 
+    /** TermSearch.joined() of many queries in one pass (yrwi_term_search_batch): one planning
+     *  and join pass for all of them, the excluded rows dropped on the device.  Query i has the
+     *  term hashes include[i] / exclude[i], the url selection urlselection[i] (the array or an
+     *  entry may be null: none), maxDistance[i] and nowMillis[i].  Returns the packed rows of
+     *  all queries and fills rowOff (length &gt;= include.length + 1): query i owns the rows
+     *  rowOff[i] .. rowOff[i + 1], 40 bytes each, byte for byte what termSearch / joinExclude
+     *  return for it. */
+    public synchronized byte[] termSearchBatch(final byte[][][] include, final byte[][][] exclude,
+                                  final byte[][][] urlselection, final int[] maxDistance, final long[] nowMillis,
+                                  final long[] rowOff) {
+        final int nq = include.length;
+        final int[] ni = new int[nq], ne = new int[nq], ns = new int[nq];
+        for (int i = 0; i < nq; i++) {
+            ni[i] = include[i].length;
+            ne[i] = exclude[i] == null ? 0 : exclude[i].length;
+            ns[i] = urlselection == null || urlselection[i] == null ? 0 : urlselection[i].length;
+        }
+        final byte[] rows = termSearchBatch(this.ctx, nq, flatten3(include), ni, flatten3(exclude), ne,
+                                            urlselection == null ? null : flatten3(urlselection),
+                                            urlselection == null ? null : ns, maxDistance, nowMillis, rowOff);
+        if (rows == null) throw new IllegalStateException("yrwi_term_search_batch failed");
+        return rows;
+    }
+
     /** joinExclude into a caller-owned direct buffer (ByteBuffer.allocateDirect, reused
      *  across queries): no copy of the joined container through a Java array.  Returns
      *  the number of 40-byte rows written; throws when the container does not fit. */
@@ -550,6 +574,19 @@ public final class GpuRWI implements AutoCloseable {
         return b;
     }
 
+    /** the 12-byte hashes of every query back to back (a null query: none) */
+    private static byte[] flatten3(final byte[][][] hashes) {
+        int n = 0;
+        for (final byte[][] q : hashes) n += q == null ? 0 : q.length;
+        final byte[] b = new byte[12 * n];
+        int k = 0;
+        for (final byte[][] q : hashes) {
+            if (q == null) continue;
+            for (final byte[] h : q) System.arraycopy(h, 0, b, 12 * k++, 12);
+        }
+        return b;
+    }
+
     private static byte[] flattenN(final byte[][] hashes, final int w) {
         if (hashes == null) return null;
         final byte[] b = new byte[w * hashes.length];
@@ -577,6 +614,9 @@ public final class GpuRWI implements AutoCloseable {
                                                 long nowMillis);
     private static native byte[] termSearch(long ctx, byte[] incl, int nincl, byte[] excl, int nexcl, byte[] sel,
                                             int nsel, int maxDistance, long nowMillis);
+    private static native byte[] termSearchBatch(long ctx, int nq, byte[] incl, int[] nincl, byte[] excl, int[] nexcl,
+                                                 byte[] sel, int[] nsel, int[] maxDistance, long[] nowMillis,
+                                                 long[] rowOff);
     private static native long joinExcludeInto(long ctx, byte[] incl, int nincl, byte[] excl, int nexcl,
                                                int maxDistance, long nowMillis, java.nio.ByteBuffer out);
     private static native byte[] query(long ctx, byte[] incl, int nincl, byte[] excl, int nexcl, int maxDistance,

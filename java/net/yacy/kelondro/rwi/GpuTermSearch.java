@@ -6,6 +6,7 @@
 //   kelondro/rwi/AbstractIndex.java:96-128        -> J1 existence from the GPU index's list sizes
 //   kelondro/rwi/ReferenceContainer.java:310-326  -> the join, one yrwi_join_exclude call
 //   kelondro/rwi/TermSearch.java:76-78 inclusion() -> fetched from the GPU index only when asked
+//   several searches at once                      -> joinedBatch(...): one yrwi_term_search_batch call
 // Wiring: AbstractIndex.query (AbstractIndex.java:130-137) returns
 //   gpu == null ? new TermSearch<R>(...) : new GpuTermSearch<R>(gpu, ...)
 // and TermSearch gets a protected constructor for subclasses (INTEGRATION.md).
@@ -70,6 +71,36 @@ public class GpuTermSearch<ReferenceType extends Reference> extends TermSearch<R
                                                     maxDistance, System.currentTimeMillis()));
         return wrap(termFactory, gpu.joinExclude(toArray(queryHashes), toArray(excludeHashes), maxDistance,
                                                  System.currentTimeMillis()));
+    }
+
+    /** joined() of many searches at once (yrwi_term_search_batch): a peer that serves several
+     *  searches (SearchEvent.java:612-631 runs an RWIProcess per search) collects their
+     *  (queryHashes, excludeHashes, urlselection) and joins them in one pass on the device
+     *  instead of one synchronized call each.  Entry i of the result is what
+     *  new GpuTermSearch(gpu, queryHashes[i], excludeHashes[i], urlselection[i], ...).joined()
+     *  returns: its own slice of the packed rows.  urlselection, or any entry of it or of
+     *  excludeHashes, may be null. */
+    public static <R extends Reference> java.util.List<ReferenceContainer<R>> joinedBatch(
+            final GpuRWI gpu, final HandleSet[] queryHashes, final HandleSet[] excludeHashes,
+            final HandleSet[] urlselection, final ReferenceFactory<R> termFactory, final int maxDistance) {
+        final int nq = queryHashes.length;
+        final byte[][][] inc = new byte[nq][][], exc = new byte[nq][][];
+        final byte[][][] sel = urlselection == null ? null : new byte[nq][][];
+        final int[] maxd = new int[nq];
+        final long[] now = new long[nq], rowOff = new long[nq + 1];
+        final long t = System.currentTimeMillis();
+        for (int i = 0; i < nq; i++) {
+            inc[i] = toArray(queryHashes[i]);  // (none: J1 gives an empty container)
+            exc[i] = toArray(excludeHashes == null ? null : excludeHashes[i]);
+            if (sel != null) sel[i] = urlselection[i] == null ? null : toArray(urlselection[i]);
+            maxd[i] = maxDistance;
+            now[i] = t;
+        }
+        final byte[] rows = gpu.termSearchBatch(inc, exc, sel, maxd, now, rowOff);
+        final java.util.List<ReferenceContainer<R>> out = new java.util.ArrayList<ReferenceContainer<R>>(nq);
+        for (int i = 0; i < nq; i++)
+            out.add(wrap(termFactory, java.util.Arrays.copyOfRange(rows, (int) (40 * rowOff[i]), (int) (40 * rowOff[i + 1]))));
+        return out;
     }
 
     /** The include words' containers (TermSearch.inclusion), read from the GPU index

@@ -99,6 +99,13 @@ class CLocalStats(ctypes.Structure):
                 ("t_total_ns", ctypes.c_int64), ("device_allocs", ctypes.c_int64)]
 
 
+class CTsbStats(ctypes.Structure):
+    _fields_ = [("rows_joined", ctypes.c_int64), ("rows_out", ctypes.c_int64), ("bytes_h2d", ctypes.c_int64),
+                ("bytes_d2h", ctypes.c_int64), ("launches_tail", ctypes.c_int32), ("syncs", ctypes.c_int32),
+                ("direct", ctypes.c_int32), ("device_allocs", ctypes.c_int64), ("t_pack_ns", ctypes.c_int64),
+                ("t_total_ns", ctypes.c_int64)]
+
+
 class CEventInfo(ctypes.Structure):
     _fields_ = [("flagcount", ctypes.c_int32 * 32), ("postings_in", ctypes.c_int64),
                 ("admitted_local", ctypes.c_int64), ("admitted_remote", ctypes.c_int64),
@@ -271,6 +278,8 @@ SIGNATURES = {
                                          ctypes.POINTER(ctypes.c_int64)]),
     "yrwi_term_search": (ctypes.c_int, [_VP, ctypes.POINTER(CQuery), _VP, ctypes.c_int64,
                                         ctypes.POINTER(ctypes.c_int64)]),
+    "yrwi_term_search_batch": (ctypes.c_int, [_VP, ctypes.POINTER(CQuery), ctypes.c_int32, _VP, ctypes.c_int64, _VP,
+                                              ctypes.POINTER(CTsbStats)]),
     "yrwi_normalize_score": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.POINTER(CProfile), ctypes.c_char_p,
                                             ctypes.c_int64, _VP]),
 }

@@ -1406,12 +1406,15 @@ int yrwi::join_containers(yrwi_ctx* ctx, Lane* L, const yrwi_query_desc* const* 
   if (int rc0 = ensure_url_ids(ctx)) return rc0;
   std::vector<Plan>& plans = *plans_out;
   plans.assign((size_t)nq, Plan());
+  L->err_query = -1;
   for (int32_t i = 0; i < nq; i++) {
     yrwi_query_desc d = *q[i];
     d.k = 1;
     d.filter = nullptr;
+    L->err_query = i;
     if (int rc = ctx->take(L, plan_query(ctx, L, d, &plans[(size_t)i]))) return rc;
   }
+  L->err_query = -1;
   int rc;
   if ((rc = ctx->take(L, resolve_selections(L, plans)))) return rc;
   if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);

@@ -321,6 +321,9 @@ struct Lane {
   // one entry per group of tiles: set by yrwi_event_add_local for its call, whose bytes over PCIe
   // must not depend on the list lengths
   bool chain_groups_on_device = false;
+  // the plan a planning error of join_containers belongs to (-1: none, or not one query's):
+  // yrwi_term_search_batch names it in its message
+  int32_t err_query = -1;
   // scratch high-water mark of the context's lanes (bytes): a lane whose arena is
   // smaller takes that size at the start of its next pass instead of growing
   // inside it (one allocation, before any of the pass's kernels)

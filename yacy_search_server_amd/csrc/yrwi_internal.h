@@ -687,6 +687,16 @@ struct LocalJob {
 // total), the rows written.  tile_base[j] = jobs[j].tile0; d_tile_cnt: `tiles` ints of scratch.
 int launch_local_rows(const LocalJob* d_jobs, const int64_t* d_tile_base, int32_t njobs, int64_t tiles,
                       const uint64_t* dkhi, const uint8_t* dklo, int32_t* d_tile_cnt, EvJob* d_evjobs, void* stream);
+// The same compaction for yrwi_term_search_batch: every job's kept rows into ONE packed image
+// in job order, three launches for the whole call.  LocalJob::out and ::evjob are not read.
+// d_qtile[i], i <= nq: the first tile of the first job that belongs to query i or a later one
+// (`tiles` when there is none).  Writes d_tile_start (tiles + 1 words: kept rows before each
+// tile, then the total) and d_row_off (nq + 1 words: kept rows before each query, then the
+// total).  The rows are stored to `out` (8-byte aligned, device or pinned host memory, room for
+// cap_rows rows) only when the total fits cap_rows; out == nullptr counts only.
+int launch_tsb_rows(const LocalJob* d_jobs, const int64_t* d_tile_base, int32_t njobs, int64_t tiles,
+                    const uint64_t* dkhi, const uint8_t* dklo, const int64_t* d_qtile, int32_t nq, int32_t* d_tile_cnt,
+                    int64_t* d_tile_start, int64_t* d_row_off, int64_t cap_rows, uint8_t* out, void* stream);
 // what the host reads back after k_event_add, in one buffer of 2 njobs + nev words: out[j] =
 // d_evjobs[j].n and out[njobs + j] = d_status[j] of the njobs arrivals, out[2 njobs + e] = the
 // epoch event e has reached

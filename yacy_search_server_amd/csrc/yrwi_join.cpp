@@ -541,9 +541,11 @@ static int plan_chains(Lane* ctx, std::vector<Plan>& plans, const std::vector<in
     const int t = (int)P.seq.size(), ni = t - 2, ns = P.has_sel ? 1 : 0;
     const bool can = chain_on && !P.empty && P.maxd >= 65535 && acc_g[qi] > 0 && t >= 2 && ni <= CHAIN_MAXI &&
                      ns + ni + P.nexcl_g > 0 && ns + ni + P.nexcl_g <= CHAIN_MAXL;
-    if (P.has_sel && !P.empty && t >= 2 && !can)
+    if (P.has_sel && !P.empty && t >= 2 && !can) {
+      ctx->err_query = (int32_t)qi;
       return ctx->fail(YRWI_E_UNSUPPORTED, "urlselection: a fold of more than four include terms or with a "
                                            "maxDistance filter");
+    }
     if (!can) continue;
     ChainQ& C = chq[qi];
     std::memset(&C, 0, sizeof(C));

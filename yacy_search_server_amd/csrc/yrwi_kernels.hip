@@ -5532,6 +5532,73 @@ int launch_local_rows(const LocalJob* d_jobs, const int64_t* d_tile_base, int32_
   return rc(hipGetLastError());
 }
 
+// ------------------------------------------------ batched term search (yrwi_term_search_batch)
+// The kept rows of every container of the call as one packed image: k_local_count's tile
+// counts become 64-bit starts across all jobs, the rows go where those point.
+//
+// One workgroup walks the tile counts of the whole call, 256 at a time with a running carry:
+// tile_start[t] = kept rows before tile t, tile_start[tiles] = the total.  The queries' offsets
+// follow from it: qtile[i] = the first tile of the first job whose query is >= i (tiles when
+// there is none), so an empty query repeats its successor's offset and row_off[nq] is the total.
+__global__ __launch_bounds__(256) void k_tsb_scan(const int32_t* __restrict__ tile_cnt, int64_t tiles,
+                                                  const int64_t* __restrict__ qtile, int32_t nq,
+                                                  int64_t* tile_start, int64_t* __restrict__ row_off) {
+  __shared__ uint64_t sScan64[4];
+  uint64_t carry = 0;
+  for (int64_t b = 0; b < tiles; b += 256) {
+    const int64_t x = b + threadIdx.x;
+    uint64_t tot;
+    const uint64_t off = block_excl_sum256_u64(x < tiles ? (uint64_t)tile_cnt[x] : 0, sScan64, &tot);
+    if (x < tiles) tile_start[x] = (int64_t)(carry + off);
+    carry += tot;
+  }
+  if (threadIdx.x == 0) tile_start[tiles] = (int64_t)carry;
+  __syncthreads();  // the workgroup reads back its own starts
+  for (int32_t i = threadIdx.x; i <= nq; i += 256) row_off[i] = tile_start[qtile[i]];
+}
+
+// k_local_rows into the packed image.  The total is read from device memory: a call whose rows
+// do not fit cap_rows, or that only counts (out == nullptr), stores nothing.  out is 8-byte
+// aligned and may be pinned host memory (five 8-byte stores per row, each row written once).
+__global__ __launch_bounds__(LR_TILE) void k_tsb_pack(const LocalJob* __restrict__ jobs,
+                                                      const int64_t* __restrict__ tile_base, int32_t njobs,
+                                                      const uint64_t* __restrict__ dkhi,
+                                                      const uint8_t* __restrict__ dklo,
+                                                      const int64_t* __restrict__ tile_start, int64_t tiles,
+                                                      int64_t cap_rows, uint8_t* __restrict__ out) {
+  __shared__ int32_t sScan[4];
+  if (!out || tile_start[tiles] > cap_rows) return;
+  const int64_t t = blockIdx.x;
+  const LocalJob& J = jobs[find_job(tile_base, njobs, t)];
+  const int64_t i = (t - J.tile0) * LR_TILE + threadIdx.x;
+  const bool keep = local_keep(J, i);
+  int32_t tot;
+  const int32_t off = block_excl_sum256(keep ? 1 : 0, sScan, &tot);
+  if (!keep) return;
+  Row r;
+  if (J.rows) {
+    r = load_row(J.rows + i * YRWI_ROW_BYTES);  // a single include list: as stored (:355-370)
+  } else {
+    const uint32_t u = J.uid[i];
+    r = row_of_rec(load_rec(J.feat, i), dkhi[u], dklo[u], J.now_ms);
+  }
+  store_row(out + (tile_start[t] + off) * YRWI_ROW_BYTES, r);
+}
+
+int launch_tsb_rows(const LocalJob* d_jobs, const int64_t* d_tile_base, int32_t njobs, int64_t tiles,
+                    const uint64_t* dkhi, const uint8_t* dklo, const int64_t* d_qtile, int32_t nq, int32_t* d_tile_cnt,
+                    int64_t* d_tile_start, int64_t* d_row_off, int64_t cap_rows, uint8_t* out, void* st) {
+  if (njobs <= 0 || tiles <= 0 || nq <= 0) return 0;
+  if (tiles > 0x7FFFFFFFLL) return -1;
+  hipLaunchKernelGGL(k_local_count, dim3((unsigned)tiles), dim3(LR_TILE), 0, S(st), d_jobs, d_tile_base, njobs,
+                     d_tile_cnt);
+  hipLaunchKernelGGL(k_tsb_scan, dim3(1), dim3(256), 0, S(st), d_tile_cnt, tiles, d_qtile, nq, d_tile_start,
+                     d_row_off);
+  hipLaunchKernelGGL(k_tsb_pack, dim3((unsigned)tiles), dim3(LR_TILE), 0, S(st), d_jobs, d_tile_base, njobs, dkhi,
+                     dklo, d_tile_start, tiles, cap_rows, out);
+  return rc(hipGetLastError());
+}
+
 __global__ void k_chain_groups(const ChainGroupJob* __restrict__ cgj, int32_t njobs, int2* __restrict__ cgrp,
                                int64_t ngroups) {
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

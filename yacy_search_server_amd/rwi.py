@@ -338,6 +338,7 @@ class RWIIndex:
             for p in getattr(self, "_pinned", []):
                 _lib.lib().yrwi_host_free(self._h, p)
             self._pinned = []
+            self._tsb_buf, self._tsb_cap = None, -1  # term_search_batch's pinned landing buffer went with them
             _lib.lib().yrwi_close(self._h)
             self._h = None
 
@@ -572,6 +573,46 @@ class RWIIndex:
                                                       urlselection)], 1)
             _check(self._h, _lib.lib().yrwi_term_search(self._h, arr, out.ctypes.data, cap, ctypes.byref(m)))
         return out[:m.value].copy()
+
+    def term_search_batch_raw(self, queries: Sequence[Query], rows_out, cap_rows: int,
+                              row_off) -> Tuple[int, "_lib.CTsbStats"]:
+        """yrwi_term_search_batch as it is: rows_out and row_off are ctypes arrays, numpy arrays,
+        addresses or None (rows_out None: the count-only form).  Returns (rc, the call's
+        yrwi_tsb_stats) and raises nothing."""
+        st = _lib.CTsbStats()
+        cq, keep = (self._marshal(queries, 1)[:2]) if len(queries) else (None, None)
+        rc = _lib.lib().yrwi_term_search_batch(self._h, cq, len(queries), _address(rows_out), cap_rows,
+                                               _address(row_off), ctypes.byref(st))
+        return rc, st
+
+    def term_search_batch(self, queries: Sequence[Query],
+                          pinned: bool = False) -> Tuple[List[np.ndarray], "_lib.CTsbStats"]:
+        """TermSearch.joined() of every query in one pass (yrwi_term_search_batch): the joined
+        and excluded container of queries[i] as an (m_i, 40) uint8 view into one buffer, what
+        term_search(...) of that query returns, and the call's yrwi_tsb_stats.  The buffer is
+        sized by the sum of each query's smallest include list (no counting call first).
+        pinned=True lands the rows in the index's pinned buffer without a staging copy: those
+        views are valid until the next pinned call or close()."""
+        cap = 0
+        for q in queries:
+            cap += min((self.get_size(t) for t in q.include), default=0)
+        row_off = np.zeros(len(queries) + 1, dtype=np.int64)
+        if pinned:
+            if getattr(self, "_tsb_cap", -1) < cap:
+                old = ctypes.addressof(self._tsb_buf) if getattr(self, "_tsb_buf", None) is not None else None
+                if old is not None:  # the grown buffer replaces it
+                    self._tsb_buf = None
+                    self._pinned.remove(old)
+                    _check(self._h, _lib.lib().yrwi_host_free(self._h, old))
+                self._tsb_buf = self.host_array(ctypes.c_uint8, 40 * max(cap, 1))
+                self._tsb_cap = cap
+            buf = np.ctypeslib.as_array(self._tsb_buf)
+        else:
+            buf = np.zeros(40 * max(cap, 1), dtype=np.uint8)
+        rc, st = self.term_search_batch_raw(queries, buf, cap, row_off)
+        _check(self._h, rc)
+        rows = buf[:40 * int(row_off[-1])].reshape(-1, 40)
+        return [rows[row_off[i]:row_off[i + 1]] for i in range(len(queries))], st
 
     # ---- ReferenceOrder.normalizeWith + cardinal ----
     def normalize_score(self, rows: np.ndarray, profile: Optional[RankingProfile] = None, language: str = "en",
