@@ -334,6 +334,60 @@ typedef struct yrwi_census_stats {
 } yrwi_census_stats;
 int yrwi_host_census(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, int32_t order, int64_t min_postings,
                      uint8_t* hosts6_out, int64_t* counts_out, int64_t cap, int64_t* nout, yrwi_census_stats* st);
+/* Retention: keeps the device index inside a budget by two rules on the lastModified day of a posting (the `a`
+ * cell: bytes 12-13 of the row, big endian, days; the raw unsigned 16-bit value, not clamped to today -- that
+ * clamp belongs to ranking).  UNVERIFIED against a reference line: the reference has no method that drops
+ * postings by age or caps a container by age; both rules are defined here.
+ *   Selection: that of yrwi_remove_hosts (nterms == 0 every list, otherwise the named lists, duplicates once,
+ * unknown terms ignored, an ill-formed term YRWI_E_HASH with nothing changed); both calls wait for the batches
+ * in flight.
+ *   Age rule: every selected row with a < min_day goes.  min_day is 0 .. 65536: 0 = no age rule, 65536 removes
+ * every selected row; outside: YRWI_E_ARG.  A list left empty disappears as after yrwi_put_list(n = 0).
+ *   Cap rule: max_refs == 0 = no cap, max_refs < 0: YRWI_E_ARG.  A selected list with s > max_refs survivors of
+ * the age rule keeps exactly max_refs of them, those with the largest a: with d* the cut day (the max_refs-th
+ * largest a among the survivors), every survivor with a > d* stays, and of the survivors with a == d* the first
+ * q = max_refs - |{a > d*}| in url-hash order.  Stated differently: stable-sort the survivors by a descending,
+ * keep the first max_refs, restore url-hash order.  The kept rows keep their bytes and their order.
+ *   yrwi_retain leaves exactly what yrwi_remove_postings of the removed (term, url) pairs would leave, fills st
+ * as that call does (removed == removed_age + removed_cap; st and rst may be NULL) and goes through the same
+ * compaction as yrwi_remove_hosts (YRWI_RM_CHUNK).  One pass over the a cells of the selected postings (40 B per
+ * posting: the cell sits inside the row) counts the old rows per list; the counts are read back once, and from
+ * them the host knows every list's final length.  The cut days and quotas are found and consumed on the device:
+ * a two-level radix select (high byte, then low byte, 2 x 256 bins of 4 B per list over the cap) over the
+ * flattened postings of the lists over the cap, then, per compaction chunk, the marks a == d* are scanned
+ * for a row's rank among its list's rows of the cut day.  launches and syncs depend on the number of
+ * compaction chunks and on which rules are given (max_refs > 0: the search and the second scan per chunk are
+ * enqueued whether or not a list is over the cap), never on the lists or their lengths; the host waits as
+ * often as in yrwi_remove_hosts.  min_day == 0 && max_refs == 0, or nothing selected: a successful no-op that
+ * enqueues nothing and reports zeros (day_min = day_max = -1).  YRWI_E_ARG, YRWI_E_HASH, YRWI_E_NOMEM: nothing
+ * has changed.
+ *   yrwi_retention_count is the dry run: it changes nothing and fills st with the counts yrwi_retain with the
+ * same arguments reports (launches, syncs and the times are the dry run's own; t_select_ns is 0: the counts
+ * need no cut day).  With day_hist != NULL (65,536 entries) day_hist[d] = selected rows with a == d, counted
+ * before any rule (they sum to st->postings), so that a caller can pick the min_day that reaches a target
+ * size; with day_hist the pass also runs for min_day == 0 && max_refs == 0.  The histogram is exact: every
+ * workgroup counts in an LDS window of 8192 days around the day of its span's first posting, and a posting
+ * whose day is outside the window is added to the device table directly (hist_bypass).
+ *   A sharded context: the age rule acts on what the rank holds and the ranks' `removed` add up; max_refs > 0
+ * returns YRWI_E_UNSUPPORTED with nothing changed (the cap is of the whole container: the ranks would have to
+ * exchange their per-list histograms).  Rules on other cells and a persistent per-list day array are not part
+ * of this. */
+typedef struct yrwi_retention_stats {
+  int64_t lists, postings;        /* selected non-empty lists, rows in them */
+  int64_t removed_age;            /* rows with a < min_day */
+  int64_t removed_cap;            /* rows the cap takes after the age rule */
+  int64_t lists_age, lists_cap;   /* lists that lose rows to each rule (a list may be in both) */
+  int64_t emptied_terms;          /* lists the age rule empties */
+  int32_t day_min, day_max;       /* smallest / largest a over the selected rows, before any rule; -1, -1 when none */
+  int32_t launches, syncs;
+  int64_t t_mark_ns, t_select_ns; /* HIP events: the streaming pass over the a cells; the per-list cut-day search */
+  int64_t t_total_ns;
+  int64_t hist_bypass;            /* day_hist only: rows counted straight into the device table (outside the LDS window) */
+} yrwi_retention_stats;
+int yrwi_retention_count(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, int32_t min_day, int64_t max_refs,
+                         int64_t* day_hist, yrwi_retention_stats* st);
+int yrwi_retain(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, int32_t min_day, int64_t max_refs,
+                yrwi_update_stats* st, yrwi_retention_stats* rst);
 /* Brings the url dictionary (url hash -> order-preserving 32-bit url id, the
  * join key in HBM) up to date now instead of at the next query.  The first
  * build sorts every key; later put_list / removal / load_heaps changes are

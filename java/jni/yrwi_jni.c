@@ -173,6 +173,59 @@ JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_hostCensus(JNIEnv
   return res;
 }
 
+/* yrwi_retention_stats as 15 longs at v: lists, postings, removed_age, removed_cap, lists_age, lists_cap,
+ * emptied_terms, day_min, day_max, launches, syncs, t_mark_ns, t_select_ns, t_total_ns, hist_bypass */
+static void retention_stats(jlong* v, const yrwi_retention_stats* st) {
+  const jlong s[15] = {st->lists,     st->postings,      st->removed_age, st->removed_cap, st->lists_age,
+                       st->lists_cap, st->emptied_terms, st->day_min,     st->day_max,     st->launches,
+                       st->syncs,     st->t_mark_ns,     st->t_select_ns, st->t_total_ns,  st->hist_bypass};
+  memcpy(v, s, sizeof(s));
+}
+
+/* yrwi_retention_count as long[15], or with hist != 0 as long[15 + 65536]: the statistics, then the histogram
+ * of the selected rows' lastModified days; NULL when the call failed */
+JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_retentionCount(JNIEnv* env, jclass c, jlong ctx,
+                                                                             jbyteArray terms, jint nterms,
+                                                                             jint min_day, jlong max_refs, jint hist) {
+  uint8_t* t = copy_in(env, terms, (int64_t)nterms * 12);
+  if (!t) return NULL;
+  const jsize n = 15 + (hist ? 65536 : 0);
+  jlong* v = (jlong*)calloc((size_t)n, sizeof(jlong));
+  yrwi_retention_stats st;
+  int rc = v ? yrwi_retention_count((yrwi_ctx*)(intptr_t)ctx, t, nterms, min_day, max_refs,
+                                    hist ? (int64_t*)(v + 15) : NULL, &st)
+             : YRWI_E_NOMEM;
+  free(t);
+  jlongArray res = NULL;
+  if (rc == 0) {
+    retention_stats(v, &st);
+    res = (*env)->NewLongArray(env, n);
+    if (res) (*env)->SetLongArrayRegion(env, res, 0, n, v);
+  }
+  free(v);
+  return res;
+}
+
+/* yrwi_retain as long[9 + 15]: the statistics of removePostings, then yrwi_retention_stats; NULL when the call
+ * failed */
+JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_retain(JNIEnv* env, jclass c, jlong ctx,
+                                                                     jbyteArray terms, jint nterms, jint min_day,
+                                                                     jlong max_refs) {
+  uint8_t* t = copy_in(env, terms, (int64_t)nterms * 12);
+  if (!t) return NULL;
+  yrwi_update_stats st;
+  yrwi_retention_stats rst;
+  int rc = yrwi_retain((yrwi_ctx*)(intptr_t)ctx, t, nterms, min_day, max_refs, &st, &rst);
+  free(t);
+  if (rc != 0) return NULL;
+  jlong v[24] = {st.terms, st.new_terms, st.emptied_terms, st.added, st.replaced, st.dropped, st.removed,
+                 st.launches, st.syncs};
+  retention_stats(v + 9, &rst);
+  jlongArray res = (*env)->NewLongArray(env, 24);
+  if (res) (*env)->SetLongArrayRegion(env, res, 0, 24, v);
+  return res;
+}
+
 JNIEXPORT jbyteArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_joinExclude(JNIEnv* env, jclass c, jlong ctx,
                                                                           jbyteArray incl, jint nincl, jbyteArray excl,
                                                                           jint nexcl, jint maxd, jlong now) {

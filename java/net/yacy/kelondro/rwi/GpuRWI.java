@@ -198,6 +198,35 @@ public final class GpuRWI implements AutoCloseable {
         return new HostCensus(hosts, counts, java.util.Arrays.copyOfRange(r, 1, 12));
     }
 
+    /** Entries of the day histogram of retentionCount: one per value of the 16-bit lastModified cell. */
+    public static final int RETENTION_DAYS = 65536;
+
+    /** What retain(terms, minDay, maxRefs) would remove, the index unchanged (yrwi_retention_count):
+     *  long[15] = {lists, postings, removedAge, removedCap, listsAge, listsCap, emptiedTerms, dayMin,
+     *  dayMax, launches, syncs, tMarkNs, tSelectNs, tTotalNs, histBypass} (yrwi_retention_stats), and with
+     *  hist the RETENTION_DAYS entries of the histogram of the selected rows' lastModified days after them
+     *  (counted before any rule: what a caller picks the minDay from that reaches a target size). */
+    public synchronized long[] retentionCount(final byte[][] terms, final int minDay, final long maxRefs,
+                                              final boolean hist) {
+        final int nterms = terms == null ? 0 : terms.length;
+        final long[] st = retentionCount(this.ctx, nterms == 0 ? new byte[0] : flatten(terms), nterms, minDay,
+                                         maxRefs, hist ? 1 : 0);
+        if (st == null) throw new IllegalStateException("yrwi_retention_count failed");
+        return st;
+    }
+
+    /** Retention on the device (yrwi_retain): from the lists of `terms` (terms == null or empty: from every
+     *  list) every posting whose lastModified day is below minDay goes (0: no age rule), then a list that
+     *  still has more than maxRefs rows (0: no cap) keeps its maxRefs newest, equal days at the cut in
+     *  url-hash order.  No list crosses to the host.  Returns long[24]: the statistics of removePostings,
+     *  then those of retentionCount.  The rules are this project's: the reference has no such method. */
+    public synchronized long[] retain(final byte[][] terms, final int minDay, final long maxRefs) {
+        final int nterms = terms == null ? 0 : terms.length;
+        final long[] st = retain(this.ctx, nterms == 0 ? new byte[0] : flatten(terms), nterms, minDay, maxRefs);
+        if (st == null) throw new IllegalStateException("yrwi_retain failed");
+        return st;
+    }
+
     /** Index.size(termHash) of each term on the GPU index (yrwi_list_size; 0: no list). */
     public synchronized long[] listSizes(final byte[][] terms) {
         return listSizes(this.ctx, flatten(terms), terms.length);
@@ -608,6 +637,10 @@ public final class GpuRWI implements AutoCloseable {
     // {nout, the 11 statistics, counts[0 .. nout)}; hosts6Out (6 * cap bytes) receives the hosts; null: failed
     private static native long[] hostCensus(long ctx, byte[] terms, int nterms, int order, long minPostings, long cap,
                                             byte[] hosts6Out);
+    // the 15 statistics, then with hist != 0 the 65536 histogram entries; null: failed
+    private static native long[] retentionCount(long ctx, byte[] terms, int nterms, int minDay, long maxRefs, int hist);
+    // the 9 statistics of removePostings, then the 15 of retentionCount; null: failed
+    private static native long[] retain(long ctx, byte[] terms, int nterms, int minDay, long maxRefs);
     private static native byte[] joinExclude(long ctx, byte[] incl, int nincl, byte[] excl, int nexcl,
                                              int maxDistance, long nowMillis);
     private static native long[] normalizeScore(long ctx, byte[] rows, int m, int[] profile32, String language,

@@ -163,6 +163,17 @@ class CCensusStats(ctypes.Structure):
                 ("t_count_ns", ctypes.c_int64), ("t_total_ns", ctypes.c_int64)]
 
 
+RETENTION_DAYS = 65536  # entries of yrwi_retention_count's day histogram: one per value of the 16-bit `a` cell
+RETENTION_LDS_WINDOW = 8192  # days a workgroup of the histogram pass counts in LDS; days outside it: hist_bypass
+
+
+class CRetentionStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("lists", "postings", "removed_age", "removed_cap", "lists_age",
+                                              "lists_cap", "emptied_terms")] + \
+        [(n, ctypes.c_int32) for n in ("day_min", "day_max", "launches", "syncs")] + \
+        [(n, ctypes.c_int64) for n in ("t_mark_ns", "t_select_ns", "t_total_ns", "hist_bypass")]
+
+
 DUMP_WINDOW_DEFAULT = 32 << 20 # yrwi_dump_heap's window without YRWI_DUMP_WINDOW (bytes)
 
 
@@ -209,6 +220,10 @@ SIGNATURES = {
     "yrwi_host_census": (ctypes.c_int, [_VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _VP, _VP,
                                         ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
                                         ctypes.POINTER(CCensusStats)]),
+    "yrwi_retention_count": (ctypes.c_int, [_VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _VP,
+                                            ctypes.POINTER(CRetentionStats)]),
+    "yrwi_retain": (ctypes.c_int, [_VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                   ctypes.POINTER(CUpdateStats), ctypes.POINTER(CRetentionStats)]),
     "yrwi_build_url_ids": (ctypes.c_int, [_VP]),
     "yrwi_list_size": (ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]),
     "yrwi_get_list": (ctypes.c_int, [_VP, ctypes.c_char_p, _VP, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),

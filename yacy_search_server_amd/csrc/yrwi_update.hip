@@ -60,6 +60,10 @@
 // count descending), and only the first min(hosts_passing, cap) cross PCIe.  All scratch is the
 // lane's arena; 5 launches and one sync per counting pass, 5 or 6 launches and one sync after them.
 //
+// yrwi_retain / yrwi_retention_count: removal by the age of a posting and a cap on the length of a list;
+// described with their kernels at the end of this file.  They share the selection, the spans and
+// compact_commit with the host calls.
+//
 // A changed list is a new list in index memory (the old copy is dead until repack_index,
 // reached through ensure_url_ids) and goes through index_changed like a replaced list.
 
@@ -524,18 +528,28 @@ int64_t rm_chunk() {
   return std::min<int64_t>(std::max<int64_t>(v, 256), (int64_t)INT32_MAX - 1);
 }
 
+// what compact_commit hands a flag functor besides the chunk: the scan's output and scratch (free until
+// the chunk's own scan), and, when asked for, every chunk list's index in the selection
+struct ChunkAux {
+  int64_t* kx;
+  void* tmp;
+  size_t tb;
+  const int32_t* sel;  // sel[c] = list c of the chunk is list sel[c] of the RmTable (want_sel only)
+};
+
 // List j of t loses rem[j] postings (counted by the caller's marking pass): the lists that lose
 // some but not all are compacted into new lists from index memory, in chunks of whole lists, and
-// every list that lost rows is committed to the context.  flag(jobs, off, nj, n, keep) enqueues
+// every list that lost rows is committed to the context.  flag(jobs, off, nj, n, keep, aux) enqueues
 // the caller's flag kernel for one chunk (keep[i] = posting i stays, keep[n] = 0).  One upload,
 // three launches per chunk and one wait; none of them if no list needs compaction.
 template <class Flag>
 int compact_commit(yrwi_ctx* ctx, Lane* L, RmTable& t, const std::vector<int64_t>& rem, const char* nomem, Flag flag,
-                   yrwi_update_stats* S, Tally* T) {
+                   yrwi_update_stats* S, Tally* T, bool want_sel = false) {
   const int nj = (int)t.jobs.size();
   std::vector<int> lose;
   std::vector<RmJob> cjobs;
   std::vector<int64_t> coff;            // offsets within the list's chunk
+  std::vector<int32_t> csel;            // want_sel: the list's index in t
   std::vector<std::pair<int, int>> ch;  // chunks: [first, last) of cjobs
   const int64_t cap = rm_chunk();
   int64_t ctotal = 0, maxc = 0;
@@ -555,6 +569,7 @@ int compact_commit(yrwi_ctx* ctx, Lane* L, RmTable& t, const std::vector<int64_t
     }
     cjobs.push_back(J);
     coff.push_back(ctotal);
+    if (want_sel) csel.push_back(j);
     ctotal += J.n;
     ch.back().second = (int)cjobs.size();
     maxc = std::max(maxc, ctotal);
@@ -562,20 +577,21 @@ int compact_commit(yrwi_ctx* ctx, Lane* L, RmTable& t, const std::vector<int64_t
   if (!ch.empty()) {
     RmJob* d_cjobs = arena_alloc<RmJob>(L, (int64_t)cjobs.size());
     int64_t* d_coff = arena_alloc<int64_t>(L, (int64_t)cjobs.size());
+    int32_t* d_csel = arena_alloc<int32_t>(L, (int64_t)csel.size());
     int32_t* keep = arena_alloc<int32_t>(L, maxc + 1);
     int64_t* kx = arena_alloc<int64_t>(L, maxc + 1);
     size_t tb = 0;
     HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, keep, kx, (int)(maxc + 1), L->stream));
     void* tmp = L->arena.alloc(tb);
-    if (!d_cjobs || !d_coff || !keep || !kx || !tmp) return ctx->fail(YRWI_E_NOMEM, nomem);
-    if (int rc = upload(L, d_cjobs, cjobs, d_coff, coff)) return ctx->take(L, rc);
+    if (!d_cjobs || !d_coff || !d_csel || !keep || !kx || !tmp) return ctx->fail(YRWI_E_NOMEM, nomem);
+    if (int rc = upload(L, d_cjobs, cjobs, d_coff, coff, d_csel, csel)) return ctx->take(L, rc);  // (one copy kernel)
     T->launches++;
     for (const auto& c : ch) {  // flag -> scan -> place, each chunk in the scratch of the one before
       const int ncj = c.second - c.first;
       const int64_t n = coff[(size_t)c.second - 1] + cjobs[(size_t)c.second - 1].n;
       const RmJob* dj = d_cjobs + c.first;
       const int64_t* doff = d_coff + c.first;
-      flag(dj, doff, ncj, n, keep);
+      flag(dj, doff, ncj, n, keep, ChunkAux{kx, tmp, tb, d_csel + c.first});
       size_t tbc = tb;
       HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(tmp, tbc, keep, kx, (int)(n + 1), L->stream));
       hipLaunchKernelGGL(k_rm_place, dim3(blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, keep, kx);
@@ -836,7 +852,7 @@ extern "C" int yrwi_remove_postings(yrwi_ctx* ctx, const uint8_t* terms12, int32
   T.syncs++;
   // ---- compaction of only the lists that lost rows, and the bookkeeping
   const std::vector<int64_t> rem(hrem, hrem + nj);  // (the pinned landing buffer may be reused)
-  auto flag = [&](const RmJob* dj, const int64_t* doff, int ncj, int64_t n, int32_t* keep) {
+  auto flag = [&](const RmJob* dj, const int64_t* doff, int ncj, int64_t n, int32_t* keep, const ChunkAux&) {
     hipLaunchKernelGGL(k_rm_flag, dim3(blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, ukh, ukl, nu, keep);
   };
   if (int rc = compact_commit(ctx, L, t, rem, "device allocation (remove_postings compaction)", flag, &S, &T)) return rc;
@@ -951,7 +967,7 @@ extern "C" int yrwi_remove_hosts(yrwi_ctx* ctx, const uint8_t* terms12, int32_t 
   Lane* L = ctx->lanes[0];
   if (int rc = host_mark(ctx, L, &P, false, &T)) return rc;
   const int nh = (int)P.hk.size();
-  auto flag = [&](const RmJob* dj, const int64_t* doff, int ncj, int64_t n, int32_t* keep) {
+  auto flag = [&](const RmJob* dj, const int64_t* doff, int ncj, int64_t n, int32_t* keep, const ChunkAux&) {
     if (nh <= HOST_LDS_MAX)
       hipLaunchKernelGGL((k_host_flag<true>), dim3(mark_blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, P.d_hk, nh, keep);
     else
@@ -1254,4 +1270,470 @@ extern "C" int yrwi_host_census(yrwi_ctx* ctx, const uint8_t* terms12, int32_t n
     counts_out[i] = hc[i];
   }
   return finish(nw);
+}
+
+// ---------------------------------------------------------------- retention: age and cap
+//
+// yrwi_retain / yrwi_retention_count (UNVERIFIED against a reference line: the rules are this project's).
+// The age rule removes every selected posting whose lastModified day (the `a` cell) is below min_day; the
+// cap rule leaves a list that still has more than max_refs rows its max_refs newest, ties at the cut day
+// kept in url-hash order.  One streaming pass over the a cells of the flattened selection (k_ret_mark, grid
+// and spans of k_host_mark, 40 B per posting: the cell sits inside the row) counts the old rows per list,
+// keeps the smallest and the largest day and, for the dry run, fills the histogram of the days: every
+// workgroup counts in an LDS window of RET_WIN days around the day of its span's first posting and adds the
+// window to the device table at the end of its span; a day outside the window goes straight to the device
+// table, equal days of the wave as one add (hist_bypass).  The per-list counts are read back once, and the
+// host then knows every list's final length.  The cut day d* and the quota q of the lists over the cap are
+// found on the device by a two-level radix select over the flattened postings of those lists (k_ret_bins:
+// 256 bins of the high byte per list, k_ret_pick, 256 bins of the low byte within the chosen bucket,
+// k_ret_pick; only survivors of the age rule are counted; a wave sums a list's bins in LDS and adds them to
+// the device bins on leaving the list) and
+// are consumed by the flag kernels of compact_commit: with a cap a chunk is flagged in two steps, the marks
+// a == d* scanned first for a row's rank among its list's rows of the cut day.
+namespace {
+
+constexpr int RET_WIN = 8192;  // days of a workgroup's LDS histogram window (32 KiB)
+constexpr int RET_DAYS = 65536;
+enum { RET_MINV = 0, RET_MAX1 = 1, RET_BYPASS = 2, RET_WORDS = 3 };
+
+// a lane's place in the flattened lists and its list's rows
+struct DayCursor : SegCursor {
+  const uint8_t* rows = nullptr;
+  bool moved = false;  // the last seek entered another list
+};
+
+__device__ __forceinline__ void day_seek(DayCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                         int nj, int64_t total, int64_t i) {
+  s.moved = i >= s.hi;
+  if (!s.moved) return;
+  seg_seek(s, jobs, off, nj, total, i);
+  s.rows = jobs[s.c].rows;
+}
+
+// One step of a thread: postings base + 256 u + thread (u < 4) below end -> their a cells and lists (-1: past
+// end).  The four loads are issued before the first use.
+__device__ __forceinline__ void day_tile(DayCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                         int nj, int64_t total, int64_t base, int64_t end, int a[4], int c[4]) {
+#pragma unroll
+  for (int u = 0; u < 4; u++) {
+    const int64_t i = base + u * 256 + threadIdx.x;
+    c[u] = -1;
+    a[u] = -1;
+    if (i < end) {
+      day_seek(s, jobs, off, nj, total, i);
+      c[u] = s.c;
+      a[u] = (int)row_lm(s.rows + (i - s.lo) * YRWI_ROW_BYTES);
+    }
+  }
+}
+
+// Age pass: jage[c] += postings of list c with a < min_day (summed in the wave per list as k_host_mark sums
+// jrem); ctr[RET_MINV] = max(65536 - a), ctr[RET_MAX1] = max(a + 1) (0: no posting; one atomic each per wave);
+// HIST: hist[d] += postings with a == d, through the workgroup's LDS window.  Every wave of a workgroup runs
+// every step whole (the ballots).
+template <bool HIST>
+__global__ __launch_bounds__(256) void k_ret_mark(const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                                  int nj, int64_t total, int min_day,
+                                                  unsigned long long* __restrict__ jage,
+                                                  unsigned long long* __restrict__ ctr,
+                                                  unsigned long long* __restrict__ hist) {
+  __shared__ uint32_t s_win[HIST ? RET_WIN : 1];
+  __shared__ int s_lo;
+  const int lane = threadIdx.x & 63;
+  int64_t begin, end;
+  host_span(total, &begin, &end);
+  if (HIST) {
+    for (int i = threadIdx.x; i < RET_WIN; i += blockDim.x) s_win[i] = 0;
+    if (threadIdx.x == 0) {
+      int lo = 0;
+      if (begin < end) {  // the window sits around the day of the span's first posting
+        const int c = seg_of(off, 0, nj - 1, begin);
+        lo = (int)row_lm(jobs[c].rows + (begin - off[c]) * YRWI_ROW_BYTES) - RET_WIN / 2;
+      }
+      s_lo = std::min(std::max(lo, 0), RET_DAYS - RET_WIN);
+    }
+    __syncthreads();
+  }
+  const int wlo = HIST ? s_lo : 0;
+  DayCursor cur;
+  int acc_c = -1;
+  uint32_t acc_n = 0;
+  int mn = RET_DAYS, mx = -1;
+  unsigned long long bypass = 0;  // the same in every lane of the wave
+  for (int64_t base = begin; base < end; base += HOST_TILE) {
+    int as[4], cs[4];
+    day_tile(cur, jobs, off, nj, total, base, end, as, cs);
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int a = as[u], c = cs[u];
+      const bool live = c >= 0;
+      const bool hit = live && a < min_day;
+      if (live) {
+        mn = std::min(mn, a);
+        mx = std::max(mx, a);
+      }
+      uint64_t act = __ballot(hit);
+      while (act) {
+        const int lead = __ffsll((unsigned long long)act) - 1;
+        const int lc = __shfl(c, lead, 64);
+        const uint64_t same = __ballot(hit && c == lc);
+        if (lc != acc_c) {
+          if (acc_n && lane == 0) atomicAdd(&jage[acc_c], (unsigned long long)acc_n);
+          acc_c = lc;
+          acc_n = 0;
+        }
+        acc_n += (uint32_t)__popcll(same);
+        act &= ~same;
+      }
+      if (HIST) {
+        act = __ballot(live);
+        // one day owns the wave's postings (lists written in one crawl): one add; else one per lane
+        const int lead = act ? __ffsll((unsigned long long)act) - 1 : 0;
+        const int la = __shfl(a, lead, 64);
+        const bool inwin = live && (unsigned)(a - wlo) < (unsigned)RET_WIN;
+        if (__ballot(live && a != la) == 0) {
+          const bool lin = (unsigned)(la - wlo) < (unsigned)RET_WIN;
+          if (act && lane == lead) {
+            if (lin)
+              atomicAdd(&s_win[la - wlo], (uint32_t)__popcll(act));
+            else
+              atomicAdd(&hist[la], (unsigned long long)__popcll(act));
+          }
+          if (!lin) bypass += (unsigned long long)__popcll(act);
+        } else {
+          if (inwin) atomicAdd(&s_win[a - wlo], 1u);
+          uint64_t left = __ballot(live && !inwin);
+          while (left) {  // equal days aggregated within the wave
+            const int pl = __ffsll((unsigned long long)left) - 1;
+            const int pa = __shfl(a, pl, 64);
+            const uint64_t same = __ballot(live && !inwin && a == pa);
+            if (lane == pl) atomicAdd(&hist[pa], (unsigned long long)__popcll(same));
+            bypass += (unsigned long long)__popcll(same);
+            left &= ~same;
+          }
+        }
+      }
+    }
+  }
+  if (acc_n && lane == 0) atomicAdd(&jage[acc_c], (unsigned long long)acc_n);
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    mn = std::min(mn, __shfl_xor(mn, d, 64));
+    mx = std::max(mx, __shfl_xor(mx, d, 64));
+  }
+  if (lane == 0 && mx >= 0) {
+    atomicMax(&ctr[RET_MINV], (unsigned long long)(RET_DAYS - mn));
+    atomicMax(&ctr[RET_MAX1], (unsigned long long)(mx + 1));
+  }
+  if (HIST) {
+    if (bypass && lane == 0) atomicAdd(&ctr[RET_BYPASS], bypass);
+    __syncthreads();
+    for (int i = threadIdx.x; i < RET_WIN; i += blockDim.x)
+      if (s_win[i]) atomicAdd(&hist[wlo + i], (unsigned long long)s_win[i]);
+  }
+}
+
+// Cut-day search, one level: bins[512 c + 256 (LEVEL - 1) + b] += survivors of capped list c (a >= min_day) whose
+// high byte is b (LEVEL 1), or whose high byte is the bucket level one chose (pick[2 c]) and whose low byte is
+// b (LEVEL 2).  Flattened over the capped lists' postings.
+template <int LEVEL>
+__global__ __launch_bounds__(256) void k_ret_bins(const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                                  int nj, int64_t total, int min_day,
+                                                  const int32_t* __restrict__ pick, uint32_t* __restrict__ bins) {
+  // a wave sums the bins of the list it is in (acc_c) in its own 256 words of LDS and adds the non-zero ones
+  // to the list's bins on leaving it: the days of a list fall into a few dozen high bytes, so a global atomic
+  // per (list, bin) per step would hammer those few words from every wave (DESIGN.md §2 has both timings).
+  // Only the wave touches its words, so no workgroup barrier is needed; the wave barriers keep the compiler
+  // from moving the plain stores and the atomics across each other.
+  __shared__ uint32_t s_bins[4][256];
+  const int lane = threadIdx.x & 63;
+  uint32_t* wb = s_bins[threadIdx.x >> 6];
+#pragma unroll
+  for (int k = 0; k < 4; k++) wb[lane + 64 * k] = 0;
+  __builtin_amdgcn_wave_barrier();
+  int acc_c = -1;
+  auto flush = [&]() {
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const uint32_t v = atomicExch(&wb[lane + 64 * k], 0u);
+      if (v) atomicAdd(&bins[(int64_t)acc_c * 512 + 256 * (LEVEL - 1) + lane + 64 * k], v);
+    }
+    __builtin_amdgcn_wave_barrier();
+  };
+  int64_t begin, end;
+  host_span(total, &begin, &end);
+  DayCursor cur;
+  int b1 = 0;
+  for (int64_t base = begin; base < end; base += HOST_TILE) {
+    int as[4], cs[4], bk[4];
+    if (LEVEL == 1) {
+      day_tile(cur, jobs, off, nj, total, base, end, as, cs);
+#pragma unroll
+      for (int u = 0; u < 4; u++) bk[u] = 0;
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; u++) {  // (day_tile, with the list's bucket looked up where the lane enters a list)
+        const int64_t i = base + u * 256 + threadIdx.x;
+        cs[u] = -1;
+        as[u] = -1;
+        bk[u] = 0;
+        if (i < end) {
+          day_seek(cur, jobs, off, nj, total, i);
+          if (cur.moved) b1 = pick[2 * (int64_t)cur.c];
+          cs[u] = cur.c;
+          bk[u] = b1;
+          as[u] = (int)row_lm(cur.rows + (i - cur.lo) * YRWI_ROW_BYTES);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int a = as[u], c = cs[u];
+      const bool in = c >= 0 && a >= min_day && (LEVEL == 1 || (a >> 8) == bk[u]);
+      const int b = (LEVEL == 1 ? a >> 8 : a) & 255;
+      uint64_t left = __ballot(in);
+      while (left) {  // the wave's lists ascend: list by list
+        const int pl = __ffsll((unsigned long long)left) - 1;
+        const int lc = __shfl(c, pl, 64);
+        const bool mine = in && c == lc;
+        const uint64_t same = __ballot(mine);
+        if (lc != acc_c) {
+          if (acc_c >= 0) flush();
+          acc_c = lc;
+        }
+        // one bin owns the list's rows of this step: one LDS add; else one per lane
+        const int lb = __shfl(b, pl, 64);
+        if (__ballot(mine && b != lb) == 0) {
+          if (lane == pl) atomicAdd(&wb[lb], (uint32_t)__popcll(same));
+        } else if (mine) {
+          atomicAdd(&wb[b], 1u);
+        }
+        left &= ~same;
+      }
+    }
+  }
+  if (acc_c >= 0) flush();
+}
+
+// The bins of one level -> the bucket that holds the K-th largest survivor, one thread per capped list.
+// LEVEL 1: K = max_refs; pick[2 c] = the high byte, pick[2 c + 1] = K - survivors in the buckets above.
+// LEVEL 2: K = pick[2 c + 1]; cut[sel[c]] = (d*, q): the cut day and how many of its rows stay.
+template <int LEVEL>
+__global__ void k_ret_pick(int ncap, const uint32_t* __restrict__ bins, int32_t max_refs, int32_t* __restrict__ pick,
+                           const int32_t* __restrict__ sel, int2* __restrict__ cut) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncap) return;
+  const uint32_t* b = bins + (int64_t)c * 512 + 256 * (LEVEL - 1);
+  const int64_t K = LEVEL == 1 ? max_refs : pick[2 * (int64_t)c + 1];
+  int64_t above = 0;
+  int at = 0;  // (the host has counted at least max_refs survivors: a bucket is found)
+  for (int k = 255; k >= 0; k--) {
+    const int64_t n = b[k];
+    if (above + n >= K) {
+      at = k;
+      break;
+    }
+    above += n;
+  }
+  if (LEVEL == 1) {
+    pick[2 * (int64_t)c] = at;
+    pick[2 * (int64_t)c + 1] = (int32_t)(K - above);
+  } else {
+    cut[sel[c]] = make_int2((pick[2 * (int64_t)c] << 8) | at, (int32_t)(K - above));
+  }
+}
+
+// The flag kernels of a compaction chunk.  MODE 0 (no cap): keep[i] = a >= min_day.  MODE 1: out[i] = posting
+// i survives the age rule and sits on its list's cut day.  MODE 2: keep[i] = a >= min_day && (a > d* ||
+// (a == d* && rank < q)), rank = tx[i] - tx[the list's first posting], tx = the exclusive sum of MODE 1's
+// marks; a list without a cut (d* < 0) keeps its survivors.  out[total] = 0 (the scan's last element).
+template <int MODE>
+__global__ __launch_bounds__(256) void k_ret_flag(const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                                  int nj, int64_t total, int min_day, const int2* __restrict__ cut,
+                                                  const int32_t* __restrict__ sel, const int64_t* __restrict__ tx,
+                                                  int32_t* __restrict__ out) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) out[total] = 0;
+  int64_t begin, end;
+  host_span(total, &begin, &end);
+  DayCursor cur;
+  int2 dq = make_int2(-1, 0);
+  int64_t tbase = 0;
+  for (int64_t base = begin; base < end; base += HOST_TILE) {
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int64_t i = base + u * 256 + threadIdx.x;
+      if (i >= end) continue;
+      day_seek(cur, jobs, off, nj, total, i);
+      if (MODE != 0 && cur.moved) {
+        dq = cut[sel[cur.c]];
+        if (MODE == 2) tbase = tx[cur.lo];
+      }
+      const int a = (int)row_lm(cur.rows + (i - cur.lo) * YRWI_ROW_BYTES);
+      const bool surv = a >= min_day;
+      if (MODE == 0)
+        out[i] = surv;
+      else if (MODE == 1)
+        out[i] = surv && a == dq.x;
+      else
+        out[i] = surv && (dq.x < 0 || a > dq.x || (a == dq.x && tx[i] - tbase < (int64_t)dq.y));
+    }
+  }
+}
+
+// both calls: the selection, the age pass and what the host derives from its per-list counts; apply: the
+// cut-day search and the compaction
+int retention(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, int32_t min_day, int64_t max_refs,
+              int64_t* day_hist, bool apply, yrwi_update_stats* st, yrwi_retention_stats* rst) {
+  if (!ctx || nterms < 0 || (nterms > 0 && !terms12)) return YRWI_E_ARG;
+  if (min_day < 0 || min_day > RET_DAYS) return ctx->fail(YRWI_E_ARG, "min_day outside 0 .. 65536");
+  if (max_refs < 0) return ctx->fail(YRWI_E_ARG, "max_refs below 0");
+  if (max_refs > 0 && ctx->world > 1)
+    return ctx->fail(YRWI_E_UNSUPPORTED, "the cap is of the whole container: not on a context of a shard group");
+  const auto t_begin = std::chrono::steady_clock::now();
+  yrwi_update_stats S;
+  std::memset(&S, 0, sizeof(S));
+  yrwi_retention_stats R;
+  std::memset(&R, 0, sizeof(R));
+  R.day_min = R.day_max = -1;
+  Tally T;
+  ListSel sel;
+  if (int rc = select_lists(ctx, terms12, nterms, false, &sel)) return rc;
+  if (st) std::memset(st, 0, sizeof(*st));
+  if (day_hist) std::memset(day_hist, 0, sizeof(int64_t) * RET_DAYS);
+  RmTable t;
+  rm_table(sel, &t);
+  auto finish = [&]() {
+    R.launches = T.launches;
+    R.syncs = T.syncs;
+    R.t_total_ns =
+        std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_begin).count();
+    if (rst) *rst = R;
+    put_stats(st, S, T);
+    return 0;
+  };
+  if (t.jobs.empty() || (min_day == 0 && max_refs == 0 && !day_hist)) return finish();
+  const int nj = (int)t.jobs.size();
+  const int64_t total = t.total;
+  const bool hist = day_hist != nullptr;
+  Lane* L = ctx->lanes[0];
+  if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
+  T.syncs++;
+  // ---- the age pass: per-list counts, the day range, the bypass count and the histogram in one block, read back once
+  const int64_t nres = (int64_t)nj + RET_WORDS + (hist ? RET_DAYS : 0);
+  RmJob* d_jobs = arena_alloc<RmJob>(L, nj);
+  int64_t* d_off = arena_alloc<int64_t>(L, nj);
+  unsigned long long* res = arena_alloc<unsigned long long>(L, nres);
+  if (!d_jobs || !d_off || !res) return ctx->fail(YRWI_E_NOMEM, "device allocation (retention age pass)");
+  if (int rc = upload(L, d_jobs, t.jobs, d_off, t.off)) return ctx->take(L, rc);
+  HIPCHK(ctx, hipMemsetAsync(res, 0, (size_t)nres * 8, L->stream));
+  hipEvent_t e0 = L->event(), e1 = L->event(), e2 = L->event(), e3 = L->event();
+  HIPCHK(ctx, hipEventRecord(e0, L->stream));
+  {
+    const dim3 g(mark_blocks(total)), b(256);
+    unsigned long long* ctr = res + nj;
+    if (hist)
+      hipLaunchKernelGGL((k_ret_mark<true>), g, b, 0, L->stream, d_jobs, d_off, nj, total, min_day, res, ctr, ctr + RET_WORDS);
+    else
+      hipLaunchKernelGGL((k_ret_mark<false>), g, b, 0, L->stream, d_jobs, d_off, nj, total, min_day, res, ctr, ctr + RET_WORDS);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipEventRecord(e1, L->stream));
+  const int64_t* h = reinterpret_cast<const int64_t*>(readback(L, &L->down_stage, res, nres, 8, 8));
+  if (!h) return ctx->take(L, YRWI_E_HIP);
+  T.launches += 4;
+  HIPCHK(ctx, lane_sync(L));
+  T.syncs++;
+  float msf = 0.f;
+  if (hipEventElapsedTime(&msf, e0, e1) == hipSuccess) R.t_mark_ns = (int64_t)((double)msf * 1e6);
+  // ---- every list's final length: rem = age + max(0, n - age - max_refs)
+  std::vector<int64_t> rem((size_t)nj);
+  std::vector<RmJob> capj;
+  std::vector<int64_t> capoff;  // (one entry more than lists: the total)
+  std::vector<int32_t> capsel;
+  int64_t ctotal = 0;
+  R.lists = nj;
+  R.postings = total;
+  R.day_min = h[nj + RET_MINV] ? (int32_t)(RET_DAYS - h[nj + RET_MINV]) : -1;
+  R.day_max = (int32_t)h[nj + RET_MAX1] - 1;
+  R.hist_bypass = h[nj + RET_BYPASS];
+  if (hist) std::memcpy(day_hist, h + nj + RET_WORDS, sizeof(int64_t) * RET_DAYS);
+  for (int j = 0; j < nj; j++) {
+    const int64_t n = t.jobs[(size_t)j].n, age = h[j];
+    const int64_t over = max_refs > 0 ? std::max<int64_t>(0, n - age - max_refs) : 0;
+    rem[(size_t)j] = age + over;
+    R.removed_age += age;
+    R.removed_cap += over;
+    R.lists_age += age > 0;
+    R.lists_cap += over > 0;
+    R.emptied_terms += age == n;
+    if (over > 0 && apply) {
+      capj.push_back(t.jobs[(size_t)j]);
+      capoff.push_back(ctotal);
+      capsel.push_back(j);
+      ctotal += n;
+    }
+  }
+  capoff.push_back(ctotal);
+  if (!apply) return finish();
+  // ---- the cut day and the quota of every list over the cap, left on the device
+  int2* cut = nullptr;
+  if (max_refs > 0) {
+    const int ncap = (int)capj.size();
+    const int64_t nb = (int64_t)std::max(ncap, 1) * 512;
+    RmJob* d_capj = arena_alloc<RmJob>(L, ncap);
+    int64_t* d_capoff = arena_alloc<int64_t>(L, ncap + 1);
+    int32_t* d_capsel = arena_alloc<int32_t>(L, ncap);
+    uint32_t* bins = arena_alloc<uint32_t>(L, nb);
+    int32_t* pick = arena_alloc<int32_t>(L, 2 * (int64_t)ncap);
+    cut = arena_alloc<int2>(L, nj);
+    if (!d_capj || !d_capoff || !d_capsel || !bins || !pick || !cut)
+      return ctx->fail(YRWI_E_NOMEM, "device allocation (retention cut-day search)");
+    if (int rc = upload(L, d_capj, capj, d_capoff, capoff, d_capsel, capsel)) return ctx->take(L, rc);
+    HIPCHK(ctx, hipMemsetAsync(bins, 0, (size_t)nb * 4, L->stream));
+    HIPCHK(ctx, hipMemsetAsync(cut, 0xFF, (size_t)nj * sizeof(int2), L->stream));  // d* = -1: no cut
+    HIPCHK(ctx, hipEventRecord(e2, L->stream));
+    const dim3 g(std::max(mark_blocks(ctotal), 1u)), gp(std::max(blocks(ncap), 1u)), b(256);
+    const int32_t K = (int32_t)std::min<int64_t>(max_refs, INT32_MAX);  // (a capped list is longer than max_refs)
+    hipLaunchKernelGGL((k_ret_bins<1>), g, b, 0, L->stream, d_capj, d_capoff, ncap, ctotal, min_day, pick, bins);
+    hipLaunchKernelGGL((k_ret_pick<1>), gp, b, 0, L->stream, ncap, bins, K, pick, d_capsel, cut);
+    hipLaunchKernelGGL((k_ret_bins<2>), g, b, 0, L->stream, d_capj, d_capoff, ncap, ctotal, min_day, pick, bins);
+    hipLaunchKernelGGL((k_ret_pick<2>), gp, b, 0, L->stream, ncap, bins, K, pick, d_capsel, cut);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(e3, L->stream));
+    T.launches += 7;
+  }
+  // ---- compaction: with a cap a chunk is flagged in two steps (the cut-day marks scanned for the ranks)
+  hipError_t ferr = hipSuccess;
+  auto flag = [&](const RmJob* dj, const int64_t* doff, int ncj, int64_t n, int32_t* keep, const ChunkAux& x) {
+    const dim3 g(mark_blocks(n)), b(256);
+    if (max_refs == 0) {
+      hipLaunchKernelGGL((k_ret_flag<0>), g, b, 0, L->stream, dj, doff, ncj, n, min_day, cut, x.sel, x.kx, keep);
+      return;
+    }
+    hipLaunchKernelGGL((k_ret_flag<1>), g, b, 0, L->stream, dj, doff, ncj, n, min_day, cut, x.sel, x.kx, keep);
+    size_t tb = x.tb;
+    const hipError_t e = hipcub::DeviceScan::ExclusiveSum(x.tmp, tb, keep, x.kx, (int)(n + 1), L->stream);
+    if (e != hipSuccess) ferr = e;
+    hipLaunchKernelGGL((k_ret_flag<2>), g, b, 0, L->stream, dj, doff, ncj, n, min_day, cut, x.sel, x.kx, keep);
+    T.launches += 2;
+  };
+  const int32_t syncs0 = T.syncs;
+  if (int rc = compact_commit(ctx, L, t, rem, "device allocation (retention compaction)", flag, &S, &T, true)) return rc;
+  if (ferr != hipSuccess) return ctx->fail(YRWI_E_HIP, std::string("retention rank scan: ") + hipGetErrorString(ferr));
+  if (max_refs > 0 && T.syncs > syncs0 && hipEventElapsedTime(&msf, e2, e3) == hipSuccess)
+    R.t_select_ns = (int64_t)((double)msf * 1e6);
+  return finish();
+}
+
+}  // namespace
+
+extern "C" int yrwi_retention_count(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, int32_t min_day,
+                                    int64_t max_refs, int64_t* day_hist, yrwi_retention_stats* st) {
+  return retention(ctx, terms12, nterms, min_day, max_refs, day_hist, false, nullptr, st);
+}
+
+extern "C" int yrwi_retain(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, int32_t min_day, int64_t max_refs,
+                           yrwi_update_stats* st, yrwi_retention_stats* rst) {
+  return retention(ctx, terms12, nterms, min_day, max_refs, nullptr, true, st, rst);
 }

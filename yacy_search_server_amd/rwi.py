@@ -449,6 +449,44 @@ class RWIIndex:
         return ([bytes(h) for h in hosts[:n.value]], counts[:n.value].copy(),
                 {f: getattr(st, f) for f, _ in _lib.CCensusStats._fields_})
 
+    @staticmethod
+    def _retention_noop() -> dict:
+        st = {f: 0 for f, _ in _lib.CRetentionStats._fields_}
+        st["day_min"] = st["day_max"] = -1
+        return st
+
+    def retention_count(self, min_day: int = 0, max_refs: int = 0, terms: Optional[Sequence[bytes]] = None,
+                        hist: bool = False) -> Tuple[dict, Optional[np.ndarray]]:
+        """What retain(min_day, max_refs, terms) would remove, the index unchanged
+        (yrwi_retention_count): the call's yrwi_retention_stats as a dict and, with hist=True, the
+        65,536-entry int64 histogram of the selected rows' lastModified days before any rule (else
+        None): what a caller picks the min_day from that reaches a target size."""
+        tb = np.frombuffer(_hashes(terms or ()), dtype=np.uint8)
+        h = np.zeros(_lib.RETENTION_DAYS, dtype=np.int64) if hist else None
+        if terms is not None and len(terms) == 0:
+            return self._retention_noop(), h  # no term named (nterms == 0 would mean every list)
+        st = _lib.CRetentionStats()
+        _check(self._h, _lib.lib().yrwi_retention_count(self._h, tb.ctypes.data if len(tb) else None, len(tb) // 12,
+                                                        min_day, max_refs, h.ctypes.data if hist else None,
+                                                        ctypes.byref(st)))
+        return {f: getattr(st, f) for f, _ in _lib.CRetentionStats._fields_}, h
+
+    def retain(self, min_day: int = 0, max_refs: int = 0,
+               terms: Optional[Sequence[bytes]] = None) -> Tuple[dict, dict]:
+        """Retention on the device (yrwi_retain): from the lists of `terms`, or with terms=None from
+        every list, removes every posting whose lastModified day is below min_day (0: no age rule),
+        then leaves a list that still has more than max_refs rows (0: no cap) its max_refs newest,
+        equal days at the cut kept in url-hash order.  No list leaves the device.  Returns the
+        call's yrwi_update_stats and yrwi_retention_stats as dicts."""
+        tb = np.frombuffer(_hashes(terms or ()), dtype=np.uint8)
+        if terms is not None and len(terms) == 0:
+            return {f: 0 for f, _ in _lib.CUpdateStats._fields_}, self._retention_noop()  # no term named
+        st, rst = _lib.CUpdateStats(), _lib.CRetentionStats()
+        _check(self._h, _lib.lib().yrwi_retain(self._h, tb.ctypes.data if len(tb) else None, len(tb) // 12,
+                                               min_day, max_refs, ctypes.byref(st), ctypes.byref(rst)))
+        return ({f: getattr(st, f) for f, _ in _lib.CUpdateStats._fields_},
+                {f: getattr(rst, f) for f, _ in _lib.CRetentionStats._fields_})
+
     def load_heaps(self, paths: Sequence[str], order_by_name: bool = False) -> "_lib.CLoadStats":
         """Load YaCy BLOB heap files (IndexCell's ReferenceContainerArray) into the index;
         lists already present act as the RAM cache (the files' rows win)."""
