@@ -9,6 +9,8 @@ what its name says; tests/test_gpu_abstracts_adversarial.py feeds the same input
 
 compress_cases() / multi_term()   lists for yrwi_index_abstracts (compressIndex)
 join_cases()                      abstracts for yrwi_secondary_search that the oracle accepts
+peer_abstracts() / oracle_plan()  random well-formed abstracts of several peers (the caller's generator),
+                                  and the oracle's join and plan for any abstracts
 refusal_cases()                   abstracts that must be refused
 wrap_case()                       the one large input: a map of 2,147,484 urls
 expected()                        the oracle's answer in the shape RWIIndex.secondary_search returns
@@ -60,6 +62,26 @@ def row_list(rows):
 
 def hashes(rows):
     return [bytes(r[:12]) for r in rows]
+
+
+def peer_abstracts(rng, words, npeers, base):
+    """every peer holds a random part of each word's url universe; arrival order shuffled"""
+    peers = sorted({bytes(B64[int(x)] for x in rng.integers(0, 64, 12)) for _ in range(npeers)})
+    out = []
+    for p in peers:
+        for w in words:
+            sel = [u for u in base[w] if rng.random() < 0.4]
+            out.append((w, p, ab.compress_index([u + bytes(28) for u in sel])))
+    order = rng.permutation(len(out))
+    return [out[i] for i in order], peers
+
+
+def oracle_plan(abstracts, words, mypeer, checked=()):
+    s = ab.SecondarySearch()
+    s.checked = set(checked)
+    for w, p, t in abstracts:
+        s.add_abstract(w, ab.decompress_index(t, p))
+    return s.prepare(words, mypeer)
 
 
 # ------------------------------------------------------------------ compressIndex

@@ -11,6 +11,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 import heap
+import index_util as iu
 
 MS_2000 = 946684800000  # 2000-01-01T00:00:00Z
 REC_HDR = 4 + heap.KEYLEN + heap.EXPORT_OVERHEAD  # reclen, key, export header: 30 bytes
@@ -95,7 +96,6 @@ SIZES = _sizes()  # list sizes of the hand-made fixture, in term order
 
 def fixture_lists(idx) -> Dict[bytes, np.ndarray]:
     """len(SIZES) hand-made lists: rows of the synthetic index `idx` as templates, url hashes set
-    as test_gpu_updates._rows does"""
-    import test_gpu_updates as tu
-    return {tu._term(5000 + 7 * i): tu._rows(idx, [tu._url(k) for k in range(n)], start=i)
+    as index_util.rows does"""
+    return {iu.term(5000 + 7 * i): iu.rows(idx, [iu.url(k) for k in range(n)], start=i)
             for i, n in enumerate(SIZES)}

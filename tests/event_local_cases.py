@@ -3,7 +3,10 @@ exercise the cases) and test_gpu_event_local.py (GPU: yrwi_event_add_local / yrw
 against the host path and the oracle).
 
 A shape names a preset, include and exclude terms by size rank, and the rows its container
-has before and after the exclusion (asserted against the oracle by the CPU test)."""
+has before and after the exclusion (asserted against the oracle by the CPU test).
+
+arrivals() and check_event() are the random arrival sequences and the event check of
+tests/test_events.py, kept here for the other tests that feed events."""
 
 import functools
 
@@ -11,7 +14,7 @@ import numpy as np
 
 import java_literal as jl
 import oracle as orc
-from yacy_search_server_amd import synth
+from yacy_search_server_amd import QueryFilter, RankingProfile, synth
 
 DAY = 86400000
 NOW = 20741 * DAY + 31337
@@ -75,10 +78,69 @@ def rows_list(a):
     return [bytes(r) for r in np.asarray(a, dtype=np.uint8).reshape(-1, 40)]
 
 
+def arrivals(idx, rng, n_remote, local_term=None, zero_pos=False, big=False):
+    """local container (a whole posting list, sorted) + remote containers built
+    from random rows of random lists (same url under other words: different
+    features), shuffled (arrival order), with duplicates inside an arrival."""
+    out = []
+    if local_term is not None:
+        out.append((np.array(idx.list_rows(local_term)), True))
+    all_rows = np.asarray(idx.rows, dtype=np.uint8)
+    for _ in range(n_remote):
+        m = int(rng.integers(0, 3000 if big else 200))
+        take = rng.integers(0, len(all_rows), m)
+        if m > 4:
+            take[: m // 4] = take[rng.integers(0, m, m // 4)]  # duplicates inside the arrival
+        r = all_rows[take].copy()
+        if m:  # word distances (the 'i' column), so the max-distance fold has work
+            d = rng.random(m) < 0.5
+            r[d, 38] = rng.integers(0, 40, int(d.sum()))
+        if zero_pos and m:
+            z = rng.random(m) < 0.3
+            r[z, 34] = 0
+            r[z, 35] = 0
+        out.append((r, False))
+    return out
+
+
 def remote_arrivals(preset, seed, n_remote=6):
-    """n_remote remote containers built as tests/test_events.py::_arrivals builds them (big)"""
-    from test_events import _arrivals
-    return [r for r, _ in _arrivals(corpus(preset)[1], np.random.default_rng(seed), n_remote, big=True)]
+    """n_remote remote containers built as arrivals() builds them (big)"""
+    return [r for r, _ in arrivals(corpus(preset)[1], np.random.default_rng(seed), n_remote, big=True)]
+
+
+def check_event(ix, arrivals, profile_fields=None, kw=None, k=100, language="en"):
+    """the arrivals into one event of the index and into java_literal.SearchEventRWI: the stack, the
+    tiebreaks and every yrwi_event_info field must agree (a plain module: every assert names its operands)"""
+    lp = jl.RankingProfile()
+    gp = RankingProfile()
+    for f, v in (profile_fields or {}).items():
+        setattr(lp, f, v)
+        setattr(gp, f, v)
+    lf = jl.QueryFilter(**(kw or {}))
+    gf = QueryFilter(**(kw or {})) if kw is not None else None
+    ref = jl.SearchEventRWI(lp, language, NOW, filt=lf)
+    total = sum(len(r) for r, _ in arrivals)
+    with ix.event(gp, language, NOW, k=k, filter=gf, max_postings=total + 16) as ev:
+        for rows, local in arrivals:
+            ref.add_rwis(rows_list(rows), local)
+            ev.add_rwis(rows, local)
+        hits, info = ev.results()
+    exp = ref.stack()[:k]
+    got = [(h.urlhash, h.score) for h in hits]
+    i = next((j for j, (a, b) in enumerate(zip(got, exp)) if a != b), min(len(got), len(exp)))
+    assert got == exp, ("stack", len(got), len(exp), "first difference at", i, got[i:i + 2], exp[i:i + 2])
+    ties = [h.tiebreak for h in hits]
+    want = [jl.bytearray_hashcode(u) for u, _ in exp]
+    assert ties == want, ("tiebreaks", [(j, a, b) for j, (a, b) in enumerate(zip(ties, want)) if a != b][:4])
+    assert list(info.flagcount) == lf.flagcount, (list(info.flagcount), lf.flagcount)
+    assert info.postings_in == total, (info.postings_in, total)
+    assert info.admitted_remote == ref.remote_available, (info.admitted_remote, ref.remote_available)
+    assert info.admitted_local == ref.local_available, (info.admitted_local, ref.local_available)
+    assert info.remote_arrivals == ref.remote_peers, (info.remote_arrivals, ref.remote_peers)
+    mx = ref.order.max
+    assert info.max_distance == (mx.distance() if mx is not None else 0), (info.max_distance, mx and mx.distance())
+    if lp.coeff_authority > 12:
+        assert info.maxdomcount == ref.order.maxdomcount, (info.maxdomcount, ref.order.maxdomcount)
 
 
 def info_of(ref, total):

@@ -23,6 +23,7 @@ import functools
 import numpy as np
 
 import java_literal as jl
+from abstract_cases import peer_abstracts
 from adv_rows import adv_rows, url_keys
 
 KHI_EDGES = (0, 1, 2, (1 << 63) - 1, 1 << 63, (1 << 63) + 1, (1 << 64) - 2, (1 << 64) - 1)
@@ -283,13 +284,12 @@ def heap_input(seed: int = SEED + 7):
 def abstract_input(seed: int = SEED + 11, npeers: int = 9):
     """-> (words, base, abstracts (word, peer, text) in shuffled arrival order, peers): three words
     over the urls of every fourth family; every peer holds a random 40 % of each word's urls
-    (test_abstracts._peer_abstracts), so peers hold different siblings and several peers one url"""
-    from test_abstracts import _peer_abstracts
+    (abstract_cases.peer_abstracts), so peers hold different siblings and several peers one url"""
     rng = np.random.default_rng(seed)
     urls = [h for fam in by_family(universe())[::4] for h in fam]
     words = sorted(b"WORDspk%d____" % i for i in range(3))
     base = {w: sorted(u for u in urls if rng.random() < 0.8) for w in words}
-    abstracts, peers = _peer_abstracts(rng, words, npeers, base)
+    abstracts, peers = peer_abstracts(rng, words, npeers, base)
     return words, base, abstracts, peers
 
 

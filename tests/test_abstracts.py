@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import abstracts as ab
+from abstract_cases import oracle_plan, peer_abstracts
 from yacy_search_server_amd import synth
 
 ALPHA = b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789-_"
@@ -106,26 +107,6 @@ def test_index_abstracts_gpu():
         ix.close()
 
 
-def _peer_abstracts(rng, words, npeers, base):
-    """every peer holds a random part of each word's url universe; arrival order shuffled"""
-    peers = sorted({bytes(ALPHA[int(x)] for x in rng.integers(0, 64, 12)) for _ in range(npeers)})
-    out = []
-    for p in peers:
-        for w in words:
-            sel = [u for u in base[w] if rng.random() < 0.4]
-            out.append((w, p, ab.compress_index([_row(u) for u in sel])))
-    order = rng.permutation(len(out))
-    return [out[i] for i in order], peers
-
-
-def _oracle_plan(abstracts, words, mypeer, checked=()):
-    s = ab.SecondarySearch()
-    s.checked = set(checked)
-    for w, p, t in abstracts:
-        s.add_abstract(w, ab.decompress_index(t, p))
-    return s.prepare(words, mypeer)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed", [0, 1])
 def test_secondary_search_gpu(seed):
@@ -134,12 +115,12 @@ def test_secondary_search_gpu(seed):
     words = sorted(bytes(ALPHA[int(x)] for x in rng.integers(0, 64, 12)) for _ in range(3))
     common = _urls(rng, 3000, 40)
     base = {w: sorted(set(common[: 2000]) | set(_urls(rng, 1500, 30))) for w in words}
-    abstracts, peers = _peer_abstracts(rng, words, 9, base)
+    abstracts, peers = peer_abstracts(rng, words, 9, base)
     ix = RWIIndex(0)
     try:
         for mypeer, checked in ((peers[0], ()), (b"notapeer____", peers[1:3])):
             join, wl, plan = ix.secondary_search(abstracts, len(words), mypeer, checked)
-            ejoin, eplan = _oracle_plan(abstracts, words, mypeer, checked)
+            ejoin, eplan = oracle_plan(abstracts, words, mypeer, checked)
             assert wl == words
             assert join == [(u, next(iter(ejoin[u]))) for u in sorted(ejoin)]
             assert plan == eplan
@@ -148,7 +129,7 @@ def test_secondary_search_gpu(seed):
         # a text without braces contributes nothing; a malformed one is refused
         extra = abstracts + [(words[0], peers[1], b"xx:AAAAAA")]
         join, _, plan = ix.secondary_search(extra, len(words), peers[0])
-        ejoin, eplan = _oracle_plan(extra, words, peers[0])
+        ejoin, eplan = oracle_plan(extra, words, peers[0])
         assert plan == eplan and len(join) == len(ejoin)
         from yacy_search_server_amd._lib import YrwiError
         with pytest.raises(YrwiError):

@@ -18,13 +18,8 @@ import numpy as np
 import pytest
 
 import java_literal as jl
-from yacy_search_server_amd import QueryFilter, RankingProfile, synth
-
-NOW = 20741 * 86400000 + 31337
-
-
-def _rows(a):
-    return [bytes(r) for r in np.asarray(a, dtype=np.uint8).reshape(-1, 40)]
+from event_local_cases import NOW, arrivals, check_event, rows_list
+from yacy_search_server_amd import RankingProfile, synth
 
 
 def _pool():
@@ -33,35 +28,10 @@ def _pool():
     return cfg, idx
 
 
-def _arrivals(idx, rng, n_remote, local_term=None, zero_pos=False, big=False):
-    """local container (a whole posting list, sorted) + remote containers built
-    from random rows of random lists (same url under other words: different
-    features), shuffled (arrival order), with duplicates inside an arrival."""
-    out = []
-    if local_term is not None:
-        out.append((np.array(idx.list_rows(local_term)), True))
-    all_rows = np.asarray(idx.rows, dtype=np.uint8)
-    for _ in range(n_remote):
-        m = int(rng.integers(0, 3000 if big else 200))
-        take = rng.integers(0, len(all_rows), m)
-        if m > 4:
-            take[: m // 4] = take[rng.integers(0, m, m // 4)]  # duplicates inside the arrival
-        r = all_rows[take].copy()
-        if m:  # word distances (the 'i' column), so the max-distance fold has work
-            d = rng.random(m) < 0.5
-            r[d, 38] = rng.integers(0, 40, int(d.sum()))
-        if zero_pos and m:
-            z = rng.random(m) < 0.3
-            r[z, 34] = 0
-            r[z, 35] = 0
-        out.append((r, False))
-    return out
-
-
 def test_single_local_arrival_equals_rank():
     _, idx = _pool()
     t = int(np.argmax(idx.sizes))
-    c = _rows(idx.list_rows(t))
+    c = rows_list(idx.list_rows(t))
     ev = jl.SearchEventRWI(jl.RankingProfile(), "en", NOW)
     ev.add_rwis(c, True)
     assert ev.stack() == jl.rank(c, jl.RankingProfile(), "en", NOW)
@@ -70,8 +40,8 @@ def test_single_local_arrival_equals_rank():
 def test_later_arrivals_keep_their_scores_and_doublecheck():
     _, idx = _pool()
     order = np.argsort(-idx.sizes)
-    a = _rows(idx.list_rows(int(order[0])))
-    b = _rows(idx.list_rows(int(order[1])))
+    a = rows_list(idx.list_rows(int(order[0])))
+    b = rows_list(idx.list_rows(int(order[1])))
     ev = jl.SearchEventRWI(jl.RankingProfile(), "en", NOW)
     ev.add_rwis(a, True)
     first = dict(ev.stack())
@@ -103,35 +73,6 @@ def test_bounded_treeset_is_topk_of_earliest_classes():
         assert [(x[0], x[2]) for x in ref] == [(w, h) for (w, _, h) in q.items], trial
 
 
-def _check_event(ix, arrivals, profile_fields=None, kw=None, k=100, language="en"):
-    lp = jl.RankingProfile()
-    gp = RankingProfile()
-    for f, v in (profile_fields or {}).items():
-        setattr(lp, f, v)
-        setattr(gp, f, v)
-    lf = jl.QueryFilter(**(kw or {}))
-    gf = QueryFilter(**(kw or {})) if kw is not None else None
-    ref = jl.SearchEventRWI(lp, language, NOW, filt=lf)
-    total = sum(len(r) for r, _ in arrivals)
-    with ix.event(gp, language, NOW, k=k, filter=gf, max_postings=total + 16) as ev:
-        for rows, local in arrivals:
-            ref.add_rwis(_rows(rows), local)
-            ev.add_rwis(rows, local)
-        hits, info = ev.results()
-    exp = ref.stack()[:k]
-    assert [(h.urlhash, h.score) for h in hits] == exp
-    assert [h.tiebreak for h in hits] == [jl.bytearray_hashcode(u) for u, _ in exp]
-    assert list(info.flagcount) == lf.flagcount
-    assert info.postings_in == total
-    assert info.admitted_remote == ref.remote_available
-    assert info.admitted_local == ref.local_available
-    assert info.remote_arrivals == ref.remote_peers
-    mx = ref.order.max
-    assert info.max_distance == (mx.distance() if mx is not None else 0)
-    if lp.coeff_authority > 12:
-        assert info.maxdomcount == ref.order.maxdomcount
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed", [0, 1, 2])
 def test_event_arrivals_bit_exact(seed):
@@ -141,10 +82,10 @@ def test_event_arrivals_bit_exact(seed):
     order = np.argsort(-idx.sizes)
     ix = RWIIndex(0)
     try:
-        arr = _arrivals(idx, rng, 12, local_term=int(order[seed]), zero_pos=(seed == 1))
-        _check_event(ix, arr)
-        _check_event(ix, arr, {"coeff_authority": 14, "coeff_worddistance": 15}, k=3000)
-        _check_event(ix, arr[1:], {"coeff_date": 15, "coeff_posintext": 13}, k=10)
+        arr = arrivals(idx, rng, 12, local_term=int(order[seed]), zero_pos=(seed == 1))
+        check_event(ix, arr)
+        check_event(ix, arr, {"coeff_authority": 14, "coeff_worddistance": 15}, k=3000)
+        check_event(ix, arr[1:], {"coeff_date": 15, "coeff_posintext": 13}, k=10)
     finally:
         ix.close()
 
@@ -154,16 +95,16 @@ def test_event_multichunk_and_filters():
     from yacy_search_server_amd import RWIIndex
     _, idx = _pool()
     rng = np.random.default_rng(11)
-    arr = _arrivals(idx, rng, 6, big=True, zero_pos=True)
+    arr = arrivals(idx, rng, 6, big=True, zero_pos=True)
     hosts = sorted({bytes(r[6:12]) for r in np.asarray(idx.rows)[rng.integers(0, len(idx.rows), 80)]})
     seeds = [bytes(r[:12]) for r in np.asarray(idx.rows)[rng.integers(0, len(idx.rows), 50)]]
     ix = RWIIndex(0)
     try:
-        _check_event(ix, arr, k=3000)
+        check_event(ix, arr, k=3000)
         for kw in (dict(constraint=b"\0\0\x10\x01"), dict(language="de"), dict(siteexcludes=hosts),
                    dict(sitehash=hosts[0], alt_sitehash=hosts[1]), dict(urlhashes=seeds, contentdom=1),
                    dict(constraint=b"\x01\0\0\0", all_of_constraint=True, strict_contentdom=True, contentdom=2)):
-            _check_event(ix, arr, {"coeff_authority": 13}, kw=kw, k=200)
+            check_event(ix, arr, {"coeff_authority": 13}, kw=kw, k=200)
     finally:
         ix.close()
 
@@ -178,7 +119,7 @@ def test_many_events_one_launch():
         nev = 40
         evs, refs, seqs = [], [], []
         for e in range(nev):
-            arr = _arrivals(idx, rng, int(rng.integers(1, 6)))
+            arr = arrivals(idx, rng, int(rng.integers(1, 6)))
             seqs.append(arr)
             evs.append(ix.event(None, "en", NOW, k=50, max_postings=sum(len(r) for r, _ in arr) + 16))
             refs.append(jl.SearchEventRWI(jl.RankingProfile(), "en", NOW))
@@ -191,7 +132,7 @@ def test_many_events_one_launch():
                 for _ in range(take):
                     if seqs[e]:
                         rows, local = seqs[e].pop(0)
-                        refs[e].add_rwis(_rows(rows), local)
+                        refs[e].add_rwis(rows_list(rows), local)
                         batch.append((evs[e], rows, local))
             ix.add_rwis(batch)
             step += 1
@@ -240,8 +181,8 @@ def test_oracle_pull_matches_settled_restatement():
     _, idx = _pool()
     rng = np.random.default_rng(5)
     ref = jl.SearchEventRWI(jl.RankingProfile(), "en", NOW, maxsize=400)
-    for rows, local in _arrivals(idx, rng, 8, big=True):
-        ref.add_rwis(_rows(rows), local)
+    for rows, local in arrivals(idx, rng, 8, big=True):
+        ref.add_rwis(rows_list(rows), local)
     st = ref.stack()
     exp = jl.pull_double_dom(st, len(st))
     got = []
@@ -265,7 +206,7 @@ def _pull_script(ix, arrivals, steps, k, profile_fields=None):
     total = sum(len(r) for r, _ in arrivals)
     with ix.event(gp, "en", NOW, k=k, max_postings=total + 16) as ev:
         for (rows, local), (n, skip) in zip(arrivals, steps):
-            ref.add_rwis(_rows(rows), local)
+            ref.add_rwis(rows_list(rows), local)
             ev.add_rwis(rows, local)
             got = [(h.urlhash, h.score) for h in ev.pull(n, skip)]
             assert got == ref.pull(n, skip), (n, skip)
@@ -287,7 +228,7 @@ def test_event_pull_double_dom(seed):
     _, idx = _pool()
     rng = np.random.default_rng(40 + seed)
     order = np.argsort(-idx.sizes)
-    arr = _arrivals(idx, rng, 9, local_term=int(order[seed]), big=True)
+    arr = arrivals(idx, rng, 9, local_term=int(order[seed]), big=True)
     steps = [(int(rng.integers(0, 40)), bool(rng.random() < 0.8)) for _ in arr]
     ix = RWIIndex(0)
     try:

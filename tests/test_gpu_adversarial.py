@@ -18,16 +18,17 @@ So the table tests run every container at k = 3000 (every row comes back: build_
 arithmetic entry by entry, in k_score_full) and at k = 256 and 100 (the top of the same
 ranking: k_qtabs -> copy_card_tab -> k_score, and k_score without tables at 512 rows)."""
 
-import ctypes
-
 import numpy as np
 import pytest
 
+import index_util as iu
 import java_literal as jl
 import oracle as orc
+import query_util as qu
 from adv_rows import (CONST_COLS, adv_profiles, adv_rows, col_values, distance_fold_rows, flag_profiles,
                       flag_walk_rows, hashcodes, palette_profile, shard_of, single, sort_rows, span_rows,
                       universe_lists)
+from event_local_cases import check_event
 from yacy_search_server_amd import Query, QueryFilter, RankingProfile, RWIIndex
 from yacy_search_server_amd._lib import CStats
 
@@ -38,7 +39,7 @@ NOW = 20741 * DAY + 4242
 NOWS = [NOW, 15500 * DAY + 7, 70000 * DAY + 1]  # day 15500: most dates in the future; day 70000: none
 INF = 2147483647
 MODES = ["edge", "few"] + ["const:" + c for c in CONST_COLS]
-HIT = 24  # sizeof(yrwi_hit) == sizeof(YoHit): urlhash[12], int32 tiebreak, int64 score
+HIT = qu.HIT
 
 
 def _rp(jlprof):
@@ -46,40 +47,6 @@ def _rp(jlprof):
     for _, f in jl.PROFILE_FIELDS:
         setattr(rp, f, getattr(jlprof, f))
     return rp
-
-
-def _decode(raw):
-    a = np.frombuffer(raw, dtype=np.dtype([("h", "S12"), ("t", "<i4"), ("s", "<i8")]))
-    return [(bytes(x["h"]).ljust(12, b"\0"), int(x["s"]), int(x["t"])) for x in a]
-
-
-def _orc_raw(d, inc, exc, prof, lang, now, k, md=INF):
-    """orc.search's hits as the raw 24-byte records (no per-hit Python objects)."""
-    lib = orc.load()
-    ip, k1 = orc._lists([(h, d.get(h)) for h in inc])
-    ep, k2 = orc._lists([(h, d.get(h)) for h in exc])
-    out = (orc.YoHit * max(1, k))()
-    n = ctypes.c_int32(0)
-    rc = lib.yo_search(ip, len(inc), ep, len(exc), md, ctypes.byref(prof), lang.encode(), now, k, out,
-                       ctypes.byref(n), None, None)
-    assert rc == 0
-    return bytes(memoryview(out).cast("B")[:n.value * HIT])
-
-
-def _gpu_raw(ix, queries, stats=None):
-    """search_batch's hits as raw records, one bytes object per query."""
-    arr, keep, hits, nout, kmax = ix._marshal(queries, None)
-    ix.search_batch_raw(arr, len(queries), kmax, hits, nout, stats)
-    mv = memoryview(hits).cast("B")
-    return [bytes(mv[i * kmax * HIT:(i * kmax + nout[i]) * HIT]) for i in range(len(queries))]
-
-
-def _same_hits(got, exp, ctx):
-    if got == exp:
-        return
-    g, e = _decode(got), _decode(exp)
-    i = next((j for j, (a, b) in enumerate(zip(g, e)) if a != b), min(len(g), len(e)))
-    assert False, (ctx, "hits", len(g), len(e), "first difference at", i, g[i:i + 2], e[i:i + 2])
 
 
 def _same_scores(got, exp, ctx):
@@ -95,11 +62,11 @@ KS = (3000, 256, 100)  # k_score_full; k_score at its largest k; k_score at the 
 def _check_lists(ix, d, rp, op, lang, now, ctx):
     """Every list of d as a one-term query, one batch per k of KS, against the oracle's
     ranking of the whole list (its first k entries are the oracle's top-k)."""
-    exp = {h: _orc_raw(d, [h], [], op, lang, now, 3000) for h in d}
+    exp = {h: qu.orc_raw(d, [h], [], op, lang, now, 3000) for h in d}
     for k in KS:
-        got = _gpu_raw(ix, [Query([h], [], k=k, profile=rp, language=lang, now_ms=now) for h in d])
+        got = qu.gpu_raw(ix, [Query([h], [], k=k, profile=rp, language=lang, now_ms=now) for h in d])
         for h, g in zip(d, got):
-            _same_hits(g, exp[h][:k * HIT], (h, k) + tuple(ctx))
+            qu.same_hits(g, exp[h][:k * HIT], (h, k) + tuple(ctx))
 
 
 @pytest.fixture(scope="module")
@@ -346,21 +313,21 @@ def test_pruning_with_ties_at_k(n, mode):
             ix.add(h, r)
         for h, name, prof, ks in cases:
             rp, op = _rp(prof), orc.profile_from(prof)
-            exp = [_orc_raw(d, [h], [], op, "en", NOW, k) for k in ks]
-            got = _gpu_raw(ix, [Query([h], [], k=k, profile=rp, now_ms=NOW) for k in ks])
+            exp = [qu.orc_raw(d, [h], [], op, "en", NOW, k) for k in ks]
+            got = qu.gpu_raw(ix, [Query([h], [], k=k, profile=rp, now_ms=NOW) for k in ks])
             for k, g, e in zip(ks, got, exp):
-                _same_hits(g, e, (h, name, k, "alone"))
-            got = _gpu_raw(ix, [Query([h], [], k=k, profile=rp, now_ms=NOW) for k in ks for _ in range(8)])
+                qu.same_hits(g, e, (h, name, k, "alone"))
+            got = qu.gpu_raw(ix, [Query([h], [], k=k, profile=rp, now_ms=NOW) for k in ks for _ in range(8)])
             for j, g in enumerate(got):
-                _same_hits(g, exp[j // 8], (h, name, ks[j // 8], "copy", j % 8))
+                qu.same_hits(g, exp[j // 8], (h, name, ks[j // 8], "copy", j % 8))
             small = [j for j, k in enumerate(ks) if k <= 256]
             if not small:
                 continue
-            got = _gpu_raw(ix, [Query([h], [], k=ks[small[c % len(small)]], profile=rp, now_ms=NOW)
+            got = qu.gpu_raw(ix, [Query([h], [], k=ks[small[c % len(small)]], profile=rp, now_ms=NOW)
                                 for c in range(2048)])
             for c, g in enumerate(got):
                 j = small[c % len(small)]
-                _same_hits(g, exp[j], (h, name, ks[j], "of 2048 copies", c))
+                qu.same_hits(g, exp[j], (h, name, ks[j], "of 2048 copies", c))
     finally:
         ix.close()
 
@@ -381,7 +348,6 @@ def test_topk_pass_ladder():
     pass 1 merges 4 lists a group and the later passes (stride 3000) 2.  Rows of few values:
     ties cross the list boundaries.  The batch in this order and reversed (other group bases),
     through search_batch and through the call that returns the hits' rows."""
-    from test_gpu_hit_rows import _same as _same_rows
     assert [-(-n // 2048) for n, _ in LADDER] == [1, 2, 5, 9]
     d = {b"TERMladder%d_" % i: adv_rows(n, 80 + i, "few") for i, (n, _) in enumerate(LADDER)}
     assert [len(r) for r in d.values()] == [n for n, _ in LADDER]
@@ -389,7 +355,7 @@ def test_topk_pass_ladder():
     rp, op = _rp(prof), orc.profile_from(prof)
     cases = [(b"TERMladderNO", 100, b"", [])]
     for (h, rows), (_, k) in zip(d.items(), LADDER):
-        exp = _orc_raw(d, [h], [], op, "en", NOW, k)
+        exp = qu.orc_raw(d, [h], [], op, "en", NOW, k)
         assert len(exp) == k * HIT  # precondition, from the reference alone: every list fills its k
         cases.append((h, k, exp, orc.term_search(d, [h], [], INF, NOW)))
     ix = RWIIndex(0)
@@ -398,10 +364,10 @@ def test_topk_pass_ladder():
             ix.add(h, rows)
         for order in (cases, cases[::-1]):
             batch = [Query([h], [], k=k, profile=rp, now_ms=NOW) for h, k, _, _ in order]
-            for (h, k, exp, _), g in zip(order, _gpu_raw(ix, batch)):
-                _same_hits(g, exp, (h, k, order is cases))
+            for (h, k, exp, _), g in zip(order, qu.gpu_raw(ix, batch)):
+                qu.same_hits(g, exp, (h, k, order is cases))
             for (h, k, exp, joined), g in zip(order, ix.search_batch(batch, rows=True)):
-                _same_rows(g, _decode(exp), joined, (h, k, order is cases, "rows"))
+                qu.same_rows(g, qu.decode(exp), joined, (h, k, order is cases, "rows"))
     finally:
         ix.close()
 
@@ -486,10 +452,10 @@ def test_adversarial_joins(join_lists, algo, chain, monkeypatch):
             rp, op = _rp(prof), orc.profile_from(prof)
             for md in (INF, 300):
                 now = NOWS[(pi + (md == 300)) % 3]
-                got = _gpu_raw(ix, [Query(inc, exc, max_distance=md, k=3000, profile=rp, now_ms=now)
+                got = qu.gpu_raw(ix, [Query(inc, exc, max_distance=md, k=3000, profile=rp, now_ms=now)
                                     for inc, exc in qs])
                 for qi, ((inc, exc), g) in enumerate(zip(qs, got)):
-                    _same_hits(g, _orc_raw(d, inc, exc, op, "en", now, 3000, md), (qi, name, md, now))
+                    qu.same_hits(g, qu.orc_raw(d, inc, exc, op, "en", now, 3000, md), (qi, name, md, now))
     finally:
         ix.close()
 
@@ -581,17 +547,17 @@ def test_pieces_many_groups(algo, monkeypatch):
         batch = [Query(t(q), t(exc), k=100, profile=_rp(prof), now_ms=NOW) for prof, q, exc in plan]
         meta = [(pi, prof, q, exc) for pi, (prof, q, exc) in enumerate(plan)]
         st = CStats()
-        got = _gpu_raw(ix, batch, stats=st)
+        got = qu.gpu_raw(ix, batch, stats=st)
         assert st.t_compact_ns > 0 and st.joined > 0
         for (pname, prof, q, exc), g in zip(meta, got):
-            exp = _orc_raw(d, t(q), t(exc), orc.profile_from(prof), "en", NOW, 100)
+            exp = qu.orc_raw(d, t(q), t(exc), orc.profile_from(prof), "en", NOW, 100)
             assert len(exp) == 100 * HIT
             if q in ("ZY", "YZ"):  # from the reference alone: the best hit's distance term depends on D
                 _, nm = orc.search(d, t(q), [], orc.profile_from(prof), "en", now_ms=NOW, k=1, with_norm=True)
                 zr = d[t("Z")[0]]
                 best = zr[(zr[:, :12] == np.frombuffer(exp[:12], dtype=np.uint8)).all(axis=1)]
                 assert nm.max_distance_D == 240 and len(best) == 1 and best[0, 38] >= 40
-            _same_hits(g, exp, (algo, pname, q, exc))
+            qu.same_hits(g, exp, (algo, pname, q, exc))
     finally:
         ix.close()
 
@@ -604,7 +570,6 @@ def test_adversarial_shards(world):
     shard is not shard 0 (k_combine's s == gf branch takes the clone clamp).  The
     first row of every list lies in the future; in list F it is the only one beside
     the first row of the last shard, whose date must stay unclamped."""
-    from test_gpu_shards_loopback import _run_parts
     full = universe_lists(31, 3000, fracs=(1.0, 0.6))
     full = {h: r for h, r in zip((b"TERMshA_____", b"TERMshB_____"), full.values())}
     uni = adv_rows(3000, 31, "edge", first_char_min=24)
@@ -628,12 +593,12 @@ def test_adversarial_shards(world):
              for name, prof in (("default", jl.RankingProfile()), ("c5", c5), ("date", single("date", 15)))]
 
     def run(rk, ix):
-        return _gpu_raw(ix, [Query(inc, exc, k=100, profile=_rp(prof), now_ms=NOW) for inc, exc, _, prof in cases])
+        return qu.gpu_raw(ix, [Query(inc, exc, k=100, profile=_rp(prof), now_ms=NOW) for inc, exc, _, prof in cases])
 
-    res = _run_parts(parts, world, run)
+    res = iu.run_parts(parts, world, run)
     for rk, got in enumerate(res):
         for (inc, exc, name, prof), g in zip(cases, got):
-            _same_hits(g, _orc_raw(full, inc, exc, orc.profile_from(prof), "en", NOW, 100), (world, rk, inc, name))
+            qu.same_hits(g, qu.orc_raw(full, inc, exc, orc.profile_from(prof), "en", NOW, 100), (world, rk, inc, name))
 
 
 # ------------------------------------------------------------------ j
@@ -641,7 +606,6 @@ def test_adversarial_events(ctx):
     """SearchEvent arrivals drawn from an adversarial pool of 1,200 rows: duplicates
     inside and across arrivals, one arrival of more than 2,048 rows; the stack, the
     flag counts, the max-distance fold and maxdomcount against java_literal."""
-    from test_events import _check_event
     pool = adv_rows(1200, 9, "edge")
     rng = np.random.default_rng(9)
     arrivals = [(pool[:300], True)]
@@ -650,9 +614,9 @@ def test_adversarial_events(ctx):
         take[: m // 4] = take[rng.integers(0, m, m // 4)]
         arrivals.append((pool[take], False))
     high = palette_profile((15, 16, 22, 23, 24, 31), 102)
-    _check_event(ctx, arrivals, k=3000)
-    _check_event(ctx, arrivals, {"coeff_authority": 14, "coeff_worddistance": 15}, k=3000)
-    _check_event(ctx, arrivals[1:], {f: getattr(high, f) for _, f in jl.PROFILE_FIELDS}, k=200)
+    check_event(ctx, arrivals, k=3000)
+    check_event(ctx, arrivals, {"coeff_authority": 14, "coeff_worddistance": 15}, k=3000)
+    check_event(ctx, arrivals[1:], {f: getattr(high, f) for _, f in jl.PROFILE_FIELDS}, k=200)
 
 
 # ------------------------------------------------------------------ k

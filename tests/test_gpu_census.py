@@ -5,36 +5,25 @@ Hosts, counts and the counters of the call's statistics are compared exactly, in
 overflow paths of both tables are reached with YRWI_CENSUS_LDS_SLOTS and YRWI_CENSUS_SLOTS."""
 
 import ctypes
-import os
-import threading
 
 import numpy as np
 import pytest
 
 import census_ref as cr
 import host_ref as hr
+import index_util as iu
 import update_ref as ur
-from yacy_search_server_amd import RWIIndex, synth
-from yacy_search_server_amd import _lib
+from yacy_search_server_amd import _lib, synth
 from yacy_search_server_amd._lib import YrwiError
 
 pytestmark = pytest.mark.gpu
 
-B64 = ur._B64
 FIRST, LAST, OTHER = b"AAAAAA", b"______", b"keepme"
 KNOBS = ("YRWI_CENSUS_SLOTS", "YRWI_CENSUS_LDS_SLOTS")
 
 
-def _enc(i, width):
-    out = bytearray()
-    for _ in range(width):
-        out.append(B64[i & 63])
-        i >>= 6
-    return bytes(reversed(out))
-
-
 def _term(i):
-    return b"-h" + _enc(i, 10)
+    return iu.term(i, b"-h")
 
 
 @pytest.fixture(scope="module")
@@ -70,26 +59,11 @@ def _defaults(monkeypatch):
         monkeypatch.delenv(k, raising=False)
 
 
-def _rows(idx, urls, start=0):
-    """hand-made rows: rows of the synthetic index as templates, the url hash set"""
-    r = idx.rows[(start + 13 * np.arange(len(urls))) % len(idx.rows)].copy()
-    for i, u in enumerate(urls):
-        r[i, :12] = np.frombuffer(u, dtype=np.uint8)
-    return r
-
-
-def _open(lists):
-    ix = RWIIndex(0)
-    for h, r in lists.items():
-        ix.add(h, r)
-    return ix
-
-
 @pytest.fixture(scope="module")
 def opened(tiny):
     """one context per corpus for the cases that change nothing"""
     idx, corp, have = tiny
-    ixs = {name: _open(lists) for name, lists in corp.items()}
+    ixs = {name: iu.open_index(lists) for name, lists in corp.items()}
     yield ixs
     for ix in ixs.values():
         ix.close()
@@ -225,16 +199,16 @@ def test_boundaries(tiny, monkeypatch):
     hand, k = {}, 0
     for n in SIZES:
         for name, member in PATTERNS.items():
-            urls = [_enc(1000 * k + i, 6) + (gone if member(i, n) else stay) for i in range(n)]
+            urls = [iu.enc(1000 * k + i, 6) + (gone if member(i, n) else stay) for i in range(n)]
             assert urls == sorted(urls, key=ur.url_key)
-            hand[_term(k)] = _rows(idx, urls, start=k)
+            hand[_term(k)] = iu.rows(idx, urls, start=k)
             k += 1
     edge = _term(500)
-    hand[edge] = _rows(idx, [_enc(i, 6) + (FIRST, LAST, OTHER)[i % 3] for i in range(300)])
+    hand[edge] = iu.rows(idx, [iu.enc(i, 6) + (FIRST, LAST, OTHER)[i % 3] for i in range(300)])
     all_lists = {**corp["rehosted"], **hand}
     exp = have["rehosted"] + cr.tally(hand)
     assert exp[FIRST] == exp[LAST] == exp[OTHER] == 100 and exp[gone] > exp[stay] > 0 and len(exp) == 69
-    ix = _open(all_lists)
+    ix = iu.open_index(all_lists)
     try:
         for lds in (None, "64"):
             if lds:
@@ -265,10 +239,10 @@ def test_hot_spot(tiny, monkeypatch):
     big = _term(900)
     three = [t for t in sorted(lists) if len(lists[t]) >= 300][:3]
     small = {t: lists[t][:300] for t in three}
-    small[big] = _rows(idx, [_enc(i, 6) + hot for i in range(20000)])
+    small[big] = iu.rows(idx, [iu.enc(i, 6) + hot for i in range(20000)])
     exp = cr.tally(small)
     assert exp[hot] == 20000 and sum(exp.values()) == 20900
-    ix = _open(small)
+    ix = iu.open_index(small)
     try:
         for lds in (None, "64"):
             if lds:
@@ -320,7 +294,7 @@ def test_top_and_min_postings(tiny, refs, opened):
 def test_agrees_with_count_hosts_and_remove_hosts(tiny, refs):
     idx, corp, have = tiny
     for name, top in (("rehosted", None), ("raw", 3000)):  # (3000 hosts: count_hosts searches them in global memory)
-        ix = _open(corp[name])
+        ix = iu.open_index(corp[name])
         try:
             hosts, counts, st = ix.host_census(None, "count", top=top)
             assert len(hosts) == (top or 64)
@@ -343,7 +317,7 @@ def test_agrees_with_count_hosts_and_remove_hosts(tiny, refs):
 def test_changes_nothing_and_allocates_once(tiny, refs):
     idx, corp, have = tiny
     lists = corp["rehosted"]
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
         info, stats = ix.index_info(), ix.stats()
@@ -396,35 +370,12 @@ def test_two_shards(tiny, refs):
     idx, corp, have = tiny
     lists = corp["rehosted"]
     world = 2
-    rank_of = lambda l: np.array([ur.url_key(bytes(r[:12]))[0] >> 5 for r in l])  # Distribution.verticalDHTPosition, world 2
-    parts = [{t: l[rank_of(l) == r] for t, l in lists.items()} for r in range(world)]
-    parts = [{t: l for t, l in p.items() if len(l)} for p in parts]
-    uid = b"YRWI-LOOPBACK\0" + os.urandom(114)
-    ixs, out, errs = [None] * world, [None] * world, []
+    parts = iu.split_by_rank(lists, world)
 
-    def opener(r):
-        try:
-            ixs[r] = RWIIndex(0, shard=(r, world, uid))
-            for h, rr in parts[r].items():
-                ixs[r].add(h, rr)
-        except Exception as e:  # pragma: no cover - reported below
-            errs.append(repr(e))
+    def fn(r, ix):
+        return [ix.host_census(None, o) for o in cr.ORDERS]
 
-    def runner(r):
-        try:
-            out[r] = [ixs[r].host_census(None, o) for o in cr.ORDERS]
-        except Exception as e:  # pragma: no cover
-            errs.append(repr(e))
-
-    for fn in (opener, runner):
-        ths = [threading.Thread(target=fn, args=(r,)) for r in range(world)]
-        for t in ths:
-            t.start()
-        for t in ths:
-            t.join(timeout=300)
-        assert not errs, errs
-    for ix in ixs:
-        ix.close()
+    out = iu.run_parts(parts, world, fn)
     merged = {}
     for r in range(world):
         assert sum(len(l) for l in parts[r].values()) > 0

@@ -9,15 +9,13 @@ import numpy as np
 import pytest
 
 import dht_ref as dr
-import test_gpu_shards_loopback as lb
-import test_gpu_updates as tu
-import update_ref as ur
+import index_util as iu
 from yacy_search_server_amd import RWIIndex, _lib, synth
 
 pytestmark = pytest.mark.gpu
 
-NOW = tu.NOW
-B64 = ur._B64
+NOW = iu.NOW
+B64 = iu.B64
 LAST = dr.LAST
 BIG = (1 << 31) - 1
 E_ARG, E_HASH = -1, -2
@@ -27,15 +25,15 @@ STAT_KEYS = ("terms", "postings", "skipped_private", "wrapped")
 def _u(c0, c1, i):
     """a url hash whose first two characters have the alphabet indices c0, c1: partition
     c0 >> 2 at e = 4, c0 * 4 + (c1 >> 4) at e = 8"""
-    return bytes([B64[c0], B64[c1]]) + tu._enc(i, 10)
+    return bytes([B64[c0], B64[c1]]) + iu.enc(i, 10)
 
 
 def _private(i):
-    return dr.PRIVATE + tu._enc(i, 10)
+    return dr.PRIVATE + iu.enc(i, 10)
 
 
 def _late(i):
-    return b"_z" + tu._enc(i, 10)  # sorts after the private terms
+    return b"_z" + iu.enc(i, 10)  # sorts after the private terms
 
 
 def _spread(rng, n, lo, hi, base):
@@ -53,22 +51,22 @@ def _fixture_urls():
     rng = np.random.default_rng(72)
     L = {}
     # rows in all 16 partitions at e = 4, 1 .. 5 of them each
-    L[tu._term(10)] = [_u(4 * p + k % 4, (11 * k) % 64, 100 * p + k) for p in range(16) for k in range(1 + (p * 7) % 5)]
-    L[tu._term(20)] = [_u(k % 4, (5 * k) % 64, k) for k in range(33)]       # wholly in partition 0
-    L[tu._term(30)] = [_u(60 + k % 4, (9 * k) % 64, k) for k in range(20)]  # wholly in partition 15
-    L[tu._term(40)] = [_u(30, 7, 1)]                                        # one row
+    L[iu.term(10)] = [_u(4 * p + k % 4, (11 * k) % 64, 100 * p + k) for p in range(16) for k in range(1 + (p * 7) % 5)]
+    L[iu.term(20)] = [_u(k % 4, (5 * k) % 64, k) for k in range(33)]       # wholly in partition 0
+    L[iu.term(30)] = [_u(60 + k % 4, (9 * k) % 64, k) for k in range(20)]  # wholly in partition 15
+    L[iu.term(40)] = [_u(30, 7, 1)]                                        # one row
     # partition boundaries right after the first row and right before the last
-    L[tu._term(50)] = [_u(8, 1, 0)] + [_u(20 + k % 4, k, k) for k in range(9)] + [_u(44, 2, 0)]
+    L[iu.term(50)] = [_u(8, 1, 0)] + [_u(20 + k % 4, k, k) for k in range(9)] + [_u(44, 2, 0)]
     # two urls that share their first character and differ at e = 8
-    L[tu._term(60)] = [_u(20, 3, 0), _u(20, 40, 0), _u(33, 0, 0), _u(33, 63, 0), _u(50, 16, 0), _u(50, 17, 0)]
+    L[iu.term(60)] = [_u(20, 3, 0), _u(20, 40, 0), _u(33, 0, 0), _u(33, 63, 0), _u(50, 16, 0), _u(50, 17, 0)]
     # the middle one's single row in partition 3 is wedged between its neighbours' rows there
-    L[tu._term(70)] = [_u(12 + k % 4, k, k) for k in range(5)]
-    L[tu._term(80)] = [_u(13, 9, 0), _u(36, 0, 0), _u(37, 0, 0)]
-    L[tu._term(90)] = [_u(12 + k % 4, 20 + k, k) for k in range(4)] + [_u(38, 5, 0), _u(39, 5, 0)]
+    L[iu.term(70)] = [_u(12 + k % 4, k, k) for k in range(5)]
+    L[iu.term(80)] = [_u(13, 9, 0), _u(36, 0, 0), _u(37, 0, 0)]
+    L[iu.term(90)] = [_u(12 + k % 4, 20 + k, k) for k in range(4)] + [_u(38, 5, 0), _u(39, 5, 0)]
     big = _spread(rng, 300, 0, 64, 1000)
-    L[tu._term(100)] = big
-    L[tu._term(110)] = sorted(set(big[::3]) | set(_spread(rng, 120, 0, 64, 5000)), key=dr.key)  # joins with it
-    L[tu._term(120)] = _spread(rng, 150, 32, 64, 9000)
+    L[iu.term(100)] = big
+    L[iu.term(110)] = sorted(set(big[::3]) | set(_spread(rng, 120, 0, 64, 5000)), key=dr.key)  # joins with it
+    L[iu.term(120)] = _spread(rng, 150, 32, 64, 9000)
     L[_private(1)] = _spread(rng, 7, 0, 64, 20000)
     L[_private(2)] = _spread(rng, 12, 0, 64, 21000)
     L[_late(1)] = _spread(rng, 40, 0, 64, 30000)
@@ -91,17 +89,17 @@ def hand(tiny):
     """the hand-made index on the device, its lists, and the reference of the whole selection
     (rotated: from the middle of the term order) for every tested exponent"""
     urls = _fixture_urls()
-    lists = {t: tu._rows(tiny, us, start=17 * i) for i, (t, us) in enumerate(urls.items())}
+    lists = {t: iu.rows(tiny, us, start=17 * i) for i, (t, us) in enumerate(urls.items())}
     assert 14 <= len(lists) <= 16 and sum(map(len, lists.values())) <= 1200
     e4 = {t: [dr.partition(u, 4) for u in us] for t, us in urls.items()}
-    assert set(e4[tu._term(10)]) == set(range(16))
-    assert set(e4[tu._term(20)]) == {0} and set(e4[tu._term(30)]) == {15} and len(urls[tu._term(40)]) == 1
-    p50 = e4[tu._term(50)]
+    assert set(e4[iu.term(10)]) == set(range(16))
+    assert set(e4[iu.term(20)]) == {0} and set(e4[iu.term(30)]) == {15} and len(urls[iu.term(40)]) == 1
+    p50 = e4[iu.term(50)]
     assert p50[0] < p50[1] == p50[-2] < p50[-1]
-    a, b = urls[tu._term(60)][:2]
+    a, b = urls[iu.term(60)][:2]
     assert a[0] == b[0] and dr.partition(a, 8) != dr.partition(b, 8) and dr.partition(a, 6) == dr.partition(b, 6)
     assert sum(t[:2] == dr.PRIVATE for t in lists) == 2
-    start = tu._term(45)
+    start = iu.term(45)
     ref = {e: dr.expected(lists, start, LAST, BIG, BIG, e) for e in (0, 1, 4, 6, 8)}
     # the edge cases, through the reference at e = 4
     terms, off, rows, st = ref[4]
@@ -112,7 +110,7 @@ def hand(tiny):
     assert _runs_of_empty(cnt) >= 3
     assert any(cnt[c] == 1 and cnt[c - 1] > 0 and cnt[c + 1] > 0 and (c - 1) // len(terms) == (c + 1) // len(terms)
                for c in range(1, len(cnt) - 1))
-    ix = tu._open(lists)
+    ix = iu.open_index(lists)
     yield ix, lists, start, ref
     ix.close()
 
@@ -189,7 +187,7 @@ def test_selection_rules(hand, monkeypatch):
         return sel
 
     # start between two terms
-    assert run(tu._term(45), LAST, 3, BIG, 4).terms == [tu._term(50), tu._term(60), tu._term(70)]
+    assert run(iu.term(45), LAST, 3, BIG, 4).terms == [iu.term(50), iu.term(60), iu.term(70)]
     # start past the last term, with and without rot
     past = _late(3)
     sel = run(past, LAST, 2, BIG, 4)
@@ -197,28 +195,28 @@ def test_selection_rules(hand, monkeypatch):
     sel = run(past, LAST, 2, BIG, 4, rot=False)
     assert sel.terms == [] and sel.part_off.tolist() == [0] and sel.stats["wrapped"] == 0
     # stop at limit; the first container is taken even when it is >= limit
-    assert run(tu._term(30), tu._term(60), BIG, BIG, 4).terms == [tu._term(30), tu._term(40), tu._term(50)]
-    assert run(tu._term(70), tu._term(60), BIG, BIG, 4).terms == [tu._term(70)]
+    assert run(iu.term(30), iu.term(60), BIG, BIG, 4).terms == [iu.term(30), iu.term(40), iu.term(50)]
+    assert run(iu.term(70), iu.term(60), BIG, BIG, 4).terms == [iu.term(70)]
     # after a wrap the comparison is still the plain one
-    assert run(_late(2), tu._term(30), BIG, BIG, 4).terms == [_late(2), tu._term(10), tu._term(20)]
+    assert run(_late(2), iu.term(30), BIG, BIG, 4).terms == [_late(2), iu.term(10), iu.term(20)]
     # the max_containers cut, and max_refs overshot by the last container
-    assert run(tu._term(10), LAST, 4, BIG, 4).terms == order[:4]
+    assert run(iu.term(10), LAST, 4, BIG, 4).terms == order[:4]
     cut = size[order[0]] + 1
-    sel = run(tu._term(10), LAST, BIG, cut, 4)
+    sel = run(iu.term(10), LAST, BIG, cut, 4)
     assert sel.terms == order[:2] and sel.stats["postings"] == size[order[0]] + size[order[1]] > cut
     # private terms are passed over without counting
-    sel = run(tu._term(120), LAST, 3, BIG, 4, rot=False)
-    assert sel.terms == [tu._term(120), _late(1), _late(2)] and sel.stats["skipped_private"] == 2
-    sel = run(tu._term(120), LAST, 3, BIG, 4, rot=False, skip_private=False)
-    assert sel.terms == [tu._term(120), _private(1), _private(2)] and sel.stats["skipped_private"] == 0
+    sel = run(iu.term(120), LAST, 3, BIG, 4, rot=False)
+    assert sel.terms == [iu.term(120), _late(1), _late(2)] and sel.stats["skipped_private"] == 2
+    sel = run(iu.term(120), LAST, 3, BIG, 4, rot=False, skip_private=False)
+    assert sel.terms == [iu.term(120), _private(1), _private(2)] and sel.stats["skipped_private"] == 0
     # a full cycle: every non-private term once, in rotated order
-    sel = run(tu._term(95), LAST, BIG, BIG, 4)
-    k = public.index(tu._term(100))
+    sel = run(iu.term(95), LAST, BIG, BIG, 4)
+    k = public.index(iu.term(100))
     assert sel.terms == public[k:] + public[:k] and sel.stats["wrapped"] == 1
     assert sel.stats["postings"] == sum(size[t] for t in public)
     # nothing to select: an empty result, rc 0
     for mc, mr in ((0, BIG), (5, 0)):
-        sel = run(tu._term(10), LAST, mc, mr, 4)
+        sel = run(iu.term(10), LAST, mc, mr, 4)
         assert sel.terms == [] and sel.part_off.tolist() == [0] and sel.rows.shape == (0, 40)
         assert sel.stats["windows"] == 0
     _unchanged(ix, lists)
@@ -228,12 +226,12 @@ def test_selection_rules(hand, monkeypatch):
 def test_remove_and_put_back(hand, tiny, monkeypatch):
     _, lists, _, _ = hand
     _window(monkeypatch, 64)
-    ix = tu._open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
-        sel = ix.dht_select(tu._term(30), tu._term(100), BIG, BIG, 4, remove=True)
-        _same(sel, dr.expected(lists, tu._term(30), tu._term(100), BIG, BIG, 4))
-        gone = [tu._term(i) for i in (30, 40, 50, 60, 70, 80, 90)]
+        sel = ix.dht_select(iu.term(30), iu.term(100), BIG, BIG, 4, remove=True)
+        _same(sel, dr.expected(lists, iu.term(30), iu.term(100), BIG, BIG, 4))
+        gone = [iu.term(i) for i in (30, 40, 50, 60, 70, 80, 90)]
         assert sel.terms == gone
         assert sel.stats["removed"] == sel.stats["postings"] == sum(len(lists[t]) for t in gone)
         left = dr.after_removal(lists, gone)
@@ -241,9 +239,9 @@ def test_remove_and_put_back(hand, tiny, monkeypatch):
             assert ix.get_size(t) == 0 and ix.get_list(t).shape == (0, 40)
         _unchanged(ix, left)
         assert ix.check_url_ids()[0] == 0
-        qs = [([tu._term(100), tu._term(110)], []), ([tu._term(110), tu._term(120)], [tu._term(100)])]
-        got = tu._hits(ix, qs)
-        assert got == tu._oracle(left, qs) and len(got[0]) > 0
+        qs = [([iu.term(100), iu.term(110)], []), ([iu.term(110), iu.term(120)], [iu.term(100)])]
+        got = iu.hits(ix, qs)
+        assert got == iu.oracle_hits(left, qs) and len(got[0]) > 0
         # what could not be sent goes back: term j for every row of its cells
         T = len(sel.terms)
         per_row = [sel.terms[c % T] for c in range(len(sel.part_off) - 1)
@@ -308,16 +306,16 @@ def test_capacity_and_errors(hand, monkeypatch):
 # ------------------------------------------------------------------ 6: cost does not follow the term count
 def test_cost_does_not_follow_term_count(tiny, monkeypatch):
     _window(monkeypatch, 64)
-    one = {tu._term(1): tu._rows(tiny, sorted((_u(k % 64, (7 * k) % 64, k) for k in range(1000)), key=dr.key))}
-    many = {tu._term(100 + i): tu._rows(tiny, sorted((_u((i + 16 * k) % 64, i % 64, i) for k in range(4)), key=dr.key),
+    one = {iu.term(1): iu.rows(tiny, sorted((_u(k % 64, (7 * k) % 64, k) for k in range(1000)), key=dr.key))}
+    many = {iu.term(100 + i): iu.rows(tiny, sorted((_u((i + 16 * k) % 64, i % 64, i) for k in range(4)), key=dr.key),
                                         start=i) for i in range(250)}
     lists = {**one, **many}
-    ix = tu._open(lists)
+    ix = iu.open_index(lists)
     try:
-        a = ix.dht_select(tu._term(1), tu._term(2), BIG, BIG, 4)
-        b = ix.dht_select(tu._term(100), LAST, BIG, BIG, 4, rot=False)
-        _same(a, dr.expected(lists, tu._term(1), tu._term(2), BIG, BIG, 4))
-        _same(b, dr.expected(lists, tu._term(100), LAST, BIG, BIG, 4, rot=False))
+        a = ix.dht_select(iu.term(1), iu.term(2), BIG, BIG, 4)
+        b = ix.dht_select(iu.term(100), LAST, BIG, BIG, 4, rot=False)
+        _same(a, dr.expected(lists, iu.term(1), iu.term(2), BIG, BIG, 4))
+        _same(b, dr.expected(lists, iu.term(100), LAST, BIG, BIG, 4, rot=False))
         assert (len(a.terms), len(b.terms)) == (1, 250) and a.stats["postings"] == b.stats["postings"] == 1000
         assert a.stats["windows"] == b.stats["windows"] == 16
         assert (a.stats["launches"], a.stats["syncs"]) == (b.stats["launches"], b.stats["syncs"]), (a.stats, b.stats)
@@ -340,8 +338,8 @@ def test_shards_loopback(hand, monkeypatch):
         sel = ix.dht_select(first, LAST, BIG, BIG, 4)
         return sel.terms, sel.part_off, sel.rows.copy(), sel.stats
 
-    res = lb._run_parts(parts, world, fn)
-    whole = tu._open(both)
+    res = iu.run_parts(parts, world, fn)
+    whole = iu.open_index(both)
     try:
         ref = whole.dht_select(first, LAST, BIG, BIG, 4)
     finally:

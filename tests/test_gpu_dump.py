@@ -10,14 +10,14 @@ import pytest
 
 import dump_ref as dr
 import heap
-import test_gpu_updates as tu
+import index_util as iu
 import update_ref as ur
 from yacy_search_server_amd import RWIIndex, _lib, synth
 from yacy_search_server_amd._lib import YrwiError
 
 pytestmark = pytest.mark.gpu
 
-NOW = tu.NOW
+NOW = iu.NOW
 
 
 @pytest.fixture(scope="module")
@@ -33,7 +33,7 @@ def tiny():
 def hand(tiny):
     """the hand-made lists (dump_ref.SIZES) on the device, and their expected image"""
     lists = dr.fixture_lists(tiny[1])
-    ix = tu._open(lists)
+    ix = iu.open_index(lists)
     yield ix, lists, dr.expected_image(lists, now_ms=NOW)
     ix.close()
 
@@ -76,10 +76,10 @@ def test_window_independence(hand, tmp_path, monkeypatch):
 # ------------------------------------------------------------------ 3: round trip
 def test_round_trip(tiny, tmp_path):
     cfg, idx, lists, qs = tiny
-    src = tu._open(lists)
+    src = iu.open_index(lists)
     back = RWIIndex(0)
     try:
-        before = tu._hits(src, qs)
+        before = iu.hits(src, qs)
         path = tmp_path / "tiny.blob"
         got, st = _dump(src, path)
         assert got == dr.expected_image(lists, now_ms=NOW)
@@ -89,10 +89,10 @@ def test_round_trip(tiny, tmp_path):
             assert back.get_list(t).tobytes() == src.get_list(t).tobytes(), t
         assert back.stats()[:2] == src.stats()[:2]
         assert back.check_url_ids()[0] == 0
-        assert tu._hits(back, qs) == before == tu._oracle(lists, qs)
+        assert iu.hits(back, qs) == before == iu.oracle_hits(lists, qs)
         # the dump changed nothing in the source context
         assert src.check_url_ids()[0] == 0
-        assert tu._hits(src, qs) == before
+        assert iu.hits(src, qs) == before
     finally:
         src.close()
         back.close()
@@ -103,18 +103,18 @@ def test_after_updates(tiny, tmp_path, monkeypatch):
     cfg, idx, lists, qs = tiny
     a, b, c, d = sorted(lists, key=lambda h: -len(lists[h]))[:4]
     cur = {h: lists[h] for h in (a, b, c, d)}
-    new_term = tu._term(9)
-    ix = tu._open(cur)
+    new_term = iu.term(9)
+    ix = iu.open_index(cur)
     try:
         ix.build_url_ids()
 
         def step(cur, k):
             # a new term, a replaced row and a new url; then a list emptied
             terms = [new_term, a, b]
-            rows = tu._rows(idx, [tu._url(700 + k), bytes(cur[a][5, :12]), tu._url(800 + k)], start=k)
-            cur, st = tu._add(ix, cur, terms, rows)
+            rows = iu.rows(idx, [iu.url(700 + k), bytes(cur[a][5, :12]), iu.url(800 + k)], start=k)
+            cur, st = iu.checked_add(ix, cur, terms, rows)
             assert st["replaced"] == 1 and st["added"] == 2
-            cur, st = tu._remove(ix, cur, [bytes(r[:12]) for r in cur[new_term]], [new_term])
+            cur, st = iu.checked_remove(ix, cur, [bytes(r[:12]) for r in cur[new_term]], [new_term])
             assert st["emptied_terms"] == 1
             return cur
 
@@ -132,7 +132,7 @@ def test_after_updates(tiny, tmp_path, monkeypatch):
         monkeypatch.setenv("YRWI_REPACK_MIN_MB", "0.05")
         first = ix.index_info()
         for i in range(16):
-            cur, _ = tu._add(ix, cur, [a] * 3, tu._rows(idx, [tu._url(1000 + 3 * i + k) for k in range(3)], start=i))
+            cur, _ = iu.checked_add(ix, cur, [a] * 3, iu.rows(idx, [iu.url(1000 + 3 * i + k) for k in range(3)], start=i))
             ix.build_url_ids()
         assert ix.index_info()["repacks"] > first["repacks"], ix.index_info()
         cur = step(cur, 1)
@@ -145,13 +145,13 @@ def test_after_updates(tiny, tmp_path, monkeypatch):
 def test_selection(hand, tmp_path, monkeypatch):
     ix, lists, image = hand
     some = sorted(lists, key=heap.key_order)[5:120:9]
-    sel = list(reversed(some)) + [some[2], tu._term(3)]  # out of order, one twice, one unknown
+    sel = list(reversed(some)) + [some[2], iu.term(3)]  # out of order, one twice, one unknown
     got, st = _dump(ix, tmp_path / "s.blob", terms=sel, window=4096, monkeypatch=monkeypatch)
     assert got == dr.expected_image(lists, sel, now_ms=NOW)
     assert [got[o + 4:o + 16] for o, _ in dr.layout(got)] == some
     assert st["terms"] == len(some) and st["postings"] == sum(len(lists[t]) for t in some)
     # only unknown terms: an empty selection, a 0-byte file
-    got, st = _dump(ix, tmp_path / "none.blob", terms=[tu._term(3)])
+    got, st = _dump(ix, tmp_path / "none.blob", terms=[iu.term(3)])
     assert got == b"" and st["windows"] == 0
     bad = tmp_path / "bad.blob"
     with pytest.raises(YrwiError) as e:
@@ -201,9 +201,9 @@ def test_files(hand, tmp_path):
 # ------------------------------------------------------------------ 7: cost does not follow the term count
 def test_cost_does_not_follow_term_count(tiny, tmp_path, monkeypatch):
     cfg, idx, lists, qs = tiny
-    one = {tu._term(1): tu._rows(idx, [tu._url(k) for k in range(1000)])}
-    many = {tu._term(100 + i): tu._rows(idx, [tu._url(k) for k in range(3)], start=i) for i in range(250)}
-    ix = tu._open({**one, **many})
+    one = {iu.term(1): iu.rows(idx, [iu.url(k) for k in range(1000)])}
+    many = {iu.term(100 + i): iu.rows(idx, [iu.url(k) for k in range(3)], start=i) for i in range(250)}
+    ix = iu.open_index({**one, **many})
     try:
         a, sa = _dump(ix, tmp_path / "one.blob", terms=list(one), window=4096, monkeypatch=monkeypatch)
         b, sb = _dump(ix, tmp_path / "many.blob", terms=list(many), window=4096, monkeypatch=monkeypatch)

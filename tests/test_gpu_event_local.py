@@ -7,16 +7,15 @@ yrwi_event_add, local = 1) and the literal oracle computes (oracle.term_search r
 java_literal.SearchEventRWI).  Every comparison is equality.  The inputs are those of
 event_local_cases.py, whose coverage tests/test_event_local_ref.py asserts on the oracle."""
 
-import os
-import threading
-
 import numpy as np
 import pytest
 
 import event_local_cases as C
 import java_literal as jl
 import oracle as orc
-from yacy_search_server_amd import Query, QueryFilter, RankingProfile, RWIIndex, synth
+from index_util import open_index, run_parts
+from query_util import hand_list
+from yacy_search_server_amd import Query, QueryFilter, RankingProfile, synth
 from yacy_search_server_amd._lib import CLocalStats, YrwiError, lib
 
 pytestmark = pytest.mark.gpu
@@ -25,17 +24,9 @@ NOW, INF = C.NOW, C.INF
 E_ARG, E_HASH, E_UNSUPPORTED, E_CAPACITY = -1, -2, -8, -10
 
 
-def _open(d):
-    ix = RWIIndex(0)
-    for h, rows in d.items():
-        ix.add(h, rows)
-    ix.build_url_ids()
-    return ix
-
-
 @pytest.fixture(scope="module")
 def indexes():
-    ixs = {p: _open(C.corpus(p)[2]) for p in ("dense", "tiny")}
+    ixs = {p: open_index(C.corpus(p)[2], url_ids=True) for p in ("dense", "tiny")}
     yield ixs
     for ix in ixs.values():
         ix.close()
@@ -209,12 +200,11 @@ def test_rows_of_hits_and_of_pulled_hits(indexes, shape):
 def test_single_include_rows_come_back_as_stored():
     """hand-built lists with nonzero typeofword / reserve bytes and a freshUntil that is not the
     recomputed one: a single-include arrival keeps all 40 bytes, a two-term one re-encodes"""
-    from test_gpu_hit_rows import _hand_list
     A, B = b"TERMrowsA___", b"TERMrowsB___"
-    a = _hand_list(700, 5)
-    b = _hand_list(700, 6, a[:, :12])[::2].copy()
+    a = hand_list(700, 5)
+    b = hand_list(700, 6, a[:, :12])[::2].copy()
     d = {A: a, B: b}
-    ix = _open(d)
+    ix = open_index(d, url_ids=True)
     try:
         with ix.event(None, "en", NOW, k=3000, max_postings=1024) as ev:
             assert ev.add_local([A], now_ms=NOW) == 700
@@ -297,7 +287,8 @@ def test_cost_contract(indexes):
     assert s4.launches_tail == s40.launches_tail and s4.syncs == s40.syncs
     assert 0 <= r4 <= 1 and 0 <= r40 <= 1 and s4.device_allocs <= 1 and s40.device_allocs <= 1
     # the same terms with every list cut to its first tenth: fewer rows, the same bytes
-    tenth = _open({h: rows[:max(1, len(rows) // 10)] for h, rows in C.corpus("dense")[2].items()})
+    tenth = open_index({h: rows[:max(1, len(rows) // 10)] for h, rows in C.corpus("dense")[2].items()},
+                       url_ids=True)
     try:
         _call(tenth, qs, 4)
         t4, mt, _ = _call(tenth, qs, 4)
@@ -341,35 +332,21 @@ def test_errors_leave_the_events_alone(indexes):
 
 
 def test_sharded_context_is_refused():
-    uid = b"YRWI-LOOPBACK\0" + os.urandom(114)
-    ixs, errs = [None, None], []
-
-    def opener(r):
-        try:
-            ixs[r] = RWIIndex(0, shard=(r, 2, uid))
-        except Exception as e:  # pragma: no cover - reported below
-            errs.append(repr(e))
-
-    ths = [threading.Thread(target=opener, args=(r,)) for r in range(2)]
-    for t in ths:
-        t.start()
-    for t in ths:
-        t.join(timeout=120)
-    assert not errs and all(ixs), errs
-    try:
-        with ixs[0].event(None, "en", NOW, k=10, max_postings=64) as ev:
+    def fn(r, ix):
+        if r:
+            return
+        with ix.event(None, "en", NOW, k=10, max_postings=64) as ev:
             with pytest.raises(YrwiError) as e:
                 ev.add_local([C.ABSENT], now_ms=NOW)
             assert e.value.rc == E_UNSUPPORTED
             assert ev.results()[0] == []
-    finally:
-        for ix in ixs:
-            ix.close()
+
+    run_parts([{}, {}], 2, fn, timeout=120)
 
 
 def test_retained_rows_are_freed_with_the_last_event():
     d = C.corpus("dense")[2]
-    ix = _open(d)
+    ix = open_index(d, url_ids=True)
     try:
         qs = _dense_queries()
         _call(ix, qs, 5)

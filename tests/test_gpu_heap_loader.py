@@ -26,6 +26,7 @@ import pytest
 import dump_ref
 import heap
 import heap_cases as hc
+import index_util as iu
 
 pytestmark = pytest.mark.gpu
 
@@ -52,10 +53,9 @@ def _check_lists(ix, exp, absent=()):
 
 
 def _check_queries(ix, lists, qs):
-    import test_gpu_updates as tu
-    exp = tu._oracle(lists, qs)
+    exp = iu.oracle_hits(lists, qs)
     assert all(exp), "a query without hits checks nothing"
-    assert tu._hits(ix, qs) == exp  # url hash, score and tiebreak
+    assert iu.hits(ix, qs) == exp  # url hash, score and tiebreak
 
 
 LOADS = {"union": hc.union_pairs, "precedence": hc.precedence, "tails": hc.unsorted_tails, "rejects": hc.rejects,

@@ -12,10 +12,12 @@ import ctypes
 import numpy as np
 import pytest
 
+import index_util as iu
 import java_literal as jl
 import oracle as orc
+import query_util as qu
 from adv_rows import adv_rows, hashcodes, shard_of, sort_rows, universe_lists
-from yacy_search_server_amd import Query, QueryFilter, RankingProfile, RWIIndex, synth
+from yacy_search_server_amd import Query, QueryFilter, RankingProfile, synth
 from yacy_search_server_amd._lib import CHit, CStats
 
 pytestmark = pytest.mark.gpu
@@ -34,33 +36,11 @@ def _rp(jlprof):
     return rp
 
 
-def _row_map(rows):
-    m = {bytes(r[:12]): bytes(r) for r in rows}
-    assert len(m) == len(rows)
-    return m
-
-
-def _same(got, exp_hits, exp_rows, ctx):
-    """got: Hits with rows; exp_hits: [(urlhash, score, tiebreak)]; exp_rows: the oracle's joined container"""
-    assert [(h.urlhash, h.score, h.tiebreak) for h in got] == list(exp_hits), (ctx, "hits")
-    m = _row_map(exp_rows)
-    for i, h in enumerate(got):
-        assert h.row is not None and len(h.row) == 40, (ctx, i)
-        assert h.row == m[h.urlhash], (ctx, "row of hit", i, h.urlhash)
-
-
-def _open(d):
-    ix = RWIIndex(0)
-    for h, rows in d.items():
-        ix.add(h, rows)
-    return ix
-
-
 @pytest.fixture(scope="module", params=["dense", "tiny", "small"])
 def corpus(request):
     cfg = synth.preset(request.param)
     idx = synth.build_index(cfg)
-    ix = _open(idx.as_dict())
+    ix = iu.open_index(idx.as_dict())
     yield cfg, idx, ix
     ix.close()
 
@@ -74,7 +54,6 @@ def _queries(cfg, idx, n, qseed, nexc=1):
 def test_parity_presets(corpus):
     """1-4 include terms, 0-1 exclude terms, four profiles, two request times, k = 100: the
     hits equal search_batch without rows and the oracle, the rows the oracle's."""
-    from test_gpu_parity import _profiles
     cfg, idx, ix = corpus
     d = idx.as_dict()
     qs = _queries(cfg, idx, 20, QSEED)
@@ -84,7 +63,7 @@ def test_parity_presets(corpus):
                for inc, exc in qs)  # an exclusion that removes a row
     for now in NOWS:
         exp_rows = [orc.term_search(d, inc, exc, INF, now) for inc, exc in qs]
-        for pname, prof in _profiles():
+        for pname, prof in qu.profiles():
             batch = [Query(inc, exc, k=100, profile=_rp(prof), now_ms=now) for inc, exc in qs]
             got = ix.search_batch(batch, rows=True)
             plain = ix.search_batch(batch)
@@ -92,42 +71,26 @@ def test_parity_presets(corpus):
                 assert [(h.urlhash, h.score, h.tiebreak) for h in g] == [(h.urlhash, h.score, h.tiebreak) for h in p]
                 assert all(h.row is None for h in p)
                 exp = orc.search(d, q.include, q.exclude, orc.profile_from(prof), "en", now_ms=now, k=100)
-                _same(g, exp, exp_rows[qi], (pname, now, qi))
+                qu.same_rows(g, exp, exp_rows[qi], (pname, now, qi))
 
 
 # ------------------------------------------------------------------ 2
-def _hand_list(n, seed, hashes=None):
-    """n rows with nonzero typeofword (g) and reserve (k) bytes and a freshUntil (s) that is
-    not lastModified + 2 (today - lastModified)."""
-    rows = adv_rows(n, seed, "edge")
-    if hashes is not None:
-        rows[:, :12] = hashes
-    a = (rows[:, 12].astype(np.int64) << 8) | rows[:, 13]
-    today = NOW // DAY
-    fresh = np.maximum(a + 2 * (today - a), 0) & 0xFFFF
-    s = (fresh + 1 + (np.arange(n) % 7)) & 0xFFFF  # never the recomputed value
-    rows[:, 14], rows[:, 15] = s >> 8, s & 0xFF
-    assert (rows[:, 28] != 0).all() and (rows[:, 39] != 0).all()
-    assert ((((rows[:, 14].astype(np.int64) << 8) | rows[:, 15]) != fresh)).all()
-    return rows
-
-
 def test_single_list_returns_stored_row():
     """One include term: the list's row as stored, all 40 bytes.  The same urls in a two-term
     query: the re-encoded record (typeofword and reserve 0, freshUntil from now_ms)."""
     A, B = b"TERMrowsA___", b"TERMrowsB___"
-    a = _hand_list(700, 5)
-    b = _hand_list(700, 6, a[:, :12])[::2].copy()
+    a = qu.hand_list(700, 5)
+    b = qu.hand_list(700, 6, a[:, :12])[::2].copy()
     d = {A: a, B: b}
-    ix = _open(d)
+    ix = iu.open_index(d)
     try:
         for k in (100, 3000):
             g = ix.search([A], k=k, now_ms=NOW, rows=True)
-            _same(g, orc.search(d, [A], [], now_ms=NOW, k=k), orc.term_search(d, [A], [], INF, NOW), ("single", k))
-            stored = _row_map(a)
+            qu.same_rows(g, orc.search(d, [A], [], now_ms=NOW, k=k), orc.term_search(d, [A], [], INF, NOW), ("single", k))
+            stored = qu.row_map(a)
             assert len(g) > 50 and all(h.row == stored[h.urlhash] for h in g)
             g2 = ix.search([A, B], k=k, now_ms=NOW, rows=True)
-            _same(g2, orc.search(d, [A, B], [], now_ms=NOW, k=k), orc.term_search(d, [A, B], [], INF, NOW), ("two", k))
+            qu.same_rows(g2, orc.search(d, [A, B], [], now_ms=NOW, k=k), orc.term_search(d, [A, B], [], INF, NOW), ("two", k))
             assert len(g2) > 50
             today = NOW // DAY
             for h in g2:
@@ -165,7 +128,7 @@ def test_k_edges_and_batch_layout(corpus):
     for qi, (q, g) in enumerate(zip(batch, got)):
         exp_rows = orc.term_search(d, q.include, q.exclude, INF, NOW)
         exp = orc.search(d, q.include, q.exclude, now_ms=NOW, k=q.k) if q.k else []
-        _same(g, exp, exp_rows, ("batch", qi))
+        qu.same_rows(g, exp, exp_rows, ("batch", qi))
         short += 0 < len(exp_rows) < q.k
         for i, h in enumerate(g):  # the raw buffer: row i of query qi at (qi * kmax + i) * 40
             assert rbuf[qi * kmax + i].tobytes() == h.row, (qi, i)
@@ -193,7 +156,7 @@ def test_doubledom_order_rows():
     d = _few_hosts(idx)
     lit = {h: [bytes(x) for x in rows] for h, rows in d.items()}
     big = [h for h, _ in sorted(d.items(), key=lambda kv: -len(kv[1]))[:3]]
-    ix = _open(d)
+    ix = iu.open_index(d)
     try:
         cases = [(inc, k) for inc in ([big[0]], [big[1], big[2]]) for k in (10, 100, 3000)]
         batch = [Query(inc, [], k=k, now_ms=NOW, filter=QueryFilter(skip_double_dom=True)) for inc, k in cases]
@@ -204,7 +167,7 @@ def test_doubledom_order_rows():
             lf = jl.QueryFilter(skip_double_dom=True) if q.filter is not None else None
             e = jl.search(lit, q.include, [], jl.RankingProfile(), "en", now_ms=NOW, k=q.k, filt=lf)
             assert [(h.urlhash, h.score) for h in g] == e
-            m = _row_map(orc.term_search(d, q.include, [], INF, NOW))
+            m = qu.row_map(orc.term_search(d, q.include, [], INF, NOW))
             assert all(h.row == m[h.urlhash] for h in g)
             changed += lf is not None and e != jl.search(lit, q.include, [], jl.RankingProfile(), "en", now_ms=NOW, k=q.k)
             alone = ix.search(q.include, [], k=q.k, now_ms=NOW, filter=q.filter, rows=True)
@@ -217,7 +180,6 @@ def test_doubledom_order_rows():
 def test_filter_quoted_urlselection_rows(corpus):
     """A filter with constraint, language, sitehash and a seeded doublecheck set; a quoted query
     (max_distance = nincl - 1); a urlselection query (rows of the index restricted to the selection)."""
-    from test_gpu_parity import _restrict
     cfg, idx, ix = corpus
     d = idx.as_dict()
     rng = np.random.default_rng(9)
@@ -235,7 +197,7 @@ def test_filter_quoted_urlselection_rows(corpus):
             g = ix.search(inc, [], k=100, now_ms=NOW, filter=QueryFilter(**kw), rows=True)
             e = jl.search(lit, inc, [], jl.RankingProfile(), "en", now_ms=NOW, k=100, filt=jl.QueryFilter(**kw))
             assert [(h.urlhash, h.score) for h in g] == e, kw
-            m = _row_map(orc.term_search(d, inc, [], INF, NOW))
+            m = qu.row_map(orc.term_search(d, inc, [], INF, NOW))
             assert all(h.row == m[h.urlhash] for h in g), kw
             nhit += len(g)
     assert nhit > 0
@@ -243,7 +205,7 @@ def test_filter_quoted_urlselection_rows(corpus):
     qs = [q for q in _queries(cfg, idx, 30, 15, 0) if len(q[0]) >= 2][:6] + [(big[:2], []), (big, [])]
     batch = [Query(inc, exc, max_distance=len(inc) - 1, k=100, now_ms=NOW) for inc, exc in qs]
     for q, g in zip(batch, ix.search_batch(batch, rows=True)):
-        _same(g, orc.search(d, q.include, q.exclude, max_distance=q.max_distance, now_ms=NOW, k=100),
+        qu.same_rows(g, orc.search(d, q.include, q.exclude, max_distance=q.max_distance, now_ms=NOW, k=100),
               orc.term_search(d, q.include, q.exclude, q.max_distance, NOW), ("quoted", q.include))
     # url selection
     urls = np.unique(np.asarray(idx.rows)[:, :12].copy().view("S12").ravel())
@@ -251,11 +213,11 @@ def test_filter_quoted_urlselection_rows(corpus):
     for frac in (0.05, 0.4):
         sel = [bytes(u) for u in rng.choice(urls, max(1, int(frac * len(urls))), replace=False)]
         sel += [b"AAAAAAAAAAA" + bytes([65 + i]) for i in range(3)]  # not in the index
-        rd = _restrict(d, sel)
+        rd = qu.restrict(d, sel)
         sq = _queries(cfg, idx, 12, 808, 2) + [([big[0]], []), (big[:2], [])]
         batch = [Query(inc, exc, now_ms=NOW, urlselection=sel) for inc, exc in sq]
         for q, g in zip(batch, ix.search_batch(batch, rows=True)):
-            _same(g, orc.search(rd, q.include, q.exclude, now_ms=NOW, k=100),
+            qu.same_rows(g, orc.search(rd, q.include, q.exclude, now_ms=NOW, k=100),
                   orc.term_search(rd, q.include, q.exclude, INF, NOW), ("selection", frac, q.include))
             nsel += len(g)
     assert nsel > 0
@@ -273,7 +235,7 @@ def test_rows_over_several_passes(corpus, gb, monkeypatch):
     batch = [Query(inc, exc, k=k, now_ms=NOW) for (inc, exc), k in zip(qs, [100, 7, 3000, 1] * 6)]
     got = ix.search_batch(batch, rows=True)
     for qi, (q, g) in enumerate(zip(batch, got)):
-        _same(g, orc.search(d, q.include, q.exclude, now_ms=NOW, k=q.k),
+        qu.same_rows(g, orc.search(d, q.include, q.exclude, now_ms=NOW, k=q.k),
               orc.term_search(d, q.include, q.exclude, INF, NOW), (gb, qi))
 
 
@@ -282,14 +244,13 @@ def test_async_pinned_and_landing(corpus):
     """Eight batches submitted before any wait: four with pinned buffers (written by the GPU
     directly), four with pageable ones (the landing path); one pinned rows buffer offset by 4
     bytes, which must land."""
-    from test_gpu_parity import _cqueries
     cfg, idx, ix = corpus
     d = idx.as_dict()
     kmax = 50
     tickets = []
     for s in range(8):
         b = [Query(inc, exc, k=50, now_ms=NOW) for inc, exc in _queries(cfg, idx, 7 + s, 60 + s, s % 2)]
-        arr, keep = _cqueries(b)
+        arr, keep = qu.cqueries(b)
         n = len(b)
         if s % 2:
             hits, nout = ix.host_array(CHit, n * kmax), ix.host_array(ctypes.c_int32, n)
@@ -313,7 +274,7 @@ def test_async_pinned_and_landing(corpus):
             got = [(bytes(hits[i * kmax + j].urlhash), hits[i * kmax + j].score, hits[i * kmax + j].tiebreak)
                    for j in range(nout[i])]
             assert got == orc.search(d, q.include, q.exclude, now_ms=NOW, k=q.k), (t, i)
-            m = _row_map(orc.term_search(d, q.include, q.exclude, INF, NOW))
+            m = qu.row_map(orc.term_search(d, q.include, q.exclude, INF, NOW))
             for j, (u, _, _) in enumerate(got):
                 assert view[i * kmax + j].tobytes() == m[u], (t, i, j)
     # the same through submit(rows=True) / PendingBatch.result
@@ -327,13 +288,12 @@ def test_async_pinned_and_landing(corpus):
 # ------------------------------------------------------------------ 7
 def test_null_rows_is_the_old_call(corpus):
     """rows40_out == NULL through the new entry points: hits and nout of the old ones."""
-    from test_gpu_parity import _cqueries
     from yacy_search_server_amd import _lib
     cfg, idx, ix = corpus
     b = [Query(inc, exc, k=k, now_ms=NOW)
          for (inc, exc), k in zip(_queries(cfg, idx, 12, 77), [100, 3, 3000, 0, 50, 1] * 2)]
     kmax, n = 3000, 12
-    arr, keep = _cqueries(b)
+    arr, keep = qu.cqueries(b)
 
     def bufs():
         return (CHit * (n * kmax))(), (ctypes.c_int32 * n)()
@@ -368,7 +328,6 @@ def test_null_rows_is_the_old_call(corpus):
 def test_sharded_rows_loopback(world):
     """Url-hash shards over the loopback transport: every rank ends with the oracle's hits; the
     rank owning a hit's url-hash range returns the oracle's row, every other rank 40 zero bytes."""
-    from test_gpu_shards_loopback import _run_parts
     cfg = synth.preset("tiny")
     idx = synth.build_index(cfg)
     whole = idx.as_dict()
@@ -386,7 +345,7 @@ def test_sharded_rows_loopback(world):
                        filter=QueryFilter(skip_double_dom=True) if dd else None) for inc, exc, prof, dd in cases]
         return ix.search_batch(batch, rows=True)
 
-    res = _run_parts(parts, world, run)
+    res = iu.run_parts(parts, world, run)
     sh = 6 - (world.bit_length() - 1)
     zero = bytes(40)
     spread = 0
@@ -396,7 +355,7 @@ def test_sharded_rows_loopback(world):
                                                 filt=jl.QueryFilter(skip_double_dom=True))]
         else:
             exp = [(u, s) for u, s, _ in orc.search(whole, inc, exc, orc.profile_from(prof), "en", now_ms=NOW, k=100)]
-        m = _row_map(orc.term_search(whole, inc, exc, INF, NOW))
+        m = qu.row_map(orc.term_search(whole, inc, exc, INF, NOW))
         for rk in range(world):
             assert [(h.urlhash, h.score) for h in res[rk][ci]] == exp, (world, rk, ci)
         owners = set()
@@ -418,13 +377,13 @@ def test_adversarial_rows_returned():
     d[b"TERMadvFEW__"] = adv_rows(6200, 52, "few")
     d[b"TERMadvTIGHT"] = adv_rows(6200, 53, "tight")
     qs = [([h], []) for h in d] + [([A, B], []), ([A, B, C], []), ([A, B, C, D], []), ([A, B], [D]), ([A], [C])]
-    ix = _open(d)
+    ix = iu.open_index(d)
     try:
         for now in NOWS:
             for k in (100, 3000):
                 batch = [Query(inc, exc, k=k, now_ms=now) for inc, exc in qs]
                 for q, g in zip(batch, ix.search_batch(batch, rows=True)):
-                    _same(g, orc.search(d, q.include, q.exclude, now_ms=now, k=k),
+                    qu.same_rows(g, orc.search(d, q.include, q.exclude, now_ms=now, k=k),
                           orc.term_search(d, q.include, q.exclude, INF, now), (now, k, q.include, q.exclude))
     finally:
         ix.close()
@@ -434,14 +393,13 @@ def test_tying_twins_across_chunks():
     """Postings that tie on score and ByteArray.hashCode, spread over several 2048-posting
     chunks: the TreeSet keeps the first of each class, and the row returned with it is its own,
     not the rejected twin's (the twins' rows differ in their reserved bytes)."""
-    from test_gpu_parity import _collision_family
     rng = np.random.default_rng(23)
     alpha = np.frombuffer(jl.ALPHA, dtype=np.uint8)
     fams, seen = [], set()
     for f in range(100):
         base = bytes(rng.choice(alpha[:26], 2)) + b"".join(
             bytes([int(rng.integers(65, 90)), int(rng.integers(97 + 6, 97 + 25))]) for _ in range(5))
-        hs = [h for h in _collision_family(base, 5) if h not in seen]
+        hs = [h for h in qu.collision_family(base, 5) if h not in seen]
         seen.update(hs)
         fams.append(hs)
     filler = set()
@@ -471,14 +429,14 @@ def test_tying_twins_across_chunks():
     T, U = b"TERMtwins___", b"TERMtwinsB__"
     d = {T: rows, U: rows[::2].copy()}
     hc = dict(zip((bytes(r[:12]) for r in rows), hashcodes(rows)))
-    ix = _open(d)
+    ix = iu.open_index(d)
     try:
         for inc in ([T], [T, U]):
             joined = orc.term_search(d, inc, [], INF, NOW)
             for k in (100, 3000):
                 g = ix.search(inc, k=k, now_ms=NOW, rows=True)
                 exp = orc.search(d, inc, [], now_ms=NOW, k=k)
-                _same(g, exp, joined, (len(inc), k))
+                qu.same_rows(g, exp, joined, (len(inc), k))
                 assert all(h.row[:12] == h.urlhash for h in g)
             # the dedupe did reject twins: fewer (score, hashCode) classes among the hits' families than postings
             kept = {u for u, _, _ in exp}

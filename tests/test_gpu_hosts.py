@@ -5,40 +5,25 @@ statistics and the call's statistics equal the reference's, and a 40-query batch
 authority profiles alternating, with excludes) equals the oracle on the reference's lists and a
 fresh index built in full from them."""
 
-import os
-import threading
-
 import numpy as np
 import pytest
 
 import host_ref as hr
-import oracle as orc
+import index_util as iu
 import update_ref as ur
-from yacy_search_server_amd import Query, RankingProfile, RWIIndex, synth
-from yacy_search_server_amd import _lib
+from yacy_search_server_amd import _lib, synth
 from yacy_search_server_amd._lib import YrwiError
 
 pytestmark = pytest.mark.gpu
 
-NOW = 20741 * 86400000 + 4242
-C5 = RankingProfile("", "date=15,domlength=15,authority=13,tf=10")
-B64 = ur._B64
-STAT_KEYS = ("terms", "new_terms", "emptied_terms", "added", "replaced", "dropped", "removed")
+B64 = iu.B64
 B = _lib.HOST_LDS_MAX
 NOBODY = b"n0b0dy"
 H0, H5, H40, H63 = (hr.host_name(i) for i in (0, 5, 40, 63))
 
 
-def _enc(i, width):
-    out = bytearray()
-    for _ in range(width):
-        out.append(B64[i & 63])
-        i >>= 6
-    return bytes(reversed(out))
-
-
 def _term(i):
-    return b"-h" + _enc(i, 10)
+    return iu.term(i, b"-h")
 
 
 @pytest.fixture(scope="module")
@@ -65,62 +50,6 @@ def every_list(tiny):
     return hosts, new, exp, hr.count_hosts(lists, hosts)
 
 
-def _rows(idx, urls, start=0):
-    """hand-made rows: rows of the synthetic index as templates, the url hash set"""
-    r = idx.rows[(start + 13 * np.arange(len(urls))) % len(idx.rows)].copy()
-    for i, u in enumerate(urls):
-        r[i, :12] = np.frombuffer(u, dtype=np.uint8)
-    return r
-
-
-def _open(lists):
-    ix = RWIIndex(0)
-    for h, r in lists.items():
-        ix.add(h, r)
-    return ix
-
-
-def _batch(qs):
-    return [Query(inc, exc, now_ms=NOW, k=50, profile=(C5 if i % 2 else None)) for i, (inc, exc) in enumerate(qs)]
-
-
-def _hits(ix, qs):
-    return [[(h.urlhash, h.score, h.tiebreak) for h in r] for r in ix.search_batch(_batch(qs))]
-
-
-def _oracle(lists, qs):
-    out = []
-    for qi, (inc, exc) in enumerate(qs):
-        d = {h: lists[h] for h in inc + exc if h in lists}
-        out.append(orc.search(d, inc, exc, profile=(orc.profile_from(C5) if qi % 2 else None), now_ms=NOW, k=50))
-    return out
-
-
-def _same_lists(ix, lists, touched):
-    for t in touched:
-        exp = lists.get(t, np.zeros((0, 40), np.uint8))
-        assert ix.get_size(t) == len(exp), t
-        assert ix.get_list(t).tobytes() == exp.tobytes(), t
-
-
-def _verify(ix, lists, touched, qs, monkeypatch):
-    """the checks of a step (as tests/test_gpu_updates.py makes them)"""
-    _same_lists(ix, lists, touched)
-    assert ix.check_url_ids()[0] == 0
-    nterms, npost, _ = ix.stats()
-    assert (nterms, npost) == (len(lists), sum(len(r) for r in lists.values()))
-    got = _hits(ix, qs)
-    assert got == _oracle(lists, qs)
-    monkeypatch.setenv("YRWI_DICT_FULL", "1")
-    fresh = _open(lists)
-    try:
-        assert fresh.check_url_ids()[0] == 0
-        assert got == _hits(fresh, qs)
-    finally:
-        fresh.close()
-        monkeypatch.delenv("YRWI_DICT_FULL")
-
-
 def _count(ix, lists, hosts, terms=None, ref=None):
     counts, hit = ix.count_hosts(hosts, terms)
     exp = ref or hr.count_hosts(lists, hosts, terms)
@@ -132,7 +61,7 @@ def _remove(ix, lists, hosts, terms=None, ref=None):
     """remove on the device and on the reference; the stats must agree"""
     st = ix.remove_hosts(hosts, terms)
     new, exp = ref or hr.apply_remove_hosts(lists, hosts, terms)
-    assert {k: st[k] for k in STAT_KEYS} == exp, (st, exp)
+    assert {k: st[k] for k in iu.STAT_KEYS} == exp, (st, exp)
     return new, st
 
 
@@ -143,18 +72,16 @@ def test_every_list(tiny, every_list, monkeypatch, chunk):
     own); lists and stats are those of the default"""
     cfg, idx, lists, qs = tiny
     hosts, new, exp, cexp = every_list
-    if chunk is None:
-        monkeypatch.delenv("YRWI_RM_CHUNK", raising=False)
-    else:
-        monkeypatch.setenv("YRWI_RM_CHUNK", str(chunk))
+    iu.set_rm_chunk(monkeypatch, chunk)
+    if chunk is not None:
         assert max(len(l) for l in lists.values()) > 256
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
         counts = _count(ix, lists, hosts, ref=cexp)
         cur, st = _remove(ix, lists, hosts, ref=(new, exp))
         assert sum(dict(zip(hosts, counts)).values()) == st["removed"] == 15128  # over the unique hosts
-        _verify(ix, cur, list(lists), qs, monkeypatch)
+        iu.verify_step(ix, cur, list(lists), qs, monkeypatch)
         _, st = _remove(ix, cur, hosts)  # nothing left to remove: nothing changes
         assert st["removed"] == 0 and st["terms"] == 0
     finally:
@@ -166,11 +93,8 @@ def test_more_chunks_more_launches(tiny, every_list, monkeypatch):
     hosts, new, exp, _ = every_list
     st = {}
     for chunk in (None, 256):
-        if chunk is None:
-            monkeypatch.delenv("YRWI_RM_CHUNK", raising=False)
-        else:
-            monkeypatch.setenv("YRWI_RM_CHUNK", str(chunk))
-        ix = _open(lists)
+        iu.set_rm_chunk(monkeypatch, chunk)
+        ix = iu.open_index(lists)
         try:
             _, st[chunk] = _remove(ix, lists, hosts, ref=(new, exp))
         finally:
@@ -189,7 +113,7 @@ def test_named_lists(tiny, monkeypatch):
     assert len(set(terms)) == 29 and len(terms) == 30
     with_host = [t for t in named if has(t)]
     assert 0 < len(with_host) < len(named) and any(has(t) for t in order if t not in named)
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
         _count(ix, lists, [H63, H63], terms)
@@ -198,7 +122,7 @@ def test_named_lists(tiny, monkeypatch):
         for t in order:  # lists not named, and named lists without the host, keep their bytes
             if t not in with_host:
                 assert cur[t] is lists[t]
-        _verify(ix, cur, order, qs, monkeypatch)
+        iu.verify_step(ix, cur, order, qs, monkeypatch)
     finally:
         ix.close()
 
@@ -223,9 +147,9 @@ def test_boundaries(tiny, monkeypatch):
     hand, k = {}, 0
     for n in SIZES:
         for name, member in PATTERNS.items():
-            urls = [_enc(1000 * k + i, 6) + (gone if member(i, n) else stay) for i in range(n)]
+            urls = [iu.enc(1000 * k + i, 6) + (gone if member(i, n) else stay) for i in range(n)]
             assert urls == sorted(urls, key=ur.url_key)
-            hand[_term(k)] = _rows(idx, urls, start=k)
+            hand[_term(k)] = iu.rows(idx, urls, start=k)
             k += 1
     terms = list(hand)
     all_lists = {**lists, **hand}
@@ -236,13 +160,13 @@ def test_boundaries(tiny, monkeypatch):
     assert losing == len(hand) - len(SIZES) - 2  # all but no_row at each size and two more 1-row lists
     qs = qs[:34] + [([terms[6], terms[12]], []), ([terms[18]], [terms[24]]), ([terms[30], terms[36]], []),
                     ([terms[42], terms[43]], [terms[44]]), ([terms[45]], []), ([terms[7], terms[8]], [])]
-    ix = _open(all_lists)
+    ix = iu.open_index(all_lists)
     try:
         ix.build_url_ids()
         _count(ix, all_lists, [gone, stay, NOBODY])
         cur, st = _remove(ix, all_lists, [gone, NOBODY])
         assert st["emptied_terms"] == emptied and st["terms"] == losing
-        _verify(ix, cur, terms + list(lists)[:10], qs, monkeypatch)
+        iu.verify_step(ix, cur, terms + list(lists)[:10], qs, monkeypatch)
     finally:
         ix.close()
 
@@ -255,7 +179,7 @@ REAL = [FIRST, H0, H5, H40, H63, LAST]
 def _host_set(n):
     """n hosts: REAL among hosts nobody has ('B....' below and 'y....' above the corpus's), so that the
     hosts with postings sit at the first, the middle and the last positions of the sorted set"""
-    fill = [bytes([B64[1 + i % 2 * 49]]) + _enc(i, 5) for i in range(n - len(REAL))]
+    fill = [bytes([B64[1 + i % 2 * 49]]) + iu.enc(i, 5) for i in range(n - len(REAL))]
     hs = fill[: len(fill) // 2] + REAL + fill[len(fill) // 2:]
     key = sorted(hs, key=ur.url_key)
     assert len(set(hs)) == n and key[0] == FIRST and key[-1] == LAST and abs(key.index(H0) - n // 2) <= 3
@@ -268,8 +192,8 @@ def across(tiny):
     reference of every set of _host_set: the hosts it adds have no posting (checked)"""
     cfg, idx, lists, qs = tiny
     extra = _term(500)
-    urls = [_enc(i, 6) + (FIRST, LAST, OTHER)[i % 3] for i in range(300)]
-    lists = {**lists, extra: _rows(idx, urls)}
+    urls = [iu.enc(i, 6) + (FIRST, LAST, OTHER)[i % 3] for i in range(300)]
+    lists = {**lists, extra: iu.rows(idx, urls)}
     have = {bytes(r[6:12]) for l in lists.values() for r in l}
     assert not have & (set(_host_set(4 * B)) - set(REAL)) and set(REAL) <= have
     qs = qs[:38] + [([extra], []), ([extra, list(lists)[0]], [])]
@@ -283,7 +207,7 @@ def test_set_sizes_across_the_lds_bound(across, monkeypatch, n):
     memory; B, B + 1 and 4 B give one reference's lists, counts and stats, so the same as each other"""
     lists, qs, ref, cref, hit = across
     hosts = [H0] if n == 1 else _host_set(n)
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
         if n == 1:
@@ -293,7 +217,7 @@ def test_set_sizes_across_the_lds_bound(across, monkeypatch, n):
             counts = _count(ix, lists, hosts, ref=([cref.get(h, 0) for h in hosts], hit))
             cur, st = _remove(ix, lists, hosts, ref=ref)
         assert st["removed"] == sum(counts) > 0
-        _verify(ix, cur, list(lists), qs, monkeypatch)
+        iu.verify_step(ix, cur, list(lists), qs, monkeypatch)
     finally:
         ix.close()
 
@@ -306,10 +230,10 @@ def test_hot_spot(tiny, monkeypatch):
     big = _term(900)
     three = [t for t in sorted(lists) if len(lists[t]) >= 300][:3]
     small = {t: lists[t][:300] for t in three}
-    small[big] = _rows(idx, [_enc(i, 6) + hot for i in range(20000)])
+    small[big] = iu.rows(idx, [iu.enc(i, 6) + hot for i in range(20000)])
     qs = [([big], []), ([three[0]], [big]), ([three[0], three[1]], []), ([three[2]], [three[0]]), ([three[1]], []),
           ([three[2], three[1]], [])]
-    ix = _open(small)
+    ix = iu.open_index(small)
     try:
         ix.build_url_ids()
         counts = _count(ix, small, [hot, H0, NOBODY])
@@ -318,7 +242,7 @@ def test_hot_spot(tiny, monkeypatch):
         assert st["removed"] == counts[0] + counts[1] and st["emptied_terms"] == 1 and big not in cur
         for t in three:
             assert cur[t].tobytes() == small[t][(small[t][:, 6:12] != np.frombuffer(H0, np.uint8)).any(axis=1)].tobytes()
-        _verify(ix, cur, list(small), qs, monkeypatch)
+        iu.verify_step(ix, cur, list(small), qs, monkeypatch)
     finally:
         ix.close()
 
@@ -327,11 +251,11 @@ def test_hot_spot(tiny, monkeypatch):
 def test_launches_and_syncs_are_a_function_of_the_chunks(tiny, monkeypatch):
     cfg, idx, lists, qs = tiny
     monkeypatch.delenv("YRWI_RM_CHUNK", raising=False)
-    fill = [b"B" + _enc(i, 5) for i in range(4 * B - 1)]
+    fill = [b"B" + iu.enc(i, 5) for i in range(4 * B - 1)]
     one = sorted(lists)[0]
     st = []
     for hosts, terms in (([H0], [one]), ([H0], None), ([H0] + fill, None)):
-        ix = _open(lists)
+        ix = iu.open_index(lists)
         try:
             st.append(_remove(ix, lists, hosts, terms)[1])
         finally:
@@ -339,7 +263,7 @@ def test_launches_and_syncs_are_a_function_of_the_chunks(tiny, monkeypatch):
     assert st[0]["terms"] == 1 and st[1]["terms"] == st[2]["terms"] == 200
     assert len({(s["launches"], s["syncs"]) for s in st}) == 1, st
     # a steady sequence of calls makes no device-wide allocation after the first
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.count_hosts([H0, H5], None)
         ix.remove_hosts([H63], None)
@@ -355,7 +279,7 @@ def test_launches_and_syncs_are_a_function_of_the_chunks(tiny, monkeypatch):
 # ------------------------------------------------------------------ 8: count_hosts changes nothing
 def test_count_changes_nothing(tiny):
     cfg, idx, lists, qs = tiny
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
         info, stats = ix.index_info(), ix.stats()
@@ -363,7 +287,7 @@ def test_count_changes_nothing(tiny):
         _count(ix, lists, [H40], sorted(lists)[:20])
         assert ix.count_hosts([H0], [])[1] == 0 and list(ix.count_hosts([], None)[0]) == []
         assert ix.index_info() == info and ix.stats() == stats
-        _same_lists(ix, lists, list(lists))
+        iu.same_lists(ix, lists, list(lists))
         assert ix.index_info() == info
     finally:
         ix.close()
@@ -372,7 +296,7 @@ def test_count_changes_nothing(tiny):
 # ------------------------------------------------------------------ 9: errors are atomic
 def test_errors_are_atomic(tiny):
     cfg, idx, lists, qs = tiny
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
         before = ix.stats()
@@ -385,9 +309,9 @@ def test_errors_are_atomic(tiny):
                 call([H0], [some[0], b"bad#term_ash"])
             assert e.value.rc == -2
         assert ix.stats() == before
-        _same_lists(ix, lists, some)
+        iu.same_lists(ix, lists, some)
         st = ix.remove_hosts([], None)
-        assert all(v == 0 for v in st.values()) and set(STAT_KEYS) <= set(st)
+        assert all(v == 0 for v in st.values()) and set(iu.STAT_KEYS) <= set(st)
         assert all(v == 0 for v in ix.remove_hosts([H0], []).values())
         assert ix.stats() == before
         assert ix.check_url_ids()[0] == 0
@@ -402,41 +326,18 @@ def test_two_shards(tiny, every_list):
     cfg, idx, lists, qs = tiny
     hosts, whole, exp, (cexp, _) = every_list
     world = 2
-    rank_of = lambda l: np.array([ur.url_key(bytes(r[:12]))[0] >> 5 for r in l])  # Distribution.verticalDHTPosition, world 2
-    parts = [{t: l[rank_of(l) == r] for t, l in lists.items()} for r in range(world)]
-    parts = [{t: l for t, l in p.items() if len(l)} for p in parts]
-    uid = b"YRWI-LOOPBACK\0" + os.urandom(114)
-    ixs, out, errs = [None] * world, [None] * world, []
+    parts = iu.split_by_rank(lists, world)
 
-    def opener(r):
-        try:
-            ixs[r] = RWIIndex(0, shard=(r, world, uid))
-            for h, rr in parts[r].items():
-                ixs[r].add(h, rr)
-        except Exception as e:  # pragma: no cover - reported below
-            errs.append(repr(e))
+    def fn(r, ix):
+        counts, _ = ix.count_hosts(hosts, None)
+        st = ix.remove_hosts(hosts, None)
+        assert ix.check_url_ids()[0] == 0
+        return list(counts), st, {t: ix.get_list(t) for t in lists}
 
-    def runner(r):
-        try:
-            counts, _ = ixs[r].count_hosts(hosts, None)
-            st = ixs[r].remove_hosts(hosts, None)
-            assert ixs[r].check_url_ids()[0] == 0
-            out[r] = (list(counts), st, {t: ixs[r].get_list(t) for t in lists})
-        except Exception as e:  # pragma: no cover
-            errs.append(repr(e))
-
-    for fn in (opener, runner):
-        ths = [threading.Thread(target=fn, args=(r,)) for r in range(world)]
-        for t in ths:
-            t.start()
-        for t in ths:
-            t.join(timeout=300)
-        assert not errs, errs
-    for ix in ixs:
-        ix.close()
+    out = iu.run_parts(parts, world, fn)
     assert [a + b for a, b in zip(out[0][0], out[1][0])] == cexp
     assert out[0][1]["removed"] + out[1][1]["removed"] == exp["removed"]
     assert out[0][1]["removed"] > 0 and out[1][1]["removed"] > 0
     for t in lists:
         got = np.concatenate([out[0][2][t], out[1][2][t]])
-        assert got.tobytes() == whole.get(t, np.zeros((0, 40), np.uint8)).tobytes(), t
+        assert got.tobytes() == whole.get(t, iu.EMPTY).tobytes(), t

@@ -8,6 +8,7 @@ import pytest
 
 import java_literal as jl
 import oracle as orc
+import query_util as qu
 from kat_util import kat_index, kat_profile, load_kats, run_kat
 from yacy_search_server_amd import Query, RankingProfile, RWIIndex, synth
 
@@ -63,19 +64,6 @@ def corpus(request):
     ix.close()
 
 
-def _profiles():
-    c5 = jl.RankingProfile.parse("", "date=15,domlength=15,authority=13,tf=10")
-    date = jl.RankingProfile()
-    date.all_zero()
-    date.coeff_date = 15
-    rng = np.random.default_rng(3)
-    rnd = jl.RankingProfile()
-    for _, f in jl.PROFILE_FIELDS:
-        setattr(rnd, f, int(rng.integers(0, 16)))
-    rnd.coeff_urlcomps = 27
-    return [("default", jl.RankingProfile()), ("c5", c5), ("date", date), ("rand", rnd)]
-
-
 def test_join_rows_bit_exact(corpus):
     cfg, idx, ix = corpus
     d = idx.as_dict()
@@ -93,7 +81,7 @@ def test_topk_bit_exact(corpus):
     cfg, idx, ix = corpus
     d = idx.as_dict()
     qs = synth.queries(cfg, 20, 1, 4, 1, qseed=12)
-    for pname, prof in _profiles():
+    for pname, prof in qu.profiles():
         for now in (NOW, 15500 * 86400000 + 7):
             batch = [Query([idx.hashes[t] for t in inc], [idx.hashes[t] for t in exc], k=100,
                            profile=_rp(prof), now_ms=now) for inc, exc in qs]
@@ -111,7 +99,7 @@ def test_normalize_score_bit_exact(corpus):
         rows = orc.term_search(d, ih, [], 2147483647, NOW)
         if len(rows) == 0:
             continue
-        for pname, prof in _profiles():
+        for pname, prof in qu.profiles():
             exp, _ = orc.normalize_score(rows, orc.profile_from(prof), "en", NOW)
             got = ix.normalize_score(rows, _rp(prof), "en", NOW)
             assert np.array_equal(got, exp), pname
@@ -165,7 +153,7 @@ def test_fold_overflow_paths():
         rows[:, 38] = rng.integers(0, 256, n)
         rows[:, 33] = rng.integers(1, 20, n)
         ix = RWIIndex(0)
-        for name, prof in _profiles():
+        for name, prof in qu.profiles():
             exp, nm = orc.normalize_score(rows, orc.profile_from(prof), "en", NOW)
             got = ix.normalize_score(rows, _rp(prof), "en", NOW)
             assert np.array_equal(got, exp), name
@@ -417,7 +405,7 @@ def test_compaction_pieces(algo, chain, monkeypatch):
             ix.add(h, r)
         qs = [([A, B], []), ([B, A], []), ([A, C], []), ([B, D], []), ([A, B, C], []), ([A, C, D], []),
               ([A, B], [E]), ([A, B, C], [E]), ([D, E], [])]
-        for pname, prof in _profiles():
+        for pname, prof in qu.profiles():
             batch = [Query(inc, exc, k=100, profile=_rp(prof), now_ms=NOW) for inc, exc in qs]
             for qi, (q, g) in enumerate(zip(batch, ix.search_batch(batch))):
                 exp = orc.search(d, q.include, q.exclude, orc.profile_from(prof), "en", now_ms=NOW, k=100)
@@ -499,19 +487,6 @@ def test_batch_split_by_scratch_budget(corpus, gb, monkeypatch):
         assert [(h.urlhash, h.score) for h in g] == [(h, s) for h, s, _ in exp], (gb, qi)
 
 
-def _collision_family(base, n_blocks=6):
-    """64 url hashes with one Java hashCode: 6 two-char blocks, each either
-    (x, y) or (x + 1, y - 31) -- equal 31 * x + y."""
-    out = []
-    for m in range(1 << n_blocks):
-        h = bytearray(base[:12 - 2 * n_blocks])
-        for j in range(n_blocks):
-            x, y = base[12 - 2 * n_blocks + 2 * j], base[12 - 2 * n_blocks + 2 * j + 1]
-            h += bytes([x + 1, y - 31]) if (m >> j) & 1 else bytes([x, y])
-        out.append(bytes(h))
-    return out
-
-
 def test_treeset_dedupe_across_chunks():
     """Many postings tying in (score, ByteArray.hashCode) spread over several
     2048-posting chunks: the TreeSet keeps the first arrival of each class, so
@@ -523,7 +498,7 @@ def test_treeset_dedupe_across_chunks():
         # x in A..Y, y in g..x: (x + 1, y - 31) is again a pair of valid url-hash characters
         base = bytes(rng.choice(np.frombuffer(jl.ALPHA[:26], dtype=np.uint8), 2)) + b"".join(
             bytes([int(rng.integers(65, 90)), int(rng.integers(97 + 6, 97 + 25))]) for _ in range(5))
-        fam.append((f, _collision_family(base, 5)))
+        fam.append((f, qu.collision_family(base, 5)))
     hashes = {}
     for f, hs in fam:
         assert len({jl.bytearray_hashcode(h) for h in hs}) == 1
@@ -559,28 +534,6 @@ def test_treeset_dedupe_across_chunks():
     ix.close()
 
 
-def _cqueries(batch):
-    from yacy_search_server_amd._lib import CQuery
-    import ctypes
-    arr = (CQuery * len(batch))()
-    keep = []
-    for i, q in enumerate(batch):
-        ib = ctypes.create_string_buffer(b"".join(q.include), max(1, 12 * len(q.include)))
-        eb = ctypes.create_string_buffer(b"".join(q.exclude), max(1, 12 * len(q.exclude)))
-        prof = RankingProfile()
-        keep += [ib, eb, prof]
-        arr[i].incl = ctypes.cast(ib, ctypes.c_void_p)
-        arr[i].nincl = len(q.include)
-        arr[i].excl = ctypes.cast(eb, ctypes.c_void_p)
-        arr[i].nexcl = len(q.exclude)
-        arr[i].max_distance = q.max_distance
-        arr[i].k = q.k
-        arr[i].profile = ctypes.pointer(prof.c)
-        arr[i].language = b"en"
-        arr[i].now_ms = q.now_ms
-    return arr, keep
-
-
 def test_async_batches_pinned_and_pageable(corpus):
     """yrwi_query_batch_submit/_wait: several batches in flight on the lanes, results
     in pinned (yrwi_host_alloc, written by the GPU directly) and in pageable buffers,
@@ -597,7 +550,7 @@ def test_async_batches_pinned_and_pageable(corpus):
     kmax = 50
     tickets = []
     for s, b in enumerate(batches):
-        arr, keep = _cqueries(b)
+        arr, keep = qu.cqueries(b)
         if s % 2:
             hits, nout = ix.host_array(CHit, len(b) * kmax), ix.host_array(ctypes.c_int32, len(b))
         else:
@@ -654,7 +607,7 @@ def test_null_stats_production_path(corpus):
     for s in range(10):
         qs = synth.queries(cfg, 6 + s, 1 + s % 3, 2 + s % 3, s % 2, qseed=900 + s)
         b = [Query([idx.hashes[t] for t in inc], [idx.hashes[t] for t in exc], k=kmax, now_ms=NOW) for inc, exc in qs]
-        arr, keep = _cqueries(b)
+        arr, keep = qu.cqueries(b)
         hits, nout = ix.host_array(CHit, len(b) * kmax), ix.host_array(ctypes.c_int32, len(b))
         pend.append((ix.submit_raw(arr, len(b), kmax, hits, nout, None), b, hits, nout, keep, arr))
     for t, b, hits, nout, keep, arr in pend:
@@ -728,19 +681,6 @@ def test_chained_folds_long_lists(long_lists, bm, cf, monkeypatch):
         ix.close()
 
 
-def _restrict(d, sel):
-    """ReferenceContainerCache.get(key, urlselection) (ReferenceContainerCache.java:448-470) for
-    every list: the rows whose url hash is in the selection, in their order; an emptied list is
-    what searchConjunction treats as absent (AbstractIndex.java:118-121)."""
-    s = set(sel)
-    out = {}
-    for h, rows in d.items():
-        r = rows[np.fromiter((bytes(x[:12]) in s for x in rows), dtype=bool, count=len(rows))]
-        if len(r):
-            out[h] = r
-    return out
-
-
 def test_urlselection_restricts_every_list(corpus):
     """TermSearch's urlselection (yrwi_query_desc.urlselection): every include and exclude
     list restricted to the selected urls before the conjunction, so J1, the J2 fold order and
@@ -758,7 +698,7 @@ def test_urlselection_restricts_every_list(corpus):
         m = max(1, int(frac * len(urls)))
         sel = [bytes(u) for u in rng.choice(urls, m, replace=False)]
         sel += [b"AAAAAAAAAAA" + bytes([65 + i]) for i in range(3)]  # not in the index
-        rd = _restrict(d, sel)
+        rd = qu.restrict(d, sel)
         batch = [Query([idx.hashes[t] for t in inc], [idx.hashes[t] for t in exc], now_ms=NOW, urlselection=sel)
                  for inc, exc in qs]
         for q, g in zip(batch, ix.search_batch(batch)):

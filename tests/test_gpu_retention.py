@@ -6,24 +6,16 @@ statistics and both statistics structs equal the reference's, and a 40-query bat
 profiles alternating, with excludes) equals the oracle on the reference's lists and a fresh index built in
 full from them."""
 
-import os
-import threading
-
 import numpy as np
 import pytest
 
-import oracle as orc
+import index_util as iu
 import retention_cases as rc
 import retention_ref as rr
-import update_ref as ur
-from yacy_search_server_amd import Query, RankingProfile, RWIIndex, synth
+from yacy_search_server_amd import synth
 from yacy_search_server_amd._lib import YrwiError
 
 pytestmark = pytest.mark.gpu
-
-NOW = 20741 * 86400000 + 4242
-C5 = RankingProfile("", "date=15,domlength=15,authority=13,tf=10")
-
 
 @pytest.fixture(scope="module")
 def tiny():
@@ -47,13 +39,6 @@ def three_ways(tiny):
     return {k: (r, rr.apply_retention(lists, *r)) for k, r in rules.items()}
 
 
-def _open(lists):
-    ix = RWIIndex(0)
-    for h, r in lists.items():
-        ix.add(h, r)
-    return ix
-
-
 def _queries(terms, n=40):
     """n queries over the given terms: two includes and, every third query, an exclude"""
     t, m = list(terms), len(terms)
@@ -65,47 +50,6 @@ def _queries(terms, n=40):
         inc = [t[a]] + ([t[b]] if b != a else [])
         out.append((inc, [t[c]] if i % 3 == 0 and c not in (a, b) else []))
     return out
-
-
-def _batch(qs):
-    return [Query(inc, exc, now_ms=NOW, k=50, profile=(C5 if i % 2 else None)) for i, (inc, exc) in enumerate(qs)]
-
-
-def _hits(ix, qs):
-    return [[(h.urlhash, h.score, h.tiebreak) for h in r] for r in ix.search_batch(_batch(qs))]
-
-
-def _oracle(lists, qs):
-    out = []
-    for qi, (inc, exc) in enumerate(qs):
-        d = {h: lists[h] for h in inc + exc if h in lists}
-        out.append(orc.search(d, inc, exc, profile=(orc.profile_from(C5) if qi % 2 else None), now_ms=NOW, k=50))
-    return out
-
-
-def _same_lists(ix, lists, touched):
-    for t in touched:
-        exp = lists.get(t, np.zeros((0, 40), np.uint8))
-        assert ix.get_size(t) == len(exp), t
-        assert ix.get_list(t).tobytes() == exp.tobytes(), t
-
-
-def _verify(ix, lists, touched, qs, monkeypatch):
-    """the checks of a step (as tests/test_gpu_hosts.py makes them)"""
-    _same_lists(ix, lists, touched)
-    assert ix.check_url_ids()[0] == 0
-    nterms, npost, _ = ix.stats()
-    assert (nterms, npost) == (len(lists), sum(len(r) for r in lists.values()))
-    got = _hits(ix, qs)
-    assert got == _oracle(lists, qs)
-    monkeypatch.setenv("YRWI_DICT_FULL", "1")
-    fresh = _open(lists)
-    try:
-        assert fresh.check_url_ids()[0] == 0
-        assert got == _hits(fresh, qs)
-    finally:
-        fresh.close()
-        monkeypatch.delenv("YRWI_DICT_FULL")
 
 
 def _counts(st):
@@ -138,13 +82,6 @@ def _retain(ix, lists, min_day, max_refs, terms=None, ref=None):
     return new, st, rst
 
 
-def _set_chunk(monkeypatch, chunk):
-    if chunk is None:
-        monkeypatch.delenv("YRWI_RM_CHUNK", raising=False)
-    else:
-        monkeypatch.setenv("YRWI_RM_CHUNK", str(chunk))
-
-
 # ------------------------------------------------------------------ 1: every list, three ways, three chunk sizes
 @pytest.mark.parametrize("chunk", [None, 256, 4096])
 @pytest.mark.parametrize("way", ["age", "cap", "both"])
@@ -154,8 +91,8 @@ def test_every_list(tiny, three_ways, monkeypatch, way, chunk):
     at every chunk size"""
     base, lists, qs, median, cap = tiny
     (min_day, max_refs), ref = three_ways[way]
-    _set_chunk(monkeypatch, chunk)
-    ix = _open(lists)
+    iu.set_rm_chunk(monkeypatch, chunk)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
         cur, st, rst = _retain(ix, lists, min_day, max_refs, ref=ref)
@@ -165,7 +102,7 @@ def test_every_list(tiny, three_ways, monkeypatch, way, chunk):
             assert rst["lists_cap"] > 100 and rst["removed_age"] == 0
         if way == "both":
             assert rst["removed_age"] > 0 and rst["removed_cap"] > 0
-        _verify(ix, cur, list(lists), qs, monkeypatch)
+        iu.verify_step(ix, cur, list(lists), qs, monkeypatch)
         _, st, rst = _retain(ix, cur, min_day, max_refs)  # a second identical call removes nothing
         assert st["removed"] == 0 and st["terms"] == 0 and rst["lists"] == len(cur)
     finally:
@@ -178,8 +115,8 @@ def test_more_chunks_more_launches(tiny, three_ways, monkeypatch, way):
     (min_day, max_refs), ref = three_ways[way]
     st = {}
     for chunk in (None, 256):
-        _set_chunk(monkeypatch, chunk)
-        ix = _open(lists)
+        iu.set_rm_chunk(monkeypatch, chunk)
+        ix = iu.open_index(lists)
         try:
             st[chunk] = ix.retain(min_day, max_refs)[0]
         finally:
@@ -202,13 +139,13 @@ def test_edges(edges, monkeypatch, cap):
     (256) and list edges of the flattened index; every cap of 1, n - 1, n and n + 1 over the sizes"""
     lists, what, qs = edges
     monkeypatch.delenv("YRWI_RM_CHUNK", raising=False)
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
         cur, st, rst = _retain(ix, lists, 0, cap)
         rc.check_edges(lists, what, cur, cap)
         assert rst["lists_cap"] == sum(1 for n, _ in what.values() if n > cap)
-        _verify(ix, cur, list(lists), qs, monkeypatch)
+        iu.verify_step(ix, cur, list(lists), qs, monkeypatch)
     finally:
         ix.close()
 
@@ -218,13 +155,13 @@ def test_edges(edges, monkeypatch, cap):
 def test_ties_single_day(tiny, monkeypatch, cap):
     lists = rc.tie_lists(tiny[0])
     monkeypatch.delenv("YRWI_RM_CHUNK", raising=False)
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
         cur, st, rst = _retain(ix, lists, 0, cap)
         for t in lists:  # exactly the first `cap` rows in url order stay
             assert cur[t].tobytes() == lists[t][:cap].tobytes()
-        _verify(ix, cur, list(lists), _queries(list(lists)), monkeypatch)
+        iu.verify_step(ix, cur, list(lists), _queries(list(lists)), monkeypatch)
     finally:
         ix.close()
 
@@ -234,13 +171,13 @@ def test_ties_scattered(tiny, monkeypatch):
     than YRWI_RM_CHUNK and so a chunk of its own"""
     lists, ends = rc.scatter_lists(tiny[0])
     monkeypatch.setenv("YRWI_RM_CHUNK", "256")
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
         cur, st, rst = _retain(ix, lists, 0, rc.SCATTER_CAP, terms=list(lists))
         rc.check_scatter(lists, ends, cur)
         assert rst["lists_cap"] == len(lists) and rst["removed_cap"] == len(lists) * (rc.SCATTER_N - rc.SCATTER_CAP)
-        _verify(ix, cur, list(lists), _queries(list(lists)), monkeypatch)
+        iu.verify_step(ix, cur, list(lists), _queries(list(lists)), monkeypatch)
     finally:
         ix.close()
 
@@ -251,17 +188,17 @@ def test_age_meets_cap(tiny, monkeypatch):
     exact, plus, emptied = list(lists)
     qs = _queries(list(lists))
     monkeypatch.delenv("YRWI_RM_CHUNK", raising=False)
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
         cur, st, rst = _retain(ix, lists, rc.AGE_MIN_DAY, rc.AGE_CAP)
         # exactly max_refs left by the age rule: no cap removal; one more: the cap removes one; none: emptied
         assert (rst["lists_age"], rst["lists_cap"], rst["removed_cap"], rst["emptied_terms"]) == (3, 1, 1, 1)
         assert len(cur[exact]) == len(cur[plus]) == rc.AGE_CAP and emptied not in cur and st["emptied_terms"] == 1
-        _verify(ix, cur, list(lists), qs, monkeypatch)
+        iu.verify_step(ix, cur, list(lists), qs, monkeypatch)
         cur2, st, rst = _retain(ix, cur, 65536, 0, terms=[plus])  # everything selected goes
         assert set(cur2) == {exact} and st["removed"] == rc.AGE_CAP and st["emptied_terms"] == 1
-        _verify(ix, cur2, list(lists), qs, monkeypatch)
+        iu.verify_step(ix, cur2, list(lists), qs, monkeypatch)
     finally:
         ix.close()
 
@@ -274,14 +211,14 @@ def test_many_small_lists(tiny, monkeypatch):
     shape = {}
     for count in (30, 3000):
         lists = rc.small_lists(tiny[0], count)
-        ix = _open(lists)
+        ix = iu.open_index(lists)
         try:
             ix.build_url_ids()
             cur, st, rst = _retain(ix, lists, 150, 1)
             assert rst["lists_age"] > 0 and rst["lists_cap"] > 0 and rst["emptied_terms"] > 0
             assert all(len(l) == 1 for l in cur.values())
             shape[count] = (st["launches"], st["syncs"])
-            _verify(ix, cur, list(lists), _queries(list(lists)[:: max(1, count // 60)]), monkeypatch)
+            iu.verify_step(ix, cur, list(lists), _queries(list(lists)[:: max(1, count // 60)]), monkeypatch)
         finally:
             ix.close()
     assert shape[30] == shape[3000], shape
@@ -297,7 +234,7 @@ def test_hot_list(tiny, monkeypatch):
     big = rc.term(900)
     small[big] = rc.hot_list(base)
     monkeypatch.delenv("YRWI_RM_CHUNK", raising=False)
-    ix = _open(small)
+    ix = iu.open_index(small)
     try:
         ix.build_url_ids()
         cur, st, rst = _retain(ix, small, 0, rc.HOT_CAP)
@@ -306,7 +243,7 @@ def test_hot_list(tiny, monkeypatch):
         assert set(a) == {20002} and (rr.days_of(small[big]) == 20002).sum() > rc.HOT_CAP
         for t in three:
             assert cur[t] is small[t]
-        _verify(ix, cur, list(small), _queries(list(small)), monkeypatch)
+        iu.verify_step(ix, cur, list(small), _queries(list(small)), monkeypatch)
     finally:
         ix.close()
 
@@ -317,7 +254,7 @@ def test_histogram_paths(tiny):
     also go straight to the device table; both histograms are exact (checked in _dry)"""
     base = tiny[0]
     for lists, spread in ((rc.band_lists(base), False), (rc.spread_lists(base), True)):
-        ix = _open(lists)
+        ix = iu.open_index(lists)
         try:
             before = ix.stats()
             st = _dry(ix, lists, 0, 0)
@@ -328,7 +265,7 @@ def test_histogram_paths(tiny):
             st = _dry(ix, lists, 30000, 100, terms=list(lists)[:2])
             assert (st["hist_bypass"] > 0) == spread and st["lists"] == 2
             assert ix.stats() == before
-            _same_lists(ix, lists, list(lists))
+            iu.same_lists(ix, lists, list(lists))
         finally:
             ix.close()
 
@@ -341,7 +278,7 @@ def test_named_lists(tiny, monkeypatch):
     terms = named + [named[3], rc.term(77)]  # 30 terms named: one of them twice, one nobody has
     assert len(set(terms)) == 29 and len(terms) == 30
     monkeypatch.delenv("YRWI_RM_CHUNK", raising=False)
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
         cur, st, rst = _retain(ix, lists, median, cap, terms)
@@ -349,17 +286,17 @@ def test_named_lists(tiny, monkeypatch):
         for t in order:  # lists not named keep their bytes
             if t not in named:
                 assert cur[t] is lists[t]
-        _verify(ix, cur, order, qs, monkeypatch)
+        iu.verify_step(ix, cur, order, qs, monkeypatch)
     finally:
         ix.close()
 
 
 def test_errors_and_noops(tiny):
     base, lists, qs, median, cap = tiny
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
-        before, hits = ix.stats(), _hits(ix, qs)
+        before, hits = ix.stats(), iu.hits(ix, qs)
         some = sorted(lists)[:3]
         for call in (ix.retain, ix.retention_count):
             for args, rc_ in (((median, cap, [some[0], b"bad#term_ash"]), -2), ((-1, 0), -1), ((65537, 0), -1),
@@ -368,8 +305,8 @@ def test_errors_and_noops(tiny):
                     call(*args)
                 assert e.value.rc == rc_, args
                 assert ix.stats() == before  # after each error: the statistics, every list, a query batch
-                _same_lists(ix, lists, list(lists))
-                assert _hits(ix, qs) == hits
+                iu.same_lists(ix, lists, list(lists))
+                assert iu.hits(ix, qs) == hits
         st, rst = ix.retain(0, 0)  # no rule: nothing is enqueued
         assert (st["launches"], rst["launches"], st["removed"], st["terms"]) == (0, 0, 0, 0)
         assert _counts(rst) == rr.noop_stats()[1]
@@ -380,7 +317,7 @@ def test_errors_and_noops(tiny):
         plain, none = ix.retention_count(0, 0)
         assert none is None and plain["launches"] == 0 and _counts(plain) == rr.noop_stats()[1]
         assert ix.stats() == before and ix.check_url_ids()[0] == 0
-        assert _hits(ix, qs) == hits
+        assert iu.hits(ix, qs) == hits
     finally:
         ix.close()
 
@@ -392,49 +329,26 @@ def test_two_shards(tiny, three_ways):
     base, lists, qs, median, cap = tiny
     (min_day, _), (whole, est, ers) = three_ways["age"]
     world = 2
-    rank_of = lambda l: np.array([ur.url_key(bytes(r[:12]))[0] >> 5 for r in l])  # Distribution.verticalDHTPosition, world 2
-    parts = [{t: l[rank_of(l) == r] for t, l in lists.items()} for r in range(world)]
-    parts = [{t: l for t, l in p.items() if len(l)} for p in parts]
-    uid = b"YRWI-LOOPBACK\0" + os.urandom(114)
-    ixs, out, errs = [None] * world, [None] * world, []
+    parts = iu.split_by_rank(lists, world)
 
-    def opener(r):
-        try:
-            ixs[r] = RWIIndex(0, shard=(r, world, uid))
-            for h, rr_ in parts[r].items():
-                ixs[r].add(h, rr_)
-        except Exception as e:  # pragma: no cover - reported below
-            errs.append(repr(e))
+    def fn(r, ix):
+        before = ix.stats()
+        for call in (ix.retain, ix.retention_count):
+            with pytest.raises(YrwiError) as e:
+                call(min_day, cap)
+            assert e.value.rc == -8
+        assert ix.stats() == before
+        iu.same_lists(ix, parts[r], list(parts[r])[:20])
+        dry, h = ix.retention_count(min_day, 0, hist=True)
+        st, rst = ix.retain(min_day, 0)
+        assert _counts(dry) == _counts(rst) and st["removed"] == rst["removed_age"]
+        assert ix.check_url_ids()[0] == 0
+        return st, rst, h, {t: ix.get_list(t) for t in lists}
 
-    def runner(r):
-        try:
-            before = ixs[r].stats()
-            for call in (ixs[r].retain, ixs[r].retention_count):
-                with pytest.raises(YrwiError) as e:
-                    call(min_day, cap)
-                assert e.value.rc == -8
-            assert ixs[r].stats() == before
-            _same_lists(ixs[r], parts[r], list(parts[r])[:20])
-            dry, h = ixs[r].retention_count(min_day, 0, hist=True)
-            st, rst = ixs[r].retain(min_day, 0)
-            assert _counts(dry) == _counts(rst) and st["removed"] == rst["removed_age"]
-            assert ixs[r].check_url_ids()[0] == 0
-            out[r] = (st, rst, h, {t: ixs[r].get_list(t) for t in lists})
-        except Exception as e:  # pragma: no cover
-            errs.append(repr(e))
-
-    for fn in (opener, runner):
-        ths = [threading.Thread(target=fn, args=(r,)) for r in range(world)]
-        for t in ths:
-            t.start()
-        for t in ths:
-            t.join(timeout=300)
-        assert not errs, errs
-    for ix in ixs:
-        ix.close()
+    out = iu.run_parts(parts, world, fn)
     assert out[0][0]["removed"] + out[1][0]["removed"] == est["removed"]
     assert out[0][0]["removed"] > 0 and out[1][0]["removed"] > 0
     assert ((out[0][2] + out[1][2]) == rr.day_hist(lists)).all()
     for t in lists:
         got = np.concatenate([out[0][3][t], out[1][3][t]])
-        assert got.tobytes() == whole.get(t, np.zeros((0, 40), np.uint8)).tobytes(), t
+        assert got.tobytes() == whole.get(t, iu.EMPTY).tobytes(), t

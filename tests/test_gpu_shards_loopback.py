@@ -9,61 +9,29 @@ flag-count all-reduce, the cross-shard top-k merge and the doubledom pull -- onl
 the transport is a device-to-device copy instead of RCCL.  Results must be
 bit-exact against the single-container oracle."""
 
-import os
-import threading
-
 import numpy as np
 import pytest
 
 import java_literal as jl
 import oracle as orc
-from yacy_search_server_amd import Query, QueryFilter, RankingProfile, RWIIndex, synth
+from index_util import run_parts
+from yacy_search_server_amd import Query, QueryFilter, RankingProfile, synth
 
 pytestmark = pytest.mark.gpu
 
 NOW = 20741 * 86400000 + 31337
 
 
-def _loop_id():
-    return b"YRWI-LOOPBACK\0" + os.urandom(114)
-
-
 def _run_shards(full, world, make_batch):
     """Open `world` shards of `full` on GPU 0, run make_batch(part) on each from its
     own thread; returns per-rank (batch, results)."""
-    uid = _loop_id()
-    parts = [synth.build_index(full.shard(r, world)) for r in range(world)]
-    ixs = [None] * world
-    out = [None] * world
-    errs = []
+    shards = [synth.build_index(full.shard(r, world)) for r in range(world)]
 
-    def opener(r):
-        try:
-            ixs[r] = RWIIndex(0, shard=(r, world, uid))
-            p = parts[r]
-            for t in range(full.n_terms):
-                if p.sizes[t]:
-                    ixs[r].add(p.hashes[t], p.list_rows(t))
-        except Exception as e:  # pragma: no cover - reported below
-            errs.append(repr(e))
+    def fn(r, ix):
+        batch = make_batch(shards[r])
+        return batch, ix.search_batch(batch)
 
-    def runner(r):
-        try:
-            batch = make_batch(parts[r])
-            out[r] = (batch, ixs[r].search_batch(batch))
-        except Exception as e:  # pragma: no cover
-            errs.append(repr(e))
-
-    for fn in (opener, runner):
-        ths = [threading.Thread(target=fn, args=(r,)) for r in range(world)]
-        for t in ths:
-            t.start()
-        for t in ths:
-            t.join(timeout=300)
-        assert not errs, errs
-    for ix in ixs:
-        ix.close()
-    return out
+    return run_parts([p.as_dict() for p in shards], world, fn)
 
 
 @pytest.mark.parametrize("world", [2, 4])
@@ -111,40 +79,6 @@ def test_loopback_shards_filters_and_doubledom():
             assert q.filter.flagcount == lf.flagcount, (r, kw, k)
 
 
-def _run_parts(parts, world, fn):
-    """parts: per-rank {term hash: rows}; fn(rank, RWIIndex) runs on every rank's own
-    thread (the same call sequence on every rank); returns the per-rank results."""
-    uid = _loop_id()
-    ixs = [None] * world
-    out = [None] * world
-    errs = []
-
-    def opener(r):
-        try:
-            ixs[r] = RWIIndex(0, shard=(r, world, uid))
-            for h, rows in parts[r].items():
-                ixs[r].add(h, rows)
-        except Exception as e:  # pragma: no cover - reported below
-            errs.append(repr(e))
-
-    def runner(r):
-        try:
-            out[r] = fn(r, ixs[r])
-        except Exception as e:  # pragma: no cover
-            errs.append(repr(e))
-
-    for f in (opener, runner):
-        ths = [threading.Thread(target=f, args=(r,)) for r in range(world)]
-        for t in ths:
-            t.start()
-        for t in ths:
-            t.join(timeout=300)
-        assert not errs, errs
-    for ix in ixs:
-        ix.close()
-    return out
-
-
 def _flip_band_queries(full, whole, parts, nq, seed):
     """Queries whose result a shard-local plan would get wrong (the J2/J3 decisions
     flip on local sizes), found with the oracle, plus a few ordinary ones."""
@@ -179,7 +113,7 @@ def test_loopback_flip_band_global_planning(world):
         hits = ix.search_batch([Query(ih, eh, now_ms=NOW, k=100) for ih, eh in cases])
         return rows, hits
 
-    res = _run_parts(parts, world, fn)
+    res = run_parts(parts, world, fn)
     for qi, (ih, eh) in enumerate(cases):
         ref = orc.term_search(whole, ih, eh, 2147483647, NOW)
         got = np.concatenate([res[r][0][qi].reshape(-1, 40) for r in range(world)])
@@ -210,7 +144,7 @@ def test_loopback_exclude_term_absent_from_a_shard():
     def fn(r, ix):
         return ix.search_batch([Query(i, e, now_ms=NOW, k=100) for i, e in cases])
 
-    res = _run_parts(parts, world, fn)
+    res = run_parts(parts, world, fn)
     for qi, (i, e) in enumerate(cases):
         exp = orc.search(whole, i, e, now_ms=NOW, k=100)
         for r in range(world):
@@ -239,7 +173,7 @@ def test_loopback_async_batches_in_flight(world):
         return [p.result() for p in pend]
 
     parts = [synth.build_index(full.shard(r, world)).as_dict() for r in range(world)]
-    res = _run_parts(parts, world, fn)
+    res = run_parts(parts, world, fn)
     for i, qs in enumerate(sets):
         exp = [orc.search(whole, [H[t] for t in inc], [H[t] for t in exc],
                           profile=(orc.profile_from(prof(i, j)) if prof(i, j) else None), now_ms=NOW, k=100)
@@ -280,7 +214,7 @@ def test_loopback_many_batches_in_flight(world, hostx, monkeypatch):
         return [p.result() for p in pend]
 
     parts = [synth.build_index(full.shard(r, world)).as_dict() for r in range(world)]
-    res = _run_parts(parts, world, fn)
+    res = run_parts(parts, world, fn)
     for i, qs in enumerate(sets):
         exp = [orc.search(whole, [H[t] for t in inc], [H[t] for t in exc],
                           profile=(orc.profile_from(prof(i)) if prof(i) else None), now_ms=NOW, k=50)
@@ -318,7 +252,7 @@ def test_loopback_count_first_four_terms(world, monkeypatch):
         return ix.search_batch([Query([H[t] for t in inc], [H[t] for t in exc], now_ms=NOW, k=100,
                                       profile=(c5 if i % 2 else None)) for i, (inc, exc) in enumerate(cases)])
 
-    res = _run_parts(parts, world, fn)
+    res = run_parts(parts, world, fn)
     for i, (inc, exc) in enumerate(cases):
         exp = orc.search(whole, [H[t] for t in inc], [H[t] for t in exc],
                          profile=(orc.profile_from(c5) if i % 2 else None), now_ms=NOW, k=100)

@@ -11,13 +11,13 @@ give the same bytes; the number of shared queries is counted here from the queri
 k_topq paths); `tiny`: its largest pairs join to 149 and 65 rows (n > k and n <= k, one chunk)."""
 
 import os
-import threading
 
 import numpy as np
 import pytest
 
 import java_literal as jl
 import oracle as orc
+from index_util import run_parts
 from yacy_search_server_amd import Query, QueryFilter, RankingProfile, RWIIndex, synth
 from yacy_search_server_amd._lib import CStats
 
@@ -290,39 +290,14 @@ def test_sharded_loopback_does_not_share():
     whole_idx = synth.build_index(full)
     whole = whole_idx.as_dict()
     lit = {h: [bytes(x) for x in rows] for h, rows in whole.items()}
-    uid = b"YRWI-LOOPBACK\0" + os.urandom(114)
-    parts = [synth.build_index(full.shard(r, world)) for r in range(world)]
-    ixs, out, errs = [None] * world, [None] * world, []
+    shards = [synth.build_index(full.shard(r, world)) for r in range(world)]
 
-    def opener(r):
-        try:
-            ixs[r] = RWIIndex(0, shard=(r, world, uid))
-            for t in range(full.n_terms):
-                if parts[r].sizes[t]:
-                    ixs[r].add(parts[r].hashes[t], parts[r].list_rows(t))
-        except Exception as e:  # pragma: no cover - reported below
-            errs.append(repr(e))
+    def fn(r, ix):
+        batch = _make_batch(whole_idx)  # (term hashes and sizes of the whole index: the same batch on every rank)
+        st = CStats()
+        return batch, ix.search_batch(batch, stats=st), st
 
-    def runner(r):
-        try:
-            batch = _make_batch(whole_idx)  # (term hashes and sizes of the whole index: the same batch on every rank)
-            st = CStats()
-            out[r] = (batch, ixs[r].search_batch(batch, stats=st), st)
-        except Exception as e:  # pragma: no cover
-            errs.append(repr(e))
-
-    try:
-        for fn in (opener, runner):
-            ths = [threading.Thread(target=fn, args=(r,)) for r in range(world)]
-            for t in ths:
-                t.start()
-            for t in ths:
-                t.join(timeout=300)
-            assert not errs, errs
-    finally:
-        for ix in ixs:
-            if ix is not None:
-                ix.close()
+    out = run_parts([p.as_dict() for p in shards], world, fn)
     for r, (batch, got, st) in enumerate(out):
         assert st.queries_shared == 0 and st.postings_shared == 0 and st.joined_shared == 0
         for qi, (q, g) in enumerate(zip(batch, got)):

@@ -49,9 +49,12 @@ import pytest
 import abstracts as ab
 import event_local_cases as C
 import heap
+import index_util as iu
 import java_literal as jl
 import oracle as orc
+import query_util as qu
 import split_keys as sk
+from abstract_cases import oracle_plan
 from yacy_search_server_amd import Query, QueryFilter, RankingProfile, RWIIndex
 from yacy_search_server_amd._lib import YrwiError
 
@@ -66,13 +69,6 @@ A, B, CC, D = sk.TERMS
 E = sk.T257
 
 
-def _open(lists):
-    ix = RWIIndex(0)
-    for h, r in lists.items():
-        ix.add(h, r)
-    return ix
-
-
 def _hashes(r):
     return [bytes(x) for x in r[:, :12]]
 
@@ -83,12 +79,11 @@ def _profiles():
 
 def _check_hits(ix, lists, qs, k, ctx, **kw):
     """search_batch of the queries under the default and the authority profile against orc.search"""
-    from test_gpu_adversarial import _gpu_raw, _orc_raw, _same_hits
     for name, rp, lp in _profiles():
         op = orc.profile_from(lp if lp is not None else jl.RankingProfile())
-        got = _gpu_raw(ix, [Query(inc, exc, k=k, profile=rp, now_ms=NOW, **kw) for inc, exc in qs])
+        got = qu.gpu_raw(ix, [Query(inc, exc, k=k, profile=rp, now_ms=NOW, **kw) for inc, exc in qs])
         for qi, ((inc, exc), g) in enumerate(zip(qs, got)):
-            _same_hits(g, _orc_raw(lists, inc, exc, op, "en", NOW, k), (ctx, name, qi))
+            qu.same_hits(g, qu.orc_raw(lists, inc, exc, op, "en", NOW, k), (ctx, name, qi))
     return got
 
 
@@ -100,7 +95,7 @@ def shared():
     for h, r in d.items():
         sk.check_list(r, h)
     assert len(d[A]) > 1024 and len(d[E]) == 257 and max(len(r) for r in d.values()) <= 8000
-    ix = _open(d)
+    ix = iu.open_index(d)
     ix.build_url_ids()
     yield ix, d
     ix.close()
@@ -155,7 +150,7 @@ def test_dictionary_full_build(shared, monkeypatch):
     assert n > len(sk.universe())  # the exclusion list names siblings that no other list has
     assert ix.check_url_ids() == (0, n)
     monkeypatch.setenv("YRWI_DICT_FULL", "1")
-    fresh = _open(d)
+    fresh = iu.open_index(d)
     try:
         assert fresh.check_url_ids() == (0, n)
         assert fresh.index_info()["incremental_updates"] == 0
@@ -175,7 +170,7 @@ def test_dictionary_incremental(monkeypatch):
     assert {sk.blind_key(h) for h in _hashes(sibl)} <= {sk.blind_key(h) for h in present}
     assert len(present) + len(sibl) == len(uni)
     qs = DICT_QS[:4] + [([A, S], []), ([S], []), ([A], [S]), ([K, B], []), ([A, K], [S]), ([S, K], [])]
-    ix = _open(base)
+    ix = iu.open_index(base)
     try:
         _check_hits(ix, base, DICT_QS[:4], 100, "first query")  # the full build
         assert ix.check_url_ids() == (0, len(present))
@@ -196,7 +191,7 @@ def test_dictionary_incremental(monkeypatch):
         assert np.array_equal(ix.term_search([A, S], [], INF, NOW), np.zeros((0, 40), np.uint8))
         assert np.array_equal(ix.term_search([A], [S], INF, NOW), base[A])
         monkeypatch.setenv("YRWI_DICT_FULL", "1")
-        fresh = _open(lists)
+        fresh = iu.open_index(lists)
         try:
             assert fresh.check_url_ids() == (0, len(uni))
             assert fresh.index_info()["incremental_updates"] == 0
@@ -220,7 +215,7 @@ def plain():
     d = sk.corpus()
     with pytest.MonkeyPatch.context() as mp:
         mp.setenv("YRWI_BM_DIV", "0")
-        ix = _open(d)
+        ix = iu.open_index(d)
         ix.build_url_ids()
     yield ix, d
     ix.close()
@@ -235,7 +230,6 @@ def test_joins_and_rank(shared, plain, index, algo, chain, monkeypatch):
     combinations of YRWI_PROBE_RATIO and YRWI_NO_CHAIN.  On the index without bitmaps these are the
     id probe and the merge tiles; on the shared index lists A and B (more than 4,096 urls) have
     bitmaps, and YRWI_PROBE_RATIO = 1 there is the bitmap probe."""
-    from test_gpu_adversarial import _gpu_raw
     from yacy_search_server_amd._lib import CStats
     monkeypatch.setenv("YRWI_PROBE_RATIO", "1" if algo == "probe" else "1000000000")
     monkeypatch.setenv("YRWI_NO_CHAIN", "1" if chain == "stepwise" else "0")
@@ -251,7 +245,7 @@ def test_joins_and_rank(shared, plain, index, algo, chain, monkeypatch):
     _check_hits(ix, d, JOIN_QS, 3000, (index, algo, chain))
     # the library's own counters: the setting took the path it names
     st = CStats()
-    _gpu_raw(ix, [Query(inc, exc, k=3000, now_ms=NOW) for inc, exc in JOIN_QS], stats=st)
+    qu.gpu_raw(ix, [Query(inc, exc, k=3000, now_ms=NOW) for inc, exc in JOIN_QS], stats=st)
     assert (st.n_chain_launches == 0) == (chain == "stepwise"), st.n_chain_launches
     # (probe tiles: a job whose larger side has a bitmap, or is more than YRWI_PROBE_RATIO times the smaller)
     assert (st.n_probe_dispatches == 0) == (index == "plain" and algo == "merge"), st.n_probe_dispatches
@@ -259,12 +253,11 @@ def test_joins_and_rank(shared, plain, index, algo, chain, monkeypatch):
 
 # ------------------------------------------------------------------ d
 def test_selection_and_doublecheck(shared):
-    from test_gpu_parity import _restrict
     ix, d = shared
     uni = sk.universe()
     sel, left, ghosts = sk.selection(uni, sk.SEED + 3)
     assert ghosts and not set(ghosts) & set(uni)
-    rd = _restrict(d, sel)
+    rd = qu.restrict(d, sel)
     qs = [([A], []), ([A, B], []), ([A, B, CC], [D]), ([B, E], []), ([A], [D]), ([CC, D], [])]
     for qi, (inc, exc) in enumerate(qs):
         exp = orc.term_search(rd, inc, exc, INF, NOW)
@@ -272,9 +265,8 @@ def test_selection_and_doublecheck(shared):
         assert got.shape == exp.shape and np.array_equal(got, exp), qi
         assert len(got) > 20 and not set(_hashes(got)) & set(left)  # siblings outside the selection are absent
     got = _check_hits(ix, rd, qs, 3000, "selection", urlselection=sel)
-    from test_gpu_adversarial import _decode
     for g in got:
-        assert len(g) and not {h for h, _, _ in _decode(g)} & (set(left) | set(ghosts))
+        assert len(g) and not {h for h, _, _ in qu.decode(g)} & (set(left) | set(ghosts))
     # the doublecheck set of a filter, built the same way
     dc, left2, ghosts2 = sk.selection(uni, sk.SEED + 4)
     lit = {h: [bytes(x) for x in d[h]] for h in (B, CC, D)}
@@ -293,13 +285,12 @@ def test_selection_and_doublecheck(shared):
 def test_hit_rows_doubledom(shared):
     """search(rows=True) under the doubledom pull order: the hits are looked up by key among the
     joined rows (k_hit_rows, HR_HITS); every hit's row is its own url's, never a sibling's"""
-    from test_gpu_hit_rows import _row_map
     ix, d = shared
     lit = {h: [bytes(x) for x in d[h]] for h in (B, CC, D)}
     for inc in ([CC], [B, D]):
         joined = orc.term_search(d, inc, [], INF, NOW)
         assert sk.sibling_bytes_differ(joined) and sk.equal_khi_fraction(joined) > 0.25
-        m = _row_map(joined)
+        m = qu.row_map(joined)
         full = jl.search(lit, inc, [], jl.RankingProfile(), "en", now_ms=NOW, k=3000,
                          filt=jl.QueryFilter(skip_double_dom=True))
         for k in (100, 3000):
@@ -312,17 +303,16 @@ def test_hit_rows_doubledom(shared):
 
 # ------------------------------------------------------------------ f
 def test_event_arrivals():
-    from test_events import NOW as ENOW, _check_event
     arrivals, never, pairs = sk.event_input()
     total = sum(len(r) for r, _ in arrivals)
     ix = RWIIndex(0)
     try:
-        _check_event(ix, arrivals, k=3000)
-        _check_event(ix, arrivals, {"coeff_authority": 14, "coeff_worddistance": 15}, k=3000)
+        C.check_event(ix, arrivals, k=3000)
+        C.check_event(ix, arrivals, {"coeff_authority": 14, "coeff_worddistance": 15}, k=3000)
         # where every url was admitted: the literal oracle's doublecheck set, arrival by arrival
-        ref = jl.SearchEventRWI(jl.RankingProfile(), "en", ENOW)
+        ref = jl.SearchEventRWI(jl.RankingProfile(), "en", C.NOW)
         admitted = {}
-        with ix.event(None, "en", ENOW, k=3000, max_postings=total + 16) as ev:
+        with ix.event(None, "en", C.NOW, k=3000, max_postings=total + 16) as ev:
             for j, (rows, local) in enumerate(arrivals, 1):
                 before = set(ref.filt.urlhashes)
                 ref.add_rwis(C.rows_list(rows), local)
@@ -421,13 +411,12 @@ def test_index_abstracts(shared):
 
 
 def test_secondary_search():
-    from test_abstracts import _oracle_plan
     words, base, abstracts, peers = sk.abstract_input()
     ix = RWIIndex(0)
     try:
         for mypeer, checked in ((peers[0], ()), (b"notapeer____", peers[1:3])):
             join, wl, plan = ix.secondary_search(abstracts, len(words), mypeer, checked)
-            ejoin, eplan = _oracle_plan(abstracts, words, mypeer, checked)
+            ejoin, eplan = oracle_plan(abstracts, words, mypeer, checked)
             assert wl == words
             assert join == [(u, next(iter(ejoin[u]))) for u in sorted(ejoin)]
             assert plan == eplan and len(plan) >= 5

@@ -8,14 +8,14 @@ tests/test_term_batch_cases_ref.py asserts on the oracle."""
 
 import ctypes
 import os
-import threading
 
 import numpy as np
 import pytest
 
 import event_local_cases as E
 import term_batch_cases as C
-from yacy_search_server_amd import Query, RWIIndex
+from index_util import open_index, run_parts
+from yacy_search_server_amd import Query
 from yacy_search_server_amd._lib import YrwiError, lib
 
 pytestmark = pytest.mark.gpu
@@ -24,24 +24,16 @@ NOW, INF = C.NOW, C.INF
 E_ARG, E_HASH, E_UNSUPPORTED = -1, -2, -8
 
 
-def _open(d):
-    ix = RWIIndex(0)
-    for h, rows in d.items():
-        ix.add(h, rows)
-    ix.build_url_ids()
-    return ix
-
-
 @pytest.fixture(scope="module")
 def ix():
-    x = _open(C.index_dict())
+    x = open_index(C.index_dict(), url_ids=True)
     yield x
     x.close()
 
 
 @pytest.fixture(scope="module")
 def tiny():
-    x = _open(E.corpus("tiny")[2])
+    x = open_index(E.corpus("tiny")[2], url_ids=True)
     yield x
     x.close()
 
@@ -232,7 +224,8 @@ def test_shape_of_the_call(ix):
         for kind in kinds:
             _shape(ix, kind, 64, pinned)
     assert lib().yrwi_settle_scratch(ix._h) == 0
-    tenth = _open({h: rows[:max(1, len(rows) // 10)] for h, rows in E.corpus("dense")[2].items()})
+    tenth = open_index({h: rows[:max(1, len(rows) // 10)] for h, rows in E.corpus("dense")[2].items()},
+                       url_ids=True)
     try:
         for pinned in (False, True):
             for kind in kinds:
@@ -276,28 +269,14 @@ def test_errors(ix):
 
 
 def test_sharded_context_is_refused():
-    uid = b"YRWI-LOOPBACK\0" + os.urandom(114)
-    ixs, errs = [None, None], []
-
-    def opener(r):
-        try:
-            ixs[r] = RWIIndex(0, shard=(r, 2, uid))
-        except Exception as e:  # pragma: no cover - reported below
-            errs.append(repr(e))
-
-    ths = [threading.Thread(target=opener, args=(r,)) for r in range(2)]
-    for t in ths:
-        t.start()
-    for t in ths:
-        t.join(timeout=120)
-    assert not errs and all(ixs), errs
-    try:
+    def fn(r, x):
+        if r:
+            return
         with pytest.raises(YrwiError) as e:
-            ixs[0].term_search_batch([Query([C.ABSENT], now_ms=NOW)])
+            x.term_search_batch([Query([C.ABSENT], now_ms=NOW)])
         assert e.value.rc == E_UNSUPPORTED
-    finally:
-        for x in ixs:
-            x.close()
+
+    run_parts([{}, {}], 2, fn, timeout=120)
 
 
 # ------------------------------------------------------------------ 11

@@ -4,41 +4,15 @@ url dictionary is consistent, a 40-query batch (default and authority profiles a
 with excludes) equals the oracle on the reference's lists, and equals a fresh index built in
 full from those lists."""
 
-import os
-import threading
-
 import numpy as np
 import pytest
 
-import oracle as orc
+import index_util as iu
 import update_ref as ur
-from yacy_search_server_amd import Query, RankingProfile, RWIIndex, synth
+from yacy_search_server_amd import synth
 from yacy_search_server_amd._lib import YrwiError
 
 pytestmark = pytest.mark.gpu
-
-NOW = 20741 * 86400000 + 4242
-C5 = RankingProfile("", "date=15,domlength=15,authority=13,tf=10")
-B64 = ur._B64
-STAT_KEYS = ("terms", "new_terms", "emptied_terms", "added", "replaced", "dropped", "removed")
-
-
-def _enc(i, width):
-    out = bytearray()
-    for _ in range(width):
-        out.append(B64[i & 63])
-        i >>= 6
-    return bytes(reversed(out))
-
-
-def _url(i):
-    """url hashes the synthetic index does not have (the fixture checks), ascending in i"""
-    return b"__" + _enc(i, 10)
-
-
-def _term(i):
-    return b"-t" + _enc(i, 10)
-
 
 @pytest.fixture(scope="module")
 def tiny():
@@ -46,100 +20,29 @@ def tiny():
     idx = synth.build_index(cfg)
     lists = idx.as_dict()
     have = {bytes(r[:12]) for r in idx.rows}
-    assert not any(_url(i) in have for i in range(1100)) and not any(u in have for u in _universe())
+    assert not any(iu.url(i) in have for i in range(1100)) and not any(u in have for u in _universe())
     qs = [([idx.hashes[t] for t in inc], [idx.hashes[t] for t in exc]) for inc, exc in synth.queries(cfg, 40, 2, 3, 1)]
     return cfg, idx, lists, qs
-
-
-def _rows(idx, urls, lm=None, start=0):
-    """hand-made rows: rows of the synthetic index as templates, the url hash (and lastModified) set"""
-    r = idx.rows[(start + 13 * np.arange(len(urls))) % len(idx.rows)].copy()
-    for i, u in enumerate(urls):
-        r[i, :12] = np.frombuffer(u, dtype=np.uint8)
-    if lm is not None:
-        lm = np.broadcast_to(np.asarray(lm), (len(urls),))
-        r[:, 12], r[:, 13] = lm >> 8, lm & 255
-    return r
-
-
-def _open(lists):
-    ix = RWIIndex(0)
-    for h, r in lists.items():
-        ix.add(h, r)
-    return ix
-
-
-def _batch(qs):
-    return [Query(inc, exc, now_ms=NOW, k=50, profile=(C5 if i % 2 else None)) for i, (inc, exc) in enumerate(qs)]
-
-
-def _hits(ix, qs):
-    return [[(h.urlhash, h.score, h.tiebreak) for h in r] for r in ix.search_batch(_batch(qs))]
-
-
-def _oracle(lists, qs):
-    out = []
-    for qi, (inc, exc) in enumerate(qs):
-        d = {h: lists[h] for h in inc + exc if h in lists}
-        out.append(orc.search(d, inc, exc, profile=(orc.profile_from(C5) if qi % 2 else None), now_ms=NOW, k=50))
-    return out
-
-
-def _verify(ix, lists, touched, qs, monkeypatch):
-    """the four checks of a step"""
-    for t in touched:
-        exp = lists.get(t, np.zeros((0, 40), np.uint8))
-        assert ix.get_size(t) == len(exp), t
-        assert ix.get_list(t).tobytes() == exp.tobytes(), t
-    assert ix.check_url_ids()[0] == 0
-    nterms, npost, _ = ix.stats()
-    assert (nterms, npost) == (len(lists), sum(len(r) for r in lists.values()))
-    got = _hits(ix, qs)
-    assert got == _oracle(lists, qs)
-    monkeypatch.setenv("YRWI_DICT_FULL", "1")
-    fresh = _open(lists)
-    try:
-        assert fresh.check_url_ids()[0] == 0
-        assert got == _hits(fresh, qs)
-    finally:
-        fresh.close()
-        monkeypatch.delenv("YRWI_DICT_FULL")
-
-
-def _add(ix, lists, terms, rows, policy="replace"):
-    """add on the device and on the reference; the stats must agree"""
-    st = ix.add_postings(terms, rows, policy)
-    new, exp = ur.apply_add(lists, terms, rows, policy)
-    assert {k: st[k] for k in STAT_KEYS} == exp, (st, exp)
-    assert st["added"] + st["replaced"] + st["dropped"] == len(rows)
-    return new, st
-
-
-def _remove(ix, lists, urls, terms=None):
-    st = ix.remove_postings(urls, terms)
-    new, exp = ur.apply_remove(lists, urls, terms)
-    assert {k: st[k] for k in STAT_KEYS} == exp, (st, exp)
-    return new, st
 
 
 # ------------------------------------------------------------------ 1: one document
 def test_one_document(tiny, monkeypatch):
     cfg, idx, lists, qs = tiny
     have = list(lists)
-    new_terms = [_term(i) for i in range(300 - len(have))]
+    new_terms = [iu.term(i) for i in range(300 - len(have))]
     assert len(new_terms) >= 50 and not set(new_terms) & set(lists)
     terms = have + new_terms
     qs = qs[:36] + [([new_terms[0]], []), ([new_terms[1], have[0]], []), ([have[0]], [new_terms[2]]),
                     ([new_terms[3], new_terms[4]], [have[1]])]
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
-        cur, st300 = _add(ix, lists, terms, _rows(idx, [_url(1)] * len(terms)))
+        cur, st300 = iu.checked_add(ix, lists, terms, iu.rows(idx, [iu.url(1)] * len(terms)))
         assert st300["added"] == len(terms) and st300["new_terms"] == len(new_terms)
-        _verify(ix, cur, terms, qs, monkeypatch)
-        cur, st8 = _add(ix, cur, terms[::40][:8], _rows(idx, [_url(2)] * 8, start=5))
+        iu.verify_step(ix, cur, terms, qs, monkeypatch)
+        cur, st8 = iu.checked_add(ix, cur, terms[::40][:8], iu.rows(idx, [iu.url(2)] * 8, start=5))
         assert st8["terms"] == 8
-        _verify(ix, cur, terms[::40][:8], qs, monkeypatch)
+        iu.verify_step(ix, cur, terms[::40][:8], qs, monkeypatch)
         # nothing is launched or waited for per term
         assert (st300["launches"], st300["syncs"]) == (st8["launches"], st8["syncs"]), (st300, st8)
     finally:
@@ -150,7 +53,7 @@ def test_one_document(tiny, monkeypatch):
 def _universe():
     """700 url hashes in groups of four that differ in the 12th character only (equal in their
     first 64 key bits: the khi / klo split), every second one left for the batches"""
-    u = [b"M" + _enc(g, 10) + bytes([c]) for g in range(2, 177) for c in b"AZz_"]
+    u = [b"M" + iu.enc(g, 10) + bytes([c]) for g in range(2, 177) for c in b"AZz_"]
     assert u == sorted(u, key=ur.url_key)
     return u
 
@@ -158,11 +61,11 @@ def _universe():
 def _hand_lists(idx):
     u = _universe()
     sizes = (255, 256, 257, 1)
-    terms = [_term(1000 + s) for s in sizes]
+    terms = [iu.term(1000 + s) for s in sizes]
     lists = {}
     for t, s in zip(terms, sizes):
         mine = u[1::2][:s] if s > 1 else [u[301]]
-        lists[t] = _rows(idx, mine, start=s)
+        lists[t] = iu.rows(idx, mine, start=s)
     return terms, lists, u
 
 
@@ -176,8 +79,8 @@ def test_boundary_sizes(tiny, monkeypatch, nb):
     lists = {**lists, **hand}
     qs = qs[:34] + [([terms[0], terms[1]], []), ([terms[1], terms[2]], [terms[0]]), ([terms[2]], [terms[3]]),
                     ([terms[3], terms[2]], []), ([terms[0], terms[1], terms[2]], []), ([terms[0]], [])]
-    before = [b"A" + _enc(i, 11) for i in range(3)]   # below every list key
-    after = [b"z" + _enc(i, 11) for i in range(3)]    # above every list key
+    before = [b"A" + iu.enc(i, 11) for i in range(3)]   # below every list key
+    after = [b"z" + iu.enc(i, 11) for i in range(3)]    # above every list key
     rng = np.random.default_rng(100 + nb)
     bt, bu = [], []
     for k, t in enumerate(terms):
@@ -197,13 +100,13 @@ def test_boundary_sizes(tiny, monkeypatch, nb):
         bu += urls
     order = rng.permutation(len(bt))  # the lists' batches interleaved
     bt, bu = [bt[int(i)] for i in order], [bu[int(i)] for i in order]
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
-        cur, st = _add(ix, lists, bt, _rows(idx, bu, start=3))
+        cur, st = iu.checked_add(ix, lists, bt, iu.rows(idx, bu, start=3))
         if nb == 0:
             assert st["added"] == 0 and st["replaced"] == len(bt)
-        _verify(ix, cur, terms, qs, monkeypatch)
+        iu.verify_step(ix, cur, terms, qs, monkeypatch)
     finally:
         ix.close()
 
@@ -226,15 +129,15 @@ def test_policies(tiny, monkeypatch):
     plan += [(t0, fresh[2 + i], 100 + i) for i in range(200)]
     plan += [(t0, own[3], 500), (t0, fresh[0], 9), (t0, own[6], 501), (t1, fresh[1], 2), (t0, own[5], 498)]
     bt = [p[0] for p in plan]
-    rows = _rows(idx, [p[1] for p in plan], lm=[p[2] for p in plan], start=11)
+    rows = iu.rows(idx, [p[1] for p in plan], lm=[p[2] for p in plan], start=11)
     qs = qs[:36] + [([t0], []), ([t0, t1], []), ([t1], [t0]), ([t0, terms[1]], [])]
     results = {}
     for policy in ur.POLICIES:
-        ix = _open(lists)
+        ix = iu.open_index(lists)
         try:
             ix.build_url_ids()
-            cur, st = _add(ix, lists, bt, rows, policy)
-            _verify(ix, cur, [t0, t1], qs, monkeypatch)
+            cur, st = iu.checked_add(ix, lists, bt, rows, policy)
+            iu.verify_step(ix, cur, [t0, t1], qs, monkeypatch)
             results[policy] = cur[t0].tobytes() + cur[t1].tobytes()
         finally:
             ix.close()
@@ -242,17 +145,9 @@ def test_policies(tiny, monkeypatch):
 
 
 # ------------------------------------------------------------------ 4: remove
-def _set_chunk(monkeypatch, chunk):
-    """rows compacted at a time (None: the default, one chunk on this corpus)"""
-    if chunk is None:
-        monkeypatch.delenv("YRWI_RM_CHUNK", raising=False)
-    else:
-        monkeypatch.setenv("YRWI_RM_CHUNK", str(chunk))
-
-
 def _state(ix, lists, qs, st):
     """what a removal leaves behind: every list, the url ids, the query hits, the counted stats"""
-    return ({t: ix.get_list(t).tobytes() for t in lists}, ix.check_url_ids(), _hits(ix, qs),
+    return ({t: ix.get_list(t).tobytes() for t in lists}, ix.check_url_ids(), iu.hits(ix, qs),
             {k: st[k] for k in ("terms", "emptied_terms", "removed")})
 
 
@@ -262,12 +157,12 @@ def _remove_steps(tiny, monkeypatch):
     by_size = sorted(lists, key=lambda h: len(lists[h]))
     small, mid, big = by_size[0], by_size[len(by_size) // 2], by_size[-1]
     # absent urls, duplicate urls, a duplicated term, an unknown term, a list emptied
-    urls = [bytes(r[:12]) for r in lists[small]] + [bytes(lists[mid][0, :12])] * 2 + [_url(5), _url(5)]
+    urls = [bytes(r[:12]) for r in lists[small]] + [bytes(lists[mid][0, :12])] * 2 + [iu.url(5), iu.url(5)]
     urls += [bytes(r[:12]) for r in lists[big][::5]]
     # a named list that holds none of the urls
     gone = set(urls)
     quiet = next(t for t in by_size[1:] if not gone & {bytes(r[:12]) for r in lists[t]})
-    named = [small, mid, mid, big, quiet, _term(77)]
+    named = [small, mid, mid, big, quiet, iu.term(77)]
     # on the reference alone: a list longer than 256 rows (a chunk of its own at YRWI_RM_CHUNK = 256)
     # loses some but not all rows, a list is emptied, a named list loses nothing
     ref, _ = ur.apply_remove(lists, urls, named)
@@ -275,13 +170,13 @@ def _remove_steps(tiny, monkeypatch):
     assert small not in ref
     assert ref[quiet] is lists[quiet] and quiet not in (small, mid, big)
     states = []
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
         n0 = ix.stats()[0]
-        cur, st = _remove(ix, lists, urls, named)
+        cur, st = iu.checked_remove(ix, lists, urls, named)
         assert st["emptied_terms"] >= 1 and ix.get_size(small) == 0 and ix.stats()[0] == n0 - st["emptied_terms"]
-        _verify(ix, cur, [small, mid, big, quiet], qs, monkeypatch)
+        iu.verify_step(ix, cur, [small, mid, big, quiet], qs, monkeypatch)
         states.append(_state(ix, lists, qs, st))
         # Segment.removeAllUrlReferences: about 50 urls that occur in many lists, over the whole index
         count = {}
@@ -290,12 +185,12 @@ def _remove_steps(tiny, monkeypatch):
                 count[bytes(x[:12])] = count.get(bytes(x[:12]), 0) + 1
         common = sorted(count, key=lambda k: (-count[k], k))[:50]
         assert count[common[-1]] >= 2
-        cur2, st = _remove(ix, cur, common, None)
+        cur2, st = iu.checked_remove(ix, cur, common, None)
         assert st["removed"] == sum(count[x] for x in common)
-        _verify(ix, cur2, list(cur), qs, monkeypatch)
+        iu.verify_step(ix, cur2, list(cur), qs, monkeypatch)
         states.append(_state(ix, lists, qs, st))
         # nothing to remove: nothing changes
-        _, st = _remove(ix, cur2, common, None)
+        _, st = iu.checked_remove(ix, cur2, common, None)
         assert st["removed"] == 0 and st["terms"] == 0
         states.append(_state(ix, lists, qs, st))
     finally:
@@ -312,7 +207,7 @@ def test_remove_at_chunk_sizes(tiny, monkeypatch):
     of 4096 rows (runs of whole lists): the same lists, url ids, hits and counts"""
     states = {}
     for chunk in (None, 256, 4096):
-        _set_chunk(monkeypatch, chunk)
+        iu.set_rm_chunk(monkeypatch, chunk)
         states[chunk] = _remove_steps(tiny, monkeypatch)
     assert states[256] == states[None]
     assert states[4096] == states[None]
@@ -327,11 +222,11 @@ def test_more_chunks_more_launches(tiny, monkeypatch):
     assert len(shrunk) >= 2 and sum(len(lists[t]) for t in shrunk) > 256  # more than one chunk of 256 rows
     st = {}
     for chunk in (None, 256):
-        _set_chunk(monkeypatch, chunk)
-        ix = _open(lists)
+        iu.set_rm_chunk(monkeypatch, chunk)
+        ix = iu.open_index(lists)
         try:
             got = ix.remove_postings(urls, None)
-            assert {k: got[k] for k in STAT_KEYS} == ref[1], (got, ref[1])
+            assert {k: got[k] for k in iu.STAT_KEYS} == ref[1], (got, ref[1])
             st[chunk] = got
         finally:
             ix.close()
@@ -342,7 +237,7 @@ def test_more_chunks_more_launches(tiny, monkeypatch):
 # ------------------------------------------------------------------ 5: small updates stay incremental
 def test_small_updates_stay_incremental(tiny, monkeypatch):
     cfg, idx, lists, qs = tiny
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()  # settled
         base = ix.index_info()
@@ -350,7 +245,7 @@ def test_small_updates_stay_incremental(tiny, monkeypatch):
         touched = by_size[:10]
         total = sum(len(r) for r in lists.values())
         assert 4 * sum(len(lists[t]) for t in touched) < total  # the precondition of an incremental update
-        cur, _ = _add(ix, lists, touched, _rows(idx, [_url(10 + i) for i in range(10)]))
+        cur, _ = iu.checked_add(ix, lists, touched, iu.rows(idx, [iu.url(10 + i) for i in range(10)]))
         assert ix.check_url_ids()[0] == 0
         info = ix.index_info()
         assert info["incremental_updates"] == base["incremental_updates"] + 1, info
@@ -359,13 +254,13 @@ def test_small_updates_stay_incremental(tiny, monkeypatch):
         big = by_size[-1]
         assert 4 * (len(lists[big]) + 20) < total
         for i in range(20):
-            cur, st = _add(ix, cur, [big], _rows(idx, [_url(100 + i)], start=i))
+            cur, st = iu.checked_add(ix, cur, [big], iu.rows(idx, [iu.url(100 + i)], start=i))
             assert st["added"] == 1
             ix.build_url_ids()
         info2 = ix.index_info()
         assert info2["full_rebuilds"] == base["full_rebuilds"], info2
         assert info2["incremental_updates"] == info["incremental_updates"] + 20, info2
-        _verify(ix, cur, touched + [big], qs, monkeypatch)
+        iu.verify_step(ix, cur, touched + [big], qs, monkeypatch)
     finally:
         ix.close()
 
@@ -377,16 +272,16 @@ def test_repack_reached(tiny, monkeypatch):
     a, b, c, d = sorted(lists, key=lambda h: -len(lists[h]))[:4]
     big, small = a, {h: lists[h] for h in (a, b, c, d)}  # a small live index: the re-written list dominates
     qs = [([a], []), ([a, b], []), ([a, b], [c]), ([c, d], []), ([a, d], [b]), ([b, c, a], [])]
-    ix = _open(small)
+    ix = iu.open_index(small)
     try:
         ix.build_url_ids()
         first = ix.index_info()
         cur = small
         for i in range(16):
-            cur, _ = _add(ix, cur, [big] * 3, _rows(idx, [_url(1000 + 3 * i + k) for k in range(3)], start=i))
+            cur, _ = iu.checked_add(ix, cur, [big] * 3, iu.rows(idx, [iu.url(1000 + 3 * i + k) for k in range(3)], start=i))
             ix.build_url_ids()
         assert ix.index_info()["repacks"] > first["repacks"], ix.index_info()
-        _verify(ix, cur, [big], qs, monkeypatch)
+        iu.verify_step(ix, cur, [big], qs, monkeypatch)
     finally:
         ix.close()
 
@@ -394,11 +289,11 @@ def test_repack_reached(tiny, monkeypatch):
 # ------------------------------------------------------------------ 7: errors are atomic
 def test_errors_are_atomic(tiny):
     cfg, idx, lists, qs = tiny
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
-        terms = list(lists)[:20] + [_term(5)]
-        good = _rows(idx, [_url(50 + i) for i in range(len(terms))])
+        terms = list(lists)[:20] + [iu.term(5)]
+        good = iu.rows(idx, [iu.url(50 + i) for i in range(len(terms))])
         before = ix.stats()
         bad_hash = good.copy()
         bad_hash[7, 4] = ord("!")
@@ -410,12 +305,12 @@ def test_errors_are_atomic(tiny):
             assert e.value.rc == code
             assert ix.stats() == before
             for t in terms:
-                assert ix.get_list(t).tobytes() == lists.get(t, np.zeros((0, 40), np.uint8)).tobytes()
+                assert ix.get_list(t).tobytes() == lists.get(t, iu.EMPTY).tobytes()
         with pytest.raises(YrwiError) as e:
             ix.add_postings([b"bad!term#ash"] + terms[1:], good)
         assert e.value.rc == -2 and ix.stats() == before
         assert ix.check_url_ids()[0] == 0
-        assert _hits(ix, qs[:10]) == _oracle(lists, qs[:10])
+        assert iu.hits(ix, qs[:10]) == iu.oracle_hits(lists, qs[:10])
     finally:
         ix.close()
 
@@ -423,20 +318,20 @@ def test_errors_are_atomic(tiny):
 # ------------------------------------------------------------------ 8: interleaving with batches in flight
 def test_interleaved_with_submitted_batches(tiny):
     cfg, idx, lists, qs = tiny
-    ix = _open(lists)
+    ix = iu.open_index(lists)
     try:
         ix.build_url_ids()
         # a url added to every term of the queries: their results change
         terms = sorted({h for inc, exc in qs for h in inc})
-        first = ix.submit(_batch(qs))
-        st = ix.add_postings(terms, _rows(idx, [_url(9)] * len(terms)))
-        cur, exp = ur.apply_add(lists, terms, _rows(idx, [_url(9)] * len(terms)), "replace")
+        first = ix.submit(iu.batch(qs))
+        st = ix.add_postings(terms, iu.rows(idx, [iu.url(9)] * len(terms)))
+        cur, exp = ur.apply_add(lists, terms, iu.rows(idx, [iu.url(9)] * len(terms)), "replace")
         assert st["added"] == exp["added"] == len(terms)
-        second = ix.submit(_batch(qs))
+        second = ix.submit(iu.batch(qs))
         r1 = [[(h.urlhash, h.score, h.tiebreak) for h in r] for r in first.result()]
         r2 = [[(h.urlhash, h.score, h.tiebreak) for h in r] for r in second.result()]
-        assert r1 == _oracle(lists, qs)
-        assert r2 == _oracle(cur, qs)
+        assert r1 == iu.oracle_hits(lists, qs)
+        assert r2 == iu.oracle_hits(cur, qs)
         assert r1 != r2
     finally:
         ix.close()
@@ -451,45 +346,24 @@ def test_sharded_loopback_updates(tiny):
     rank_of = lambda row: ur.url_key(bytes(row[:12]))[0] >> 5  # Distribution.verticalDHTPosition, world 2
     parts = [synth.build_index(cfg.shard(r, world)).as_dict() for r in range(world)]
     terms = sorted({h for inc, exc in qs for h in inc})[:30]
-    urls = [_url(3), b"A_" + _enc(3, 10), _url(4), b"B_" + _enc(4, 10)]  # both ranges
+    urls = [iu.url(3), b"A_" + iu.enc(3, 10), iu.url(4), b"B_" + iu.enc(4, 10)]  # both ranges
     bt = [t for t in terms for _ in urls]
-    rows = _rows(idx, urls * len(terms))
+    rows = iu.rows(idx, urls * len(terms))
     big = max(lists, key=lambda h: len(lists[h]))
     gone = [bytes(r[:12]) for r in lists[big][::4]]
     whole, _ = ur.apply_add(lists, bt, rows, "replace")
     whole, _ = ur.apply_remove(whole, gone, None)
-    uid = b"YRWI-LOOPBACK\0" + os.urandom(114)
-    ixs, out, errs = [None] * world, [None] * world, []
 
-    def opener(r):
-        try:
-            ixs[r] = RWIIndex(0, shard=(r, world, uid))
-            for h, rr in parts[r].items():
-                ixs[r].add(h, rr)
-        except Exception as e:  # pragma: no cover - reported below
-            errs.append(repr(e))
+    def fn(r, ix):
+        mine = [i for i in range(len(rows)) if rank_of(rows[i]) == r]
+        st = ix.add_postings([bt[i] for i in mine], rows[mine])
+        assert st["added"] == len(mine)
+        ix.remove_postings([u for u in gone if ur.url_key(u)[0] >> 5 == r], None)
+        assert ix.check_url_ids()[0] == 0
+        return iu.hits(ix, qs)
 
-    def runner(r):
-        try:
-            mine = [i for i in range(len(rows)) if rank_of(rows[i]) == r]
-            st = ixs[r].add_postings([bt[i] for i in mine], rows[mine])
-            assert st["added"] == len(mine)
-            ixs[r].remove_postings([u for u in gone if ur.url_key(u)[0] >> 5 == r], None)
-            assert ixs[r].check_url_ids()[0] == 0
-            out[r] = _hits(ixs[r], qs)
-        except Exception as e:  # pragma: no cover
-            errs.append(repr(e))
-
-    for fn in (opener, runner):
-        ths = [threading.Thread(target=fn, args=(r,)) for r in range(world)]
-        for t in ths:
-            t.start()
-        for t in ths:
-            t.join(timeout=300)
-        assert not errs, errs
-    for ix in ixs:
-        ix.close()
-    exp = _oracle(whole, qs)
-    assert exp != _oracle(lists, qs)
+    out = iu.run_parts(parts, world, fn)
+    exp = iu.oracle_hits(whole, qs)
+    assert exp != iu.oracle_hits(lists, qs)
     for r in range(world):
         assert out[r] == exp, r
