@@ -5,7 +5,8 @@ against hand-derived expectations of SearchEvent.java:736-806 (filters),
 :2459-2474 (testFlags) and :1297-1394 (pullOneRWI).
 GPU: libyrwi (filter predicates fused into k_score, k_doubledom) against the
 literal oracle on seeded corpora, mixed filtered / unfiltered batches.
-No reference test covers these paths (parity pinned by the restatement)."""
+No reference test covers these paths (parity pinned by the restatement); the directed inputs
+are in tests/filter_cases.py (tests/test_filter_cases_ref.py, tests/test_gpu_filters_directed.py)."""
 
 import numpy as np
 import pytest
