@@ -388,6 +388,69 @@ int yrwi_retention_count(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, 
                          int64_t* day_hist, yrwi_retention_stats* st);
 int yrwi_retain(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, int32_t min_day, int64_t max_refs,
                 yrwi_update_stats* st, yrwi_retention_stats* rst);
+/* References of urls: the read-only form of yrwi_remove_postings -- which postings of the selected lists
+ * carry one of the nurls url hashes, how many each url has, and the rows themselves with the term of their
+ * list (which words index this url; the rows to move, re-host, re-send or re-add).  UNVERIFIED against a
+ * reference line: the reference has no such method (Segment.removeAllUrlReferences re-loads and re-parses
+ * the document to learn its words); the call is defined through calls of this header instead.
+ *   Selection and url set are those of yrwi_remove_postings: nterms == 0 every list, otherwise the named
+ * lists; duplicate terms and urls count once, unknown terms and absent urls are ignored.  A reference is a
+ * row of a selected list whose url hash is in the set.  The call waits for the batches in flight and
+ * changes nothing in the context.
+ *   counts[i] (counts may be NULL) = references of urls12 + 12 i; a url given twice gets its full count
+ * twice, as in yrwi_count_hosts.  st->refs, st->lists_hit and st->lists_covered are st->removed, st->terms
+ * and st->emptied_terms of yrwi_remove_postings with the same arguments.
+ *   cap_refs > 0 fetches: reference r in `order` is written, rows40_out + 40 r = the row as stored, all 40
+ * bytes (what yrwi_get_list returns for it), terms12_out + 12 r = the term hash of its list.
+ * YRWI_REFS_BY_TERM: lists by ascending term hash (the order yrwi_dump_heap writes them in), within a list
+ * by ascending url hash; YRWI_REFS_BY_URL: by ascending url hash (72-bit key order), the references of one
+ * url by ascending term hash.  cap_refs == 0 only counts (the buffers may be NULL).  st->refs > cap_refs
+ * (cap_refs > 0): YRWI_E_ARG with counts and st filled and not a byte of the two buffers written, the rule
+ * of yrwi_term_search_batch.  nurls == 0 or nothing selected: a successful empty result.  YRWI_E_HASH (a url
+ * or term hash with a character outside the Base64 alphabet): nothing is written.  `order` outside the two
+ * values, cap_refs < 0, or cap_refs > 0 with a NULL buffer: YRWI_E_ARG.  YRWI_E_LIMIT: 2^31 urls or more,
+ * 2^31 references or more in YRWI_REFS_BY_URL, or YRWI_REFS_PROBE forced over 2^39 (list, url) pairs or more.
+ *   Two ways to find the references.  YRWI_REFS_STREAM: one pass over the 9 key bytes of every selected
+ * posting (grid and spans of the marking pass of yrwi_remove_hosts; no row is read), each key searched in
+ * the sorted url set, which is staged in LDS up to YRWI_REF_LDS_MAX urls (9 B each) and searched in global
+ * memory above.  YRWI_REFS_PROBE: one thread per (selected list, url of the set) searches the list for the
+ * url -- one document against every list is a search per list, not a pass over the index.  The call takes
+ * PROBE when lists * urls * ceil(log2(mean list length + 1)) search steps, each weighed as
+ * REF_PROBE_STEP_KEYS streamed keys (yrwi_update.hip, set at the measured crossover), cost no more than the
+ * selected postings; the environment's YRWI_REFS_PATH = stream | probe, read per call, forces a path;
+ * st->path says which ran.  The results of the two paths are the same bytes.
+ *   Delivery: a count pass leaves one hit count per tile of the path's domain (1024 postings, 256 pairs),
+ * one workgroup scans them with a 64-bit carry, and the pack pass finds its hits again in the tiles that
+ * have any and writes each at its tile's start plus its rank in the tile; it reads the total from device
+ * memory and stores nothing when it exceeds cap_refs, so the host does not wait in between.
+ * YRWI_REFS_BY_URL sorts the references alone (never the postings) stably by their slot in the url set
+ * on the device.  rows40_out from yrwi_host_alloc and 8-byte aligned is written by the kernel itself
+ * (st->direct = 1); any other buffer receives the rows from device scratch through the lane's pinned
+ * landing buffer.  Scratch grows with the tiles and with min(cap_refs, lists * urls, postings), never with
+ * the postings alone.  st->launches / st->syncs depend on the order, on count-only against fetch and on
+ * direct alone: 4 / 2 counting; fetching 8 / 3 by term and 10 / 3 by url, one launch fewer when direct.
+ * A steady sequence of calls makes no device-wide allocation after the first.  A sharded context reports
+ * what it holds: every rank gets the same call, no collective runs, a url lies in one rank's range, so the
+ * ranks' references are disjoint and their counts add up.  st may be NULL. */
+#define YRWI_REFS_BY_TERM 0   /* term ascending (the order yrwi_dump_heap writes lists in), then url hash ascending */
+#define YRWI_REFS_BY_URL  1   /* url hash ascending (72-bit key order), then term ascending */
+#define YRWI_REFS_STREAM  0   /* stats.path: one pass over the selected postings' keys */
+#define YRWI_REFS_PROBE   1   /* stats.path: one search per (selected list, url) */
+#define YRWI_REF_LDS_MAX 2048
+typedef struct yrwi_ref_stats {
+  int64_t lists, postings;    /* selected non-empty lists, rows in them */
+  int64_t urls, urls_found;   /* distinct urls given; of which with at least one reference */
+  int64_t refs;               /* references found == st->removed of yrwi_remove_postings with the same arguments */
+  int64_t lists_hit;          /* == st->terms of that call */
+  int64_t lists_covered;      /* lists all of whose rows are references == st->emptied_terms of that call */
+  int32_t path, direct;       /* path taken; 1: the kernel wrote the rows into the caller's buffer */
+  int32_t launches, syncs;
+  int64_t bytes_h2d, bytes_d2h;
+  int64_t t_find_ns, t_total_ns;
+} yrwi_ref_stats;
+int yrwi_url_references(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uint8_t* urls12, int64_t nurls,
+                        int32_t order, int64_t* counts, uint8_t* terms12_out, uint8_t* rows40_out, int64_t cap_refs,
+                        yrwi_ref_stats* st);
 /* Brings the url dictionary (url hash -> order-preserving 32-bit url id, the
  * join key in HBM) up to date now instead of at the next query.  The first
  * build sorts every key; later put_list / removal / load_heaps changes are

@@ -141,6 +141,54 @@ JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_countHosts(JNIEnv
   return res;
 }
 
+/* yrwi_url_references as long[16 + nurls]: yrwi_ref_stats (lists, postings, urls, urls_found, refs, lists_hit,
+ * lists_covered, path, direct, launches, syncs, bytes_h2d, bytes_d2h, t_find_ns, t_total_ns), the call's return
+ * code (0, or YRWI_E_ARG when refs > cap and nothing was fetched), then the references of every url.  With
+ * cap > 0 the references' terms go into terms12 (at least 12 * cap bytes) and their rows into rows40 (at least
+ * 40 * cap bytes), in `order`; cap == 0 only counts (the arrays may be null).  NULL when the call failed otherwise */
+JNIEXPORT jlongArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_urlReferences(JNIEnv* env, jclass c, jlong ctx,
+                                                                            jbyteArray terms, jint nterms,
+                                                                            jbyteArray urls, jint nurls, jint order,
+                                                                            jlong cap, jbyteArray terms12,
+                                                                            jbyteArray rows40) {
+  if (cap < 0 || (cap > 0 && (!terms12 || !rows40 || (jlong)(*env)->GetArrayLength(env, terms12) < 12 * cap ||
+                              (jlong)(*env)->GetArrayLength(env, rows40) < 40 * cap)))
+    return NULL;
+  uint8_t* t = copy_in(env, terms, (int64_t)nterms * 12);
+  if (!t) return NULL;
+  uint8_t* u = copy_in(env, urls, (int64_t)nurls * 12);
+  if (!u) {
+    free(t);
+    return NULL;
+  }
+  uint8_t* to = (uint8_t*)malloc((size_t)cap * 12 + 1);
+  uint8_t* ro = (uint8_t*)malloc((size_t)cap * 40 + 1);
+  jlong* v = (jlong*)calloc((size_t)nurls + 16, sizeof(jlong));
+  yrwi_ref_stats st;
+  int rc = to && ro && v ? yrwi_url_references((yrwi_ctx*)(intptr_t)ctx, t, nterms, u, nurls, order, (int64_t*)(v + 16),
+                                               cap ? to : NULL, cap ? ro : NULL, cap, &st)
+                         : YRWI_E_NOMEM;
+  free(t);
+  free(u);
+  jlongArray res = NULL;
+  if (rc == 0 || (rc == YRWI_E_ARG && cap > 0 && st.refs > cap)) {
+    const jlong s[16] = {st.lists, st.postings, st.urls,      st.urls_found, st.refs,      st.lists_hit,
+                         st.lists_covered, st.path, st.direct, st.launches,  st.syncs,     st.bytes_h2d,
+                         st.bytes_d2h,     st.t_find_ns,       st.t_total_ns, rc};
+    memcpy(v, s, sizeof(s));
+    if (rc == 0 && cap > 0 && st.refs > 0) {
+      (*env)->SetByteArrayRegion(env, terms12, 0, (jsize)(12 * st.refs), (const jbyte*)to);
+      (*env)->SetByteArrayRegion(env, rows40, 0, (jsize)(40 * st.refs), (const jbyte*)ro);
+    }
+    res = (*env)->NewLongArray(env, (jsize)(16 + nurls));
+    if (res) (*env)->SetLongArrayRegion(env, res, 0, (jsize)(16 + nurls), v);
+  }
+  free(to);
+  free(ro);
+  free(v);
+  return res;
+}
+
 /* yrwi_host_census as long[12 + nout]: nout, then yrwi_census_stats (lists, postings, hosts, hosts_passing,
  * table_slots, passes, lds_bypass, launches, syncs, t_count_ns, t_total_ns), then the nout counts; the hosts
  * (6 bytes each) go into hosts6 (at least 6 * cap bytes); NULL when the call failed */

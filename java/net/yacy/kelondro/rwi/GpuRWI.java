@@ -151,6 +151,66 @@ public final class GpuRWI implements AutoCloseable {
         return counts;
     }
 
+    /** Orders of urlReferences (YRWI_REFS_BY_*). */
+    public static final int REFS_BY_TERM = 0;  // ascending term hash, the references of one list by ascending url hash
+    public static final int REFS_BY_URL = 1;   // ascending url hash, the references of one url by ascending term hash
+
+    /** What urlReferences returns: counts[i] = the references of urls[i] (a url given twice gets its count
+     *  twice); with fetch, reference r is rows[r] (the 40-byte row as stored) in the list of terms[r], in the
+     *  order asked for; without, terms and rows are null.  stats = {lists, postings, urls, urlsFound, refs,
+     *  listsHit, listsCovered, path, direct, launches, syncs, bytesH2d, bytesD2h, tFindNs, tTotalNs}
+     *  (yrwi_ref_stats): refs, listsHit and listsCovered are removed, terms and emptiedTerms of
+     *  removePostings(terms, urls). */
+    public static final class UrlReferences {
+        public final long[] counts;
+        public final byte[][] terms;
+        public final byte[][] rows;
+        public final long[] stats;
+        UrlReferences(final long[] counts, final byte[][] terms, final byte[][] rows, final long[] stats) {
+            this.counts = counts;
+            this.terms = terms;
+            this.rows = rows;
+            this.stats = stats;
+        }
+    }
+
+    /** What removePostings(terms, urls) would remove, the index unchanged (yrwi_url_references): which
+     *  words index these urls, how many references each url has and, with fetch, the rows themselves (to
+     *  move, re-host, re-send or re-add them).  terms == null or empty: every list.  The references are
+     *  found on the device and only they cross to the host.  No reference method stands behind this:
+     *  Segment.removeAllUrlReferences re-loads and re-parses the document to learn its words.  A first
+     *  call counts, a second one fetches into arrays of that size.  Uncompiled like the rest of this
+     *  class (see the head of the file). */
+    public synchronized UrlReferences urlReferences(final byte[][] terms, final byte[][] urls, final int order,
+                                                    final boolean fetch) {
+        final int nterms = terms == null ? 0 : terms.length;
+        final byte[] t = nterms == 0 ? new byte[0] : flatten(terms);
+        final byte[] u = flatten(urls);
+        long[] r = urlReferences(this.ctx, t, nterms, u, urls.length, order, 0L, null, null);
+        if (r == null) throw new IllegalStateException("yrwi_url_references failed");
+        final long refs = r[4];
+        byte[][] outTerms = null;
+        byte[][] outRows = null;
+        if (fetch) {
+            if (40L * refs > Integer.MAX_VALUE) throw new IllegalArgumentException("more references than a byte[] holds: name fewer urls");
+            final int n = (int) refs;
+            final byte[] t12 = new byte[12 * n];
+            final byte[] r40 = new byte[40 * n];
+            if (n > 0) {
+                r = urlReferences(this.ctx, t, nterms, u, urls.length, order, refs, t12, r40);
+                if (r == null || r[15] != 0 || r[4] != refs) throw new IllegalStateException("yrwi_url_references failed");
+            }
+            outTerms = new byte[n][];
+            outRows = new byte[n][];
+            for (int i = 0; i < n; i++) {
+                outTerms[i] = java.util.Arrays.copyOfRange(t12, 12 * i, 12 * i + 12);
+                outRows[i] = java.util.Arrays.copyOfRange(r40, 40 * i, 40 * i + 40);
+            }
+        }
+        return new UrlReferences(java.util.Arrays.copyOfRange(r, 16, 16 + urls.length), outTerms, outRows,
+                                 java.util.Arrays.copyOfRange(r, 0, 15));
+    }
+
     /** Orders of hostCensus (YRWI_CENSUS_BY_*). */
     public static final int CENSUS_BY_HOST = 0;   // ascending host hash (Base64Order)
     public static final int CENSUS_BY_COUNT = 1;  // postings descending, equal counts by ascending host hash
@@ -634,6 +694,8 @@ public final class GpuRWI implements AutoCloseable {
     private static native long[] removePostings(long ctx, byte[] terms, int nterms, byte[] urls, int nurls);
     private static native long[] removeHosts(long ctx, byte[] terms, int nterms, byte[] hosts6, int nhosts);
     private static native long[] countHosts(long ctx, byte[] terms, int nterms, byte[] hosts6, int nhosts);
+    private static native long[] urlReferences(long ctx, byte[] terms, int nterms, byte[] urls, int nurls, int order,
+                                               long cap, byte[] terms12, byte[] rows40);
     // {nout, the 11 statistics, counts[0 .. nout)}; hosts6Out (6 * cap bytes) receives the hosts; null: failed
     private static native long[] hostCensus(long ctx, byte[] terms, int nterms, int order, long minPostings, long cap,
                                             byte[] hosts6Out);

@@ -174,6 +174,19 @@ class CRetentionStats(ctypes.Structure):
         [(n, ctypes.c_int64) for n in ("t_mark_ns", "t_select_ns", "t_total_ns", "hist_bypass")]
 
 
+REFS_BY_TERM, REFS_BY_URL = 0, 1  # YRWI_REFS_BY_*: the orders of yrwi_url_references
+REFS_ORDERS = {"term": REFS_BY_TERM, "url": REFS_BY_URL}
+REFS_STREAM, REFS_PROBE = 0, 1  # yrwi_ref_stats.path
+REF_LDS_MAX = 2048  # YRWI_REF_LDS_MAX: the largest url set the streaming path of yrwi_url_references searches in LDS
+
+
+class CRefStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("lists", "postings", "urls", "urls_found", "refs", "lists_hit",
+                                              "lists_covered")] + \
+        [(n, ctypes.c_int32) for n in ("path", "direct", "launches", "syncs")] + \
+        [(n, ctypes.c_int64) for n in ("bytes_h2d", "bytes_d2h", "t_find_ns", "t_total_ns")]
+
+
 DUMP_WINDOW_DEFAULT = 32 << 20 # yrwi_dump_heap's window without YRWI_DUMP_WINDOW (bytes)
 
 
@@ -224,6 +237,8 @@ SIGNATURES = {
                                             ctypes.POINTER(CRetentionStats)]),
     "yrwi_retain": (ctypes.c_int, [_VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
                                    ctypes.POINTER(CUpdateStats), ctypes.POINTER(CRetentionStats)]),
+    "yrwi_url_references": (ctypes.c_int, [_VP, _VP, ctypes.c_int32, _VP, ctypes.c_int64, ctypes.c_int32, _VP, _VP,
+                                           _VP, ctypes.c_int64, ctypes.POINTER(CRefStats)]),
     "yrwi_build_url_ids": (ctypes.c_int, [_VP]),
     "yrwi_list_size": (ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]),
     "yrwi_get_list": (ctypes.c_int, [_VP, ctypes.c_char_p, _VP, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),

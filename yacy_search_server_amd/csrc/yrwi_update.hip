@@ -64,6 +64,10 @@
 // described with their kernels at the end of this file.  They share the selection, the spans and
 // compact_commit with the host calls.
 //
+// yrwi_url_references: the read-only form of yrwi_remove_postings, counts and rows of the postings of a url
+// set; described with its kernels at the end of this file.  It shares the selection, the spans and the
+// cursor with the host calls.
+//
 // A changed list is a new list in index memory (the old copy is dead until repack_index,
 // reached through ensure_url_ids) and goes through index_changed like a replaced list.
 
@@ -1736,4 +1740,512 @@ extern "C" int yrwi_retention_count(yrwi_ctx* ctx, const uint8_t* terms12, int32
 extern "C" int yrwi_retain(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, int32_t min_day, int64_t max_refs,
                            yrwi_update_stats* st, yrwi_retention_stats* rst) {
   return retention(ctx, terms12, nterms, min_day, max_refs, nullptr, true, st, rst);
+}
+
+// ---------------------------------------------------------------- references of urls
+//
+// yrwi_url_references, the read-only form of yrwi_remove_postings (UNVERIFIED against a reference line: the
+// reference has no such method).  Two ways to find the references, one way to deliver them.
+//
+// STREAM (k_ref_stream): the grid, spans, SegCursor and four loads in flight of k_host_mark over khi / klo of
+// the selected lists in term order, 9 B per posting and no row read; the lookup is the slot of the 72-bit key
+// in the sorted url set, staged in LDS (8 B + 1 B per url) up to REF_LDS_MAX urls and searched in global
+// memory above.  Per-list hits are summed in the wave and added on leaving the list, as jrem is; per-url
+// hits take one atomic per distinct slot of a wave's step.
+// PROBE (k_ref_probe): one thread per (list, slot) pair, list-major, searches the list for the url (lb_key).
+//
+// Both number their domain the way YRWI_REFS_BY_TERM orders the references (term, then url), so a hit's
+// place is the hits before it: the count pass adds every wave's hits to its tile's count (1024 postings,
+// 256 pairs), k_ref_scan turns the counts into 64-bit starts, and the pack pass (the same kernels, MODE
+// REF_PACK) finds the hits of the tiles that have any again and writes each at its tile's start plus its rank
+// in the tile.  The pack pass reads the total from device memory and returns when it exceeds the capacity.
+// YRWI_REFS_BY_URL: the pack pass writes (slot, list << 32 | row) per reference instead (REF_KEYS), one
+// stable radix sort by slot orders them, k_ref_place moves the rows.
+namespace {
+
+constexpr int REF_LDS_MAX = YRWI_REF_LDS_MAX;  // urls searched in LDS (9 B each)
+constexpr int REF_PAIR_TILE = 256;             // (list, url) pairs per tile of PROBE: one per thread
+// dispatch: one search step of PROBE is weighed as this many streamed keys of STREAM.  From the crossover of the
+// two forced paths on C2: PROBE still wins at 4096 urls, where the estimate tips at 0.174,
+// STREAM at 65,536, where it tips at 0.011 (a wave's searches of one list share their loads; a streamed key
+// costs a search of the set as well)
+constexpr double REF_PROBE_STEP_KEYS = 0.05;
+
+enum { REF_COUNT = 0, REF_TILES = 1, REF_PACK = 2, REF_KEYS = 3 };  // what a finding kernel does with a hit
+
+struct RefOut {  // where the pack pass writes (REF_PACK: rows, terms; REF_KEYS: skey, sval)
+  const int64_t* tile_start;  // references before every tile; [tiles] = all of them
+  int64_t tiles, cap;
+  const uint32_t* lterm;  // the term hash of every selected list, three words each
+  uint8_t* rows;
+  uint32_t* terms;
+  uint32_t* skey;
+  uint64_t* sval;
+};
+
+// slot of (h, l) in the ascending 72-bit set, -1: not in it
+__device__ __forceinline__ int ref_slot(const uint64_t* kh, const uint8_t* kl, int nu, uint64_t h, uint32_t l) {
+  int lo = 0, hi = nu;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (key_lt(kh[mid], kl[mid], h, l)) lo = mid + 1; else hi = mid;
+  }
+  return lo < nu && kh[lo] == h && (uint32_t)kl[lo] == l ? lo : -1;
+}
+
+// cnt[key] += the wave's hits of that key: one atomic per distinct key.  Called by the whole wave.
+__device__ __forceinline__ void wave_add_by(bool hit, int key, unsigned long long* __restrict__ cnt) {
+  const int lane = threadIdx.x & 63;
+  uint64_t act = __ballot(hit);
+  while (act) {
+    const int lead = __ffsll((unsigned long long)act) - 1;
+    const int lk = __shfl(key, lead, 64);
+    const uint64_t same = __ballot(hit && key == lk);
+    if (lane == lead) atomicAdd(&cnt[lk], (unsigned long long)__popcll(same));
+    act &= ~same;
+  }
+}
+
+__device__ __forceinline__ uint32_t lanes_below(uint64_t ballot) {
+  return (uint32_t)__popcll(ballot & (((uint64_t)1 << (threadIdx.x & 63)) - 1));
+}
+
+// reference r = row k of list c, url slot `slot`
+template <int MODE>
+__device__ __forceinline__ void ref_emit(const RefOut& O, const RmJob* __restrict__ jobs, int64_t r, int c, int64_t k,
+                                         int slot) {
+  if (MODE == REF_PACK) {
+    copy_row(O.rows + r * YRWI_ROW_BYTES, jobs[c].rows + k * YRWI_ROW_BYTES);
+#pragma unroll
+    for (int w = 0; w < 3; w++) O.terms[r * 3 + w] = O.lterm[(int64_t)c * 3 + w];
+  } else {
+    O.skey[r] = (uint32_t)slot;
+    O.sval[r] = ((uint64_t)(uint32_t)c << 32) | (uint64_t)k;
+  }
+}
+
+// One step of a thread, as mark_tile: postings base + 256 u + thread (u < 4) below end -> their slots in the
+// url set (-1: not of the set, or past end), lists and rows.  The four key loads are issued before the first search.
+__device__ __forceinline__ void ref_tile(SegCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                         int nj, int64_t total, const uint64_t* kh, const uint8_t* kl, int nu,
+                                         int64_t base, int64_t end, int slot[4], int c[4], int64_t k[4]) {
+  uint64_t h[4];
+  uint32_t l[4];
+#pragma unroll
+  for (int u = 0; u < 4; u++) {
+    const int64_t i = base + u * 256 + threadIdx.x;
+    c[u] = -1;
+    k[u] = 0;
+    h[u] = 0;
+    l[u] = 0;
+    if (i < end) {
+      seg_seek(s, jobs, off, nj, total, i);
+      c[u] = s.c;
+      k[u] = i - s.lo;
+      h[u] = s.kh[k[u]];
+      l[u] = s.kl[k[u]];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < 4; u++) slot[u] = c[u] >= 0 ? ref_slot(kh, kl, nu, h[u], l[u]) : -1;
+}
+
+// STREAM.  REF_COUNT / REF_TILES: jcnt[c] += references in list c, ucnt[slot] += references of url slot,
+// REF_TILES: tile_cnt[t] += references in tile t (the three zeroed by the caller).  REF_PACK / REF_KEYS: the
+// references of every tile that has any go where O says.  Every wave of a workgroup runs every step whole.
+template <bool LDS, int MODE>
+__global__ __launch_bounds__(256) void k_ref_stream(const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                                    int nj, int64_t total, const uint64_t* __restrict__ ukh,
+                                                    const uint8_t* __restrict__ ukl, int nu,
+                                                    unsigned long long* __restrict__ jcnt,
+                                                    unsigned long long* __restrict__ ucnt,
+                                                    int32_t* __restrict__ tile_cnt, RefOut O) {
+  __shared__ uint64_t s_kh[LDS ? REF_LDS_MAX : 1];
+  __shared__ uint8_t s_kl[LDS ? REF_LDS_MAX : 1];
+  __shared__ uint32_t s_w[16];
+  if (MODE >= REF_PACK && O.tile_start[O.tiles] > O.cap) return;  // (the same in every thread of the grid)
+  const uint64_t* kh = ukh;
+  const uint8_t* kl = ukl;
+  if (LDS) {
+    for (int i = threadIdx.x; i < nu; i += blockDim.x) {
+      s_kh[i] = ukh[i];
+      s_kl[i] = ukl[i];
+    }
+    __syncthreads();
+    kh = s_kh;
+    kl = s_kl;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int64_t begin, end;
+  host_span(total, &begin, &end);
+  SegCursor cur;
+  int acc_c = -1;
+  uint32_t acc_n = 0;
+  for (int64_t base = begin; base < end; base += HOST_TILE) {
+    const int64_t t = base / HOST_TILE;
+    int64_t tstart = 0;
+    if (MODE >= REF_PACK) {
+      tstart = O.tile_start[t];
+      if (O.tile_start[t + 1] == tstart) continue;  // (the same in every thread of the workgroup)
+    }
+    int slots[4], cs[4];
+    int64_t ks[4];
+    ref_tile(cur, jobs, off, nj, total, kh, kl, nu, base, end, slots, cs, ks);
+    if (MODE <= REF_TILES) {
+      uint32_t tile_n = 0;
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int c = cs[u];
+        const bool hit = slots[u] >= 0;
+        // per list: as k_host_mark sums jrem (acc_c, acc_n: the same in every lane)
+        uint64_t act = __ballot(hit);
+        tile_n += (uint32_t)__popcll(act);
+        while (act) {
+          const int lead = __ffsll((unsigned long long)act) - 1;
+          const int lc = __shfl(c, lead, 64);
+          const uint64_t same = __ballot(hit && c == lc);
+          if (lc != acc_c) {
+            if (acc_n && lane == 0) atomicAdd(&jcnt[acc_c], (unsigned long long)acc_n);
+            acc_c = lc;
+            acc_n = 0;
+          }
+          acc_n += (uint32_t)__popcll(same);
+          act &= ~same;
+        }
+        wave_add_by(hit, slots[u], ucnt);
+      }
+      if (MODE == REF_TILES && tile_n && lane == 0) atomicAdd(&tile_cnt[t], (int32_t)tile_n);
+    } else {
+      // a hit's rank in the tile: the hits of the steps before, of the waves before in its step, of the lanes before
+      uint64_t bal[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        bal[u] = __ballot(slots[u] >= 0);
+        if (lane == 0) s_w[u * 4 + wave] = (uint32_t)__popcll(bal[u]);
+      }
+      __syncthreads();
+      uint32_t run = 0;
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        uint32_t mine = run;
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+          const uint32_t v = s_w[u * 4 + w];
+          if (w < wave) mine += v;
+          run += v;
+        }
+        if (slots[u] >= 0) ref_emit<MODE>(O, jobs, tstart + mine + lanes_below(bal[u]), cs[u], ks[u], slots[u]);
+      }
+      __syncthreads();  // (s_w is written again in the next tile that has hits)
+    }
+  }
+  if (MODE <= REF_TILES && acc_n && lane == 0) atomicAdd(&jcnt[acc_c], (unsigned long long)acc_n);
+}
+
+// PROBE: pair p = list p / nu, slot p % nu; tile t = pairs [256 t, 256 t + 256).  Modes as k_ref_stream.
+template <int MODE>
+__global__ __launch_bounds__(REF_PAIR_TILE) void k_ref_probe(const RmJob* __restrict__ jobs,
+                                                             const uint64_t* __restrict__ ukh,
+                                                             const uint8_t* __restrict__ ukl, int nu, int64_t pairs,
+                                                             unsigned long long* __restrict__ jcnt,
+                                                             unsigned long long* __restrict__ ucnt,
+                                                             int32_t* __restrict__ tile_cnt, RefOut O) {
+  __shared__ uint32_t s_w[4];
+  const int64_t t = blockIdx.x;
+  int64_t tstart = 0;
+  if (MODE >= REF_PACK) {
+    if (O.tile_start[O.tiles] > O.cap) return;
+    tstart = O.tile_start[t];
+    if (O.tile_start[t + 1] == tstart) return;  // (the same in every thread of the workgroup)
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t p = t * REF_PAIR_TILE + threadIdx.x;
+  bool hit = false;
+  int c = 0, slot = 0;
+  int64_t k = 0;
+  if (p < pairs) {
+    c = (int)(p / nu);
+    slot = (int)(p - (int64_t)c * nu);
+    const uint64_t* lkh = jobs[c].khi;
+    const uint8_t* lkl = jobs[c].klo;
+    const int64_t n = jobs[c].n;
+    const uint64_t h = ukh[slot];
+    const uint32_t l = ukl[slot];
+    k = lb_key(lkh, lkl, 0, n, h, l);
+    hit = k < n && lkh[k] == h && (uint32_t)lkl[k] == l;
+  }
+  const uint64_t bal = __ballot(hit);
+  if (MODE <= REF_TILES) {
+    wave_add_by(hit, c, jcnt);
+    wave_add_by(hit, slot, ucnt);
+    if (MODE == REF_TILES && bal && lane == 0) atomicAdd(&tile_cnt[t], (int32_t)__popcll(bal));
+  } else {
+    if (lane == 0) s_w[wave] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint32_t mine = 0;
+    for (int w = 0; w < wave; w++) mine += s_w[w];
+    if (hit) ref_emit<MODE>(O, jobs, tstart + mine + lanes_below(bal), c, k, slot);
+  }
+}
+
+// One workgroup walks the tile counts, 1024 at a time (four neighbours per thread) with a running 64-bit
+// carry: tile_start[t] = references before tile t, tile_start[tiles] = *total = all of them.
+__global__ __launch_bounds__(256) void k_ref_scan(const int32_t* __restrict__ tile_cnt, int64_t tiles,
+                                                  int64_t* __restrict__ tile_start,
+                                                  unsigned long long* __restrict__ total) {
+  __shared__ uint64_t s_w[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint64_t carry = 0;
+  for (int64_t b = 0; b < tiles; b += 1024) {
+    const int64_t x = b + 4 * (int64_t)threadIdx.x;
+    uint32_t v[4];
+    uint64_t sum = 0;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      v[u] = x + u < tiles ? (uint32_t)tile_cnt[x + u] : 0u;
+      sum += v[u];
+    }
+    uint64_t inc = sum;  // inclusive sums over the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint64_t o = shfl64(inc, lane >= d ? lane - d : lane);
+      if (lane >= d) inc += o;
+    }
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    uint64_t before = carry + inc - sum, all = 0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      if (w < wave) before += s_w[w];
+      all += s_w[w];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      if (x + u < tiles) tile_start[x + u] = (int64_t)before;
+      before += v[u];
+    }
+    carry += all;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    tile_start[tiles] = (int64_t)carry;
+    *total = carry;
+  }
+}
+
+// YRWI_REFS_BY_URL, after the sort: reference r is row (sval[r] & 2^32 - 1) of list sval[r] >> 32
+__global__ __launch_bounds__(256) void k_ref_place(const RmJob* __restrict__ jobs, const uint32_t* __restrict__ lterm,
+                                                   const uint64_t* __restrict__ sval, int64_t n,
+                                                   uint8_t* __restrict__ rows, uint32_t* __restrict__ terms) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const uint64_t v = sval[r];
+  const int64_t c = (int64_t)(v >> 32), k = (int64_t)(v & 0xFFFFFFFFull);
+  copy_row(rows + r * YRWI_ROW_BYTES, jobs[c].rows + k * YRWI_ROW_BYTES);
+#pragma unroll
+  for (int w = 0; w < 3; w++) terms[r * 3 + w] = lterm[c * 3 + w];
+}
+
+struct RefPass {  // the device side of one call, as its finding kernels take it
+  const RmJob* jobs;
+  const int64_t* off;
+  int nj, nu;
+  int64_t total, pairs, tiles;
+  const uint64_t* ukh;
+  const uint8_t* ukl;
+  unsigned long long *jcnt, *ucnt;
+  int32_t* tile_cnt;
+  bool probe;
+};
+
+template <int MODE>
+void ref_find(const RefPass& P, const RefOut& O, hipStream_t s) {
+  if (P.probe) {
+    hipLaunchKernelGGL((k_ref_probe<MODE>), dim3((unsigned)P.tiles), dim3(REF_PAIR_TILE), 0, s, P.jobs, P.ukh, P.ukl,
+                       P.nu, P.pairs, P.jcnt, P.ucnt, P.tile_cnt, O);
+  } else if (P.nu <= REF_LDS_MAX) {
+    hipLaunchKernelGGL((k_ref_stream<true, MODE>), dim3(mark_blocks(P.total)), dim3(256), 0, s, P.jobs, P.off, P.nj,
+                       P.total, P.ukh, P.ukl, P.nu, P.jcnt, P.ucnt, P.tile_cnt, O);
+  } else {
+    hipLaunchKernelGGL((k_ref_stream<false, MODE>), dim3(mark_blocks(P.total)), dim3(256), 0, s, P.jobs, P.off, P.nj,
+                       P.total, P.ukh, P.ukl, P.nu, P.jcnt, P.ucnt, P.tile_cnt, O);
+  }
+}
+
+}  // namespace
+
+extern "C" int yrwi_url_references(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uint8_t* urls12,
+                                   int64_t nurls, int32_t order, int64_t* counts, uint8_t* terms12_out,
+                                   uint8_t* rows40_out, int64_t cap_refs, yrwi_ref_stats* st) {
+  if (st) std::memset(st, 0, sizeof(*st));
+  if (!ctx || nterms < 0 || nurls < 0 || (nterms > 0 && !terms12) || (nurls > 0 && !urls12)) return YRWI_E_ARG;
+  if (order != YRWI_REFS_BY_TERM && order != YRWI_REFS_BY_URL) return ctx->fail(YRWI_E_ARG, "unknown reference order");
+  if (cap_refs < 0 || (cap_refs > 0 && (!terms12_out || !rows40_out)))
+    return ctx->fail(YRWI_E_ARG, "reference capacity without buffers");
+  if (nurls > (int64_t)INT32_MAX) return ctx->fail(YRWI_E_LIMIT, "2^31 urls or more in one call");
+  const auto t_begin = std::chrono::steady_clock::now();
+  yrwi_ref_stats S;
+  std::memset(&S, 0, sizeof(S));
+  Tally T;
+  // ---- the urls as given (for counts) and as a set, sorted and each once; the selected lists in term order
+  std::vector<KeyT> in((size_t)nurls);
+  for (int64_t i = 0; i < nurls; i++)
+    if (!key_of(urls12 + i * 12, &in[(size_t)i])) return ctx->fail(YRWI_E_HASH, "url hash is not well-formed Base64");
+  std::vector<KeyT> uk = in;
+  std::sort(uk.begin(), uk.end());
+  uk.erase(std::unique(uk.begin(), uk.end()), uk.end());
+  ListSel sel;
+  if (int rc = select_lists(ctx, terms12, nterms, true, &sel)) return rc;
+  RmTable t;
+  rm_table(sel, &t);
+  const int nj = (int)t.jobs.size(), nu = (int)uk.size();
+  const int64_t total = t.total;
+  if (counts) std::fill(counts, counts + nurls, (int64_t)0);
+  S.lists = nj;
+  S.postings = total;
+  S.urls = nu;
+  Lane* L = ctx->lanes[0];
+  const int64_t up0 = L->up_bytes, down0 = L->down_bytes;
+  auto finish = [&](int rc) {
+    S.launches = T.launches;
+    S.syncs = T.syncs;
+    S.bytes_h2d = L->up_bytes - up0;
+    S.bytes_d2h = L->down_bytes - down0;
+    S.t_total_ns =
+        std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_begin).count();
+    if (st) *st = S;
+    return rc;
+  };
+  if (nu == 0 || nj == 0) return finish(0);
+  // ---- the path: PROBE's search steps against STREAM's keys, unless the environment names one
+  const int64_t pairs = (int64_t)nj * nu;
+  int steps = 1;  // of one search: ceil(log2(mean list length + 1))
+  while (steps < 63 && ((int64_t)1 << steps) < total / nj + 1) steps++;
+  bool probe = (double)pairs * steps * REF_PROBE_STEP_KEYS <= (double)total;
+  const char* forced = getenv("YRWI_REFS_PATH");
+  if (forced && !strcmp(forced, "stream")) probe = false;
+  if (forced && !strcmp(forced, "probe")) probe = true;
+  const int64_t tiles = probe ? ceil_div(pairs, REF_PAIR_TILE) : ceil_div(total, HOST_TILE);
+  if (probe && tiles > (int64_t)INT32_MAX) return ctx->fail(YRWI_E_LIMIT, "2^39 (list, url) pairs or more on the probe path");
+  S.path = probe ? YRWI_REFS_PROBE : YRWI_REFS_STREAM;
+  const bool fetch = cap_refs > 0, by_url = order == YRWI_REFS_BY_URL;
+  // no more references than postings or pairs: a larger cap_refs promises nothing the call could use
+  const int64_t room = std::min(cap_refs, std::min(total, pairs));
+  const bool direct = fetch && (reinterpret_cast<uintptr_t>(rows40_out) & 7) == 0 &&
+                      ctx->hostreg.contains(rows40_out, (size_t)room * YRWI_ROW_BYTES);
+  if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
+  T.syncs++;
+  std::vector<uint64_t> h_ukh((size_t)nu);
+  std::vector<uint8_t> h_ukl((size_t)nu);
+  for (int i = 0; i < nu; i++) {
+    h_ukh[(size_t)i] = uk[(size_t)i].hi;
+    h_ukl[(size_t)i] = (uint8_t)uk[(size_t)i].lo;
+  }
+  std::vector<uint32_t> lterm((size_t)nj * 3);  // the lists' term hashes, as the pack pass stores them
+  for (int j = 0; j < nj; j++) key_chars(t.jkey[(size_t)j], reinterpret_cast<uint8_t*>(&lterm[(size_t)j * 3]));
+  // ---- device tables; the counters (per list, per url, the total) and the tile counts are one block, zeroed at once
+  const int64_t nres = (int64_t)nj + nu + 1;
+  const size_t zero_bytes = (size_t)nres * 8 + (fetch ? (size_t)tiles * 4 : 0);
+  uint64_t* ukh = arena_alloc<uint64_t>(L, nu);
+  uint8_t* ukl = arena_alloc<uint8_t>(L, nu);
+  RmJob* d_jobs = arena_alloc<RmJob>(L, nj);
+  int64_t* d_off = arena_alloc<int64_t>(L, nj);
+  uint32_t* d_lterm = arena_alloc<uint32_t>(L, (int64_t)nj * 3);
+  unsigned long long* res = reinterpret_cast<unsigned long long*>(L->arena.alloc(zero_bytes));
+  int64_t* tile_start = fetch ? arena_alloc<int64_t>(L, tiles + 1) : nullptr;
+  if (!ukh || !ukl || !d_jobs || !d_off || !d_lterm || !res || (fetch && !tile_start))
+    return ctx->fail(YRWI_E_NOMEM, "device allocation (url references)");
+  RefPass P{d_jobs, d_off, nj, nu, total, pairs, tiles, ukh, ukl, res, res + nj,
+            reinterpret_cast<int32_t*>(res + nres), probe};
+  RefOut O{tile_start, tiles, cap_refs, d_lterm, nullptr, nullptr, nullptr, nullptr};
+  uint8_t* d_rows = nullptr;  // where the rows are written: the caller's pinned buffer or scratch
+  auto out_buffers = [&](int64_t n) {
+    if (direct) {
+      if (hipHostGetDevicePointer(reinterpret_cast<void**>(&d_rows), rows40_out, 0) != hipSuccess) return false;
+    } else {
+      d_rows = arena_alloc<uint8_t>(L, n * YRWI_ROW_BYTES);
+    }
+    O.rows = d_rows;
+    O.terms = arena_alloc<uint32_t>(L, n * 3);
+    return d_rows && O.terms;
+  };
+  if (fetch && !by_url && !out_buffers(room)) return ctx->fail(YRWI_E_NOMEM, "device allocation (url references)");
+  // ---- find: one upload, one memset, the count pass; fetch: the scan and, by term, the pack pass behind it
+  if (int rc = upload(L, ukh, h_ukh, ukl, h_ukl, d_jobs, t.jobs, d_off, t.off, d_lterm, lterm)) return ctx->take(L, rc);
+  HIPCHK(ctx, hipMemsetAsync(res, 0, zero_bytes, L->stream));
+  hipEvent_t e0 = L->event(), e1 = L->event();
+  HIPCHK(ctx, hipEventRecord(e0, L->stream));
+  if (fetch) ref_find<REF_TILES>(P, O, L->stream); else ref_find<REF_COUNT>(P, O, L->stream);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipEventRecord(e1, L->stream));
+  T.launches += 3;
+  if (fetch) {
+    hipLaunchKernelGGL(k_ref_scan, dim3(1), dim3(256), 0, L->stream, P.tile_cnt, tiles, tile_start, res + nres - 1);
+    T.launches++;
+    if (!by_url) {
+      ref_find<REF_PACK>(P, O, L->stream);
+      T.launches++;
+    }
+    HIPCHK(ctx, hipGetLastError());
+  }
+  const int64_t* h = reinterpret_cast<const int64_t*>(readback(L, &L->down_stage, res, nres, 8, 8));
+  if (!h) return ctx->take(L, YRWI_E_HIP);
+  T.launches++;
+  HIPCHK(ctx, lane_sync(L));
+  T.syncs++;
+  float msf = 0.f;
+  if (hipEventElapsedTime(&msf, e0, e1) == hipSuccess) S.t_find_ns = (int64_t)((double)msf * 1e6);
+  (void)hipGetLastError();  // a statistics event that could not be read is not the call's error
+  // ---- the counts (the pinned landing buffer is reused below)
+  for (int j = 0; j < nj; j++) {
+    S.refs += h[j];
+    S.lists_hit += h[j] > 0;
+    S.lists_covered += h[j] == t.jobs[(size_t)j].n;
+  }
+  for (int i = 0; i < nu; i++) S.urls_found += h[nj + i] > 0;
+  if (counts)
+    for (int64_t i = 0; i < nurls; i++)
+      counts[i] = h[nj + (std::lower_bound(uk.begin(), uk.end(), in[(size_t)i]) - uk.begin())];
+  if (!fetch) return finish(0);
+  const int64_t refs = S.refs;
+  if (refs > cap_refs) {  // the pack pass saw the same total and stored nothing
+    finish(0);
+    return ctx->fail(YRWI_E_ARG, "reference capacity too small: st->refs references are needed");
+  }
+  const int64_t nout = std::max<int64_t>(refs, 1);  // (nothing found: the tail runs over one unused element)
+  if (by_url) {
+    // ---- the references alone, sorted stably by url slot, then placed
+    if (refs > (int64_t)INT32_MAX) return ctx->fail(YRWI_E_LIMIT, "2^31 references or more by url");
+    int bits = 1;
+    while (bits < 32 && ((int64_t)1 << bits) < nu) bits++;
+    uint32_t* skey = arena_alloc<uint32_t>(L, nout);
+    uint32_t* okey = arena_alloc<uint32_t>(L, nout);
+    uint64_t* sval = arena_alloc<uint64_t>(L, nout);
+    uint64_t* oval = arena_alloc<uint64_t>(L, nout);
+    size_t tb = 0;
+    HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, skey, okey, sval, oval, (int)nout, 0, bits, L->stream));
+    void* tmp = L->arena.alloc(tb);
+    if (!skey || !okey || !sval || !oval || !tmp || !out_buffers(nout))
+      return ctx->fail(YRWI_E_NOMEM, "device allocation (url references by url)");
+    O.skey = skey;
+    O.sval = sval;
+    ref_find<REF_KEYS>(P, O, L->stream);
+    HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairs(tmp, tb, skey, okey, sval, oval, (int)nout, 0, bits, L->stream));
+    hipLaunchKernelGGL(k_ref_place, dim3(blocks(nout)), dim3(256), 0, L->stream, d_jobs, d_lterm, oval, refs, d_rows,
+                       O.terms);
+    HIPCHK(ctx, hipGetLastError());
+    T.launches += 3;
+  }
+  // ---- the terms, and the rows that were not written in place, leave through the pinned landing buffers
+  const uint8_t* ht = readback(L, &L->down_stage, O.terms, nout, 12, 12);
+  const uint8_t* hr = direct ? nullptr : readback(L, &L->out_stage, d_rows, nout, YRWI_ROW_BYTES, YRWI_ROW_BYTES);
+  if (!ht || (!direct && !hr)) return ctx->take(L, YRWI_E_HIP);
+  T.launches += direct ? 1 : 2;
+  if (direct) L->down_bytes += refs * YRWI_ROW_BYTES;
+  HIPCHK(ctx, lane_sync(L));
+  T.syncs++;
+  std::memcpy(terms12_out, ht, (size_t)refs * 12);
+  if (!direct) std::memcpy(rows40_out, hr, (size_t)refs * YRWI_ROW_BYTES);
+  S.direct = direct ? 1 : 0;
+  return finish(0);
 }

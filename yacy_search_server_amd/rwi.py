@@ -420,6 +420,57 @@ class RWIIndex:
                                                     counts.ctypes.data if len(counts) else None, ctypes.byref(hit)))
         return counts, hit.value
 
+    def url_references_raw(self, urls, terms, order: int, counts, terms_out, rows_out,
+                           cap_refs: int) -> Tuple[int, "_lib.CRefStats"]:
+        """yrwi_url_references as it is: urls and terms are the hashes' bytes (terms empty or None:
+        every list), counts / terms_out / rows_out ctypes arrays, numpy arrays, addresses or None.
+        Returns (rc, the call's yrwi_ref_stats) and raises nothing."""
+        st = _lib.CRefStats()
+        ub = np.frombuffer(bytes(urls or b""), dtype=np.uint8)
+        tb = np.frombuffer(bytes(terms or b""), dtype=np.uint8)
+        rc = _lib.lib().yrwi_url_references(self._h, tb.ctypes.data if len(tb) else None, len(tb) // 12,
+                                            ub.ctypes.data if len(ub) else None, len(ub) // 12, order,
+                                            _address(counts), _address(terms_out), _address(rows_out), cap_refs,
+                                            ctypes.byref(st))
+        return rc, st
+
+    def url_references(self, urls: Sequence[bytes], terms: Optional[Sequence[bytes]] = None, order: str = "term",
+                       fetch: bool = True, rows_out=None):
+        """What remove_postings(urls, terms) would remove, the index unchanged (yrwi_url_references):
+        (counts, terms, rows, stats) -- the references of each url as int64 in the order given, and
+        with fetch=True every reference in `order` ("term": by term hash, then url hash; "url": by
+        url hash, then term hash) as an (n, 12) uint8 array of term hashes and an (n, 40) uint8
+        array of rows as get_list returns them; fetch=False: terms and rows are None.  stats is the
+        yrwi_ref_stats of the last call as a dict.  rows_out: a uint8 buffer for the rows (a numpy
+        array or, for rows written by the kernel itself, a host_array); the call then fetches at once
+        into its 40-byte capacity and raises YRWI_E_ARG when that is too small (rows is a view of
+        it).  Without rows_out a counting call sizes the buffers first."""
+        o = _lib.REFS_ORDERS[order]
+        ub = _hashes(urls)
+        tb = _hashes(terms or ())
+        counts = np.zeros(len(urls), dtype=np.int64)
+        as_dict = lambda st: {f: getattr(st, f) for f, _ in _lib.CRefStats._fields_}
+        cptr = counts if len(counts) else None
+        if terms is not None and len(terms) == 0:  # no term named (nterms == 0 would mean every list)
+            none = (np.zeros((0, 12), np.uint8), np.zeros((0, 40), np.uint8)) if fetch else (None, None)
+            return (counts,) + none + (as_dict(_lib.CRefStats()),)
+        if not fetch or rows_out is None:
+            rc, st = self.url_references_raw(ub, tb, o, cptr, None, None, 0)
+            _check(self._h, rc)
+            if not fetch or st.refs == 0:
+                none = (np.zeros((0, 12), np.uint8), np.zeros((0, 40), np.uint8)) if fetch else (None, None)
+                return (counts,) + none + (as_dict(st),)
+            buf = np.zeros(40 * st.refs, dtype=np.uint8)
+        else:
+            buf = rows_out if isinstance(rows_out, np.ndarray) else np.ctypeslib.as_array(rows_out)
+            buf = buf.reshape(-1).view(np.uint8)
+        cap = len(buf) // 40
+        tout = np.zeros((max(cap, 1), 12), dtype=np.uint8)
+        rc, st = self.url_references_raw(ub, tb, o, cptr, tout if cap else None, buf if cap else None, cap)
+        _check(self._h, rc)
+        n = st.refs if cap else 0
+        return counts, tout[:n], buf[:40 * n].reshape(-1, 40), as_dict(st)
+
     def host_census(self, terms: Optional[Sequence[bytes]] = None, order: str = "count", min_postings: int = 1,
                     top: Optional[int] = None) -> Tuple[List[bytes], np.ndarray, dict]:
         """Which hosts have postings in the lists of `terms`, or with terms=None in every list, and
