@@ -1,6 +1,6 @@
 // yrwi_host.h -- host-side structures shared by libyrwi's host translation
 // units (yrwi_host.cpp: contexts, planning, query execution; yrwi_join.cpp: the
-// join phase; yrwi_rank.cpp: the rank phase; yrwi_heap.cpp: BLOB heap loader).
+// join phase; yrwi_rank.cpp: the rank phase; yrwi_load.hip: BLOB heap loader).
 // Internal; the public ABI is include/yrwi.h.
 #pragma once
 

@@ -68,6 +68,14 @@
 // set; described with its kernels at the end of this file.  It shares the selection, the spans and the
 // cursor with the host calls.
 //
+// What the streaming passes share stands once, in front of the first kernel: the span of a workgroup (span_of,
+// span_blocks, SPAN_TILE, SPAN_BLOCKS), the cursor (SegCursor), the four key loads of a step (key_tile; day_tile
+// is its counterpart over the rows), the per-list sum of a wave (ListTally), equal keys of a wave as one atomic
+// (wave_add_by), the search of a sorted set (set_slot, host_slot) and its staging in LDS (stage_set).  On the
+// host the first pass of every call but yrwi_add_postings runs in one frame (pass_begin: a new pass, the tables
+// allocated and uploaded at once, the result block zeroed; pass_end: one read-back, one wait), and the two calls
+// that take urls prepare them in url_set.
+//
 // A changed list is a new list in index memory (the old copy is dead until repack_index,
 // reached through ensure_url_ids) and goes through index_changed like a replaced list.
 
@@ -81,8 +89,14 @@ using namespace yrwi;
 namespace {
 
 constexpr int HOST_LDS_MAX = YRWI_HOST_LDS_MAX;         // host keys searched in LDS (8 B each)
-constexpr int HOST_MARK_BLOCKS = 2048;                  // k_host_mark's grid cap
+constexpr int SPAN_TILE = 1024;    // postings a workgroup of a streaming pass takes per step: 4 per thread, their loads in flight together
+constexpr int SPAN_BLOCKS = 2048;  // the grid cap of the streaming passes
 constexpr int64_t RM_CHUNK_DEFAULT = (int64_t)1 << 26;  // rows compacted at a time (YRWI_RM_CHUNK)
+
+unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+// the grid of a streaming pass over n flattened postings
+unsigned span_blocks(int64_t n) { return (unsigned)std::min<int64_t>((n + SPAN_TILE - 1) / SPAN_TILE, SPAN_BLOCKS); }
 
 struct UpdJob {  // one touched list and the job's rows in the sorted batch
   const uint64_t* akhi;
@@ -129,6 +143,135 @@ __device__ __forceinline__ void wave_move_rows(const uint8_t* srcp, uint8_t* dst
 
 // lastModified: the row's `a` cell (bytes 12-13, big endian)
 __device__ __forceinline__ uint32_t row_lm(const uint8_t* __restrict__ r) { return ((uint32_t)r[12] << 8) | r[13]; }
+
+// ---------------------------------------------------------------- what the kernels below share
+
+// slot of (h, l) in the ascending 72-bit set kh / kl[0, n), -1: not in it.  I: int for a set of at most 2^31
+// keys, as the streaming passes take, int64_t for k_rm_*'s.
+template <class I>
+__device__ __forceinline__ I set_slot(const uint64_t* kh, const uint8_t* kl, I n, uint64_t h, uint32_t l) {
+  I lo = 0, hi = n;
+  while (lo < hi) {
+    const I mid = (lo + hi) >> 1;
+    if (key_lt(kh[mid], kl[mid], h, l)) lo = mid + 1; else hi = mid;
+  }
+  return lo < n && kh[lo] == h && (uint32_t)kl[lo] == l ? lo : (I)-1;
+}
+
+// slot of h in the ascending set hs[0, nh), -1: not in it
+__device__ __forceinline__ int host_slot(const uint64_t* __restrict__ hs, int nh, uint64_t h) {
+  int lo = 0, hi = nh;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (hs[mid] < h) lo = mid + 1; else hi = mid;
+  }
+  return lo < nh && hs[lo] == h ? lo : -1;
+}
+
+// The sorted set of a streaming pass into LDS (LDS = true: it fits; the pass then searches it there), or left
+// where it is.  A set of 8-byte keys kh, or (LOW) of 8 + 1-byte keys kh / kl.
+template <bool LDS, bool LOW = false>
+__device__ __forceinline__ void stage_set(uint64_t* s_kh, const uint64_t* __restrict__ kh, int n,
+                                          uint8_t* s_kl = nullptr, const uint8_t* __restrict__ kl = nullptr) {
+  if (!LDS) return;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    s_kh[i] = kh[i];
+    if (LOW) s_kl[i] = kl[i];
+  }
+  __syncthreads();
+}
+
+// A lane's place in the flattened lists.  A workgroup walks a contiguous span of postings upwards, so a
+// lane's postings ascend: its list is looked up again (a binary search over the lists above) only when
+// it passes the end of the one it is in, and the list's pointers stay in registers meanwhile.
+struct SegCursor {
+  int c = -1;
+  int64_t lo = 0, hi = 0;  // list c holds postings [lo, hi)
+  const uint64_t* kh = nullptr;
+  const uint8_t* kl = nullptr;
+};
+
+__device__ __forceinline__ void seg_seek(SegCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                         int nj, int64_t total, int64_t i) {
+  if (i < s.hi) return;
+  const int above = nj - s.c - 1;  // lists above c (i < total: one of them holds it)
+  s.c += 1 + seg_of(off + s.c + 1, 0, above - 1, i);
+  s.lo = off[s.c];
+  s.hi = s.c + 1 < nj ? off[s.c + 1] : total;
+  s.kh = jobs[s.c].khi;
+  s.kl = jobs[s.c].klo;
+}
+
+// the workgroup's span [begin, end) of the flattened postings: whole tiles, the same for every thread
+__device__ __forceinline__ void span_of(int64_t total, int64_t* begin, int64_t* end) {
+  const int64_t per = ((total + gridDim.x - 1) / gridDim.x + SPAN_TILE - 1) / SPAN_TILE * SPAN_TILE;
+  *begin = std::min<int64_t>((int64_t)blockIdx.x * per, total);
+  *end = std::min<int64_t>(*begin + per, total);
+}
+
+// One step of a thread over the keys: postings base + 256 u + thread (u < 4) below end -> their lists (-1: past
+// end), rows in the list and keys.  The four key loads are issued here, before the caller's first use of one.
+__device__ __forceinline__ void key_tile(SegCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                         int nj, int64_t total, int64_t base, int64_t end, int c[4], int64_t k[4],
+                                         uint64_t h[4], uint32_t l[4]) {
+#pragma unroll
+  for (int u = 0; u < 4; u++) {
+    const int64_t i = base + u * 256 + threadIdx.x;
+    c[u] = -1;
+    k[u] = 0;
+    h[u] = 0;
+    l[u] = 0;
+    if (i < end) {
+      seg_seek(s, jobs, off, nj, total, i);
+      c[u] = s.c;
+      k[u] = i - s.lo;
+      h[u] = s.kh[k[u]];
+      l[u] = s.kl[k[u]];
+    }
+  }
+}
+
+// cnt[key] += the wave's hits of that key: one atomic per distinct key.  Called by the whole wave; -> the hits.
+__device__ __forceinline__ uint32_t wave_add_by(bool hit, int key, unsigned long long* __restrict__ cnt) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t all = __ballot(hit);
+  uint64_t act = all;
+  while (act) {
+    const int lead = __ffsll((unsigned long long)act) - 1;
+    const int lk = __shfl(key, lead, 64);
+    const uint64_t same = __ballot(hit && key == lk);
+    if (lane == lead) atomicAdd(&cnt[lk], (unsigned long long)__popcll(same));
+    act &= ~same;
+  }
+  return (uint32_t)__popcll(all);
+}
+
+// The hits of a wave per list, where the lists of a wave's postings ascend (a streaming pass): the lanes of one
+// list are neighbours, so the wave sums a list's hits over its steps (c, n: the same in every lane) and adds
+// them once, on leaving the list: one atomic per list per wave.  add() is called by the whole wave.
+struct ListTally {
+  int c = -1;
+  uint32_t n = 0;
+  // this step's hits: the lane has one (hit) of list lc
+  __device__ __forceinline__ void add(bool hit, int lc, unsigned long long* cnt) {
+    uint64_t act = __ballot(hit);
+    while (act) {
+      const int lead = __ffsll((unsigned long long)act) - 1;
+      const int c1 = __shfl(lc, lead, 64);
+      const uint64_t same = __ballot(hit && lc == c1);
+      if (c1 != c) {
+        flush(cnt);
+        c = c1;
+        n = 0;
+      }
+      n += (uint32_t)__popcll(same);
+      act &= ~same;
+    }
+  }
+  __device__ __forceinline__ void flush(unsigned long long* cnt) const {
+    if (n && (threadIdx.x & 63) == 0) atomicAdd(&cnt[c], (unsigned long long)n);
+  }
+};
 
 // ---------------------------------------------------------------- add: sort keys
 __global__ void k_upd_key_a(const uint64_t* __restrict__ khi, const uint8_t* __restrict__ klo, int64_t n,
@@ -254,12 +397,6 @@ __global__ void k_upd_new(const UpdJob* __restrict__ jobs, const uint8_t* __rest
 }
 
 // ---------------------------------------------------------------- remove
-__device__ __forceinline__ bool in_set(const uint64_t* __restrict__ ukh, const uint8_t* __restrict__ ukl, int64_t nu,
-                                       uint64_t h, uint32_t l) {
-  const int64_t p = lb_key(ukh, ukl, 0, nu, h, l);
-  return p < nu && ukh[p] == h && (uint32_t)ukl[p] == l;
-}
-
 __global__ void k_rm_count(const RmJob* __restrict__ jobs, const int64_t* __restrict__ off, int nj, int64_t total,
                            const uint64_t* __restrict__ ukh, const uint8_t* __restrict__ ukl, int64_t nu,
                            unsigned long long* __restrict__ jrem) {
@@ -267,7 +404,7 @@ __global__ void k_rm_count(const RmJob* __restrict__ jobs, const int64_t* __rest
   if (i >= total) return;
   const int c = seg_of(off, 0, nj - 1, i);
   const int64_t k = i - off[c];
-  if (in_set(ukh, ukl, nu, jobs[c].khi[k], jobs[c].klo[k])) atomicAdd(&jrem[c], 1ull);
+  if (set_slot(ukh, ukl, nu, jobs[c].khi[k], jobs[c].klo[k]) >= 0) atomicAdd(&jrem[c], 1ull);
 }
 
 // keep[i] = posting i of the chunk's flattened lists stays; keep[total] = 0 (the scan's last element)
@@ -279,7 +416,7 @@ __global__ void k_rm_flag(const RmJob* __restrict__ jobs, const int64_t* __restr
   if (i >= total) return;
   const int c = seg_of(off, 0, nj - 1, i);
   const int64_t k = i - off[c];
-  keep[i] = in_set(ukh, ukl, nu, jobs[c].khi[k], jobs[c].klo[k]) ? 0 : 1;
+  keep[i] = set_slot(ukh, ukl, nu, jobs[c].khi[k], jobs[c].klo[k]) >= 0 ? 0 : 1;
 }
 
 __global__ __launch_bounds__(256) void k_rm_place(const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
@@ -303,78 +440,16 @@ __global__ __launch_bounds__(256) void k_rm_place(const RmJob* __restrict__ jobs
 
 // ---------------------------------------------------------------- hosts
 
-// slot of h in the ascending set hs[0, nh), -1: not in it
-__device__ __forceinline__ int host_slot(const uint64_t* __restrict__ hs, int nh, uint64_t h) {
-  int lo = 0, hi = nh;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (hs[mid] < h) lo = mid + 1; else hi = mid;
-  }
-  return lo < nh && hs[lo] == h ? lo : -1;
-}
-
-// A lane's place in the flattened lists.  A workgroup walks a contiguous span of postings upwards, so a
-// lane's postings ascend: its list is looked up again (a binary search over the lists above) only when
-// it passes the end of the one it is in, and the list's pointers stay in registers meanwhile.
-struct SegCursor {
-  int c = -1;
-  int64_t lo = 0, hi = 0;  // list c holds postings [lo, hi)
-  const uint64_t* kh = nullptr;
-  const uint8_t* kl = nullptr;
-};
-
-__device__ __forceinline__ void seg_seek(SegCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
-                                         int nj, int64_t total, int64_t i) {
-  if (i < s.hi) return;
-  const int above = nj - s.c - 1;  // lists above c (i < total: one of them holds it)
-  s.c += 1 + seg_of(off + s.c + 1, 0, above - 1, i);
-  s.lo = off[s.c];
-  s.hi = s.c + 1 < nj ? off[s.c + 1] : total;
-  s.kh = jobs[s.c].khi;
-  s.kl = jobs[s.c].klo;
-}
-
-constexpr int HOST_TILE = 1024;  // postings a workgroup takes per step: 4 per thread, their loads in flight together
-
-// the workgroup's span [begin, end) of the flattened postings: whole tiles, the same for every thread
-__device__ __forceinline__ void host_span(int64_t total, int64_t* begin, int64_t* end) {
-  const int64_t per = ((total + gridDim.x - 1) / gridDim.x + HOST_TILE - 1) / HOST_TILE * HOST_TILE;
-  *begin = std::min<int64_t>((int64_t)blockIdx.x * per, total);
-  *end = std::min<int64_t>(*begin + per, total);
-}
-
-// One step of a thread: postings base + 256 u + thread (u < 4) below end -> their host slots (-1: not of
-// the set, or past end) and lists.  The four key loads are issued before the first search.
-template <bool LDS>
+// a key tile -> its postings' host slots (-1: not of the set, or past end) and lists
 __device__ __forceinline__ void mark_tile(SegCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
                                           int nj, int64_t total, const uint64_t* hs, int nh, int64_t base, int64_t end,
                                           int slot[4], int c[4]) {
+  int64_t k[4];
   uint64_t h[4];
   uint32_t l[4];
-#pragma unroll
-  for (int u = 0; u < 4; u++) {
-    const int64_t i = base + u * 256 + threadIdx.x;
-    c[u] = -1;
-    h[u] = 0;
-    l[u] = 0;
-    if (i < end) {
-      seg_seek(s, jobs, off, nj, total, i);
-      c[u] = s.c;
-      h[u] = s.kh[i - s.lo];
-      l[u] = s.kl[i - s.lo];
-    }
-  }
+  key_tile(s, jobs, off, nj, total, base, end, c, k, h, l);
 #pragma unroll
   for (int u = 0; u < 4; u++) slot[u] = c[u] >= 0 ? host_slot(hs, nh, host36(h[u], l[u])) : -1;
-}
-
-// the host set into LDS (LDS = true: nh <= HOST_LDS_MAX), or left where it is
-template <bool LDS>
-__device__ __forceinline__ const uint64_t* stage_set(uint64_t* s_set, const uint64_t* __restrict__ hset, int nh) {
-  if (!LDS) return hset;
-  for (int i = threadIdx.x; i < nh; i += blockDim.x) s_set[i] = hset[i];
-  __syncthreads();
-  return s_set;
 }
 
 // Marking pass: jrem[c] += postings of list c whose host is in the set; COUNT: hcnt[slot] += postings of
@@ -388,37 +463,23 @@ __global__ __launch_bounds__(256) void k_host_mark(const RmJob* __restrict__ job
   __shared__ uint32_t s_cnt[LDS && COUNT ? HOST_LDS_MAX : 1];
   if (LDS && COUNT)
     for (int i = threadIdx.x; i < nh; i += blockDim.x) s_cnt[i] = 0;
-  const uint64_t* hs = stage_set<LDS>(s_set, hset, nh);
+  stage_set<LDS>(s_set, hset, nh);
+  const uint64_t* hs = LDS ? s_set : hset;
   const int lane = threadIdx.x & 63;
   int64_t begin, end;
-  host_span(total, &begin, &end);
+  span_of(total, &begin, &end);
   SegCursor cur;
-  int acc_c = -1;
-  uint32_t acc_n = 0;
-  for (int64_t base = begin; base < end; base += HOST_TILE) {
+  ListTally per_list;
+  for (int64_t base = begin; base < end; base += SPAN_TILE) {
     int slots[4], cs[4];
-    mark_tile<LDS>(cur, jobs, off, nj, total, hs, nh, base, end, slots, cs);
+    mark_tile(cur, jobs, off, nj, total, hs, nh, base, end, slots, cs);
 #pragma unroll
     for (int u = 0; u < 4; u++) {
-      const int slot = slots[u], c = cs[u];
+      const int slot = slots[u];
       const bool hit = slot >= 0;
-      // per list: the lanes of one list are neighbours and the wave's lists ascend, so the wave sums a
-      // list's hits over its steps (acc_c, acc_n: the same in every lane) and adds them once, on leaving it
-      uint64_t act = __ballot(hit);
-      while (act) {
-        const int lead = __ffsll((unsigned long long)act) - 1;
-        const int lc = __shfl(c, lead, 64);
-        const uint64_t same = __ballot(hit && c == lc);
-        if (lc != acc_c) {
-          if (acc_n && lane == 0) atomicAdd(&jrem[acc_c], (unsigned long long)acc_n);
-          acc_c = lc;
-          acc_n = 0;
-        }
-        acc_n += (uint32_t)__popcll(same);
-        act &= ~same;
-      }
+      per_list.add(hit, cs[u], jrem);
       if (COUNT) {
-        act = __ballot(hit);
+        const uint64_t act = __ballot(hit);
         if (LDS) {
           // one host owns the wave's hits (a hot spot): one LDS add; else one per lane, spread over the slots
           const int lead = act ? __ffsll((unsigned long long)act) - 1 : 0;
@@ -429,18 +490,12 @@ __global__ __launch_bounds__(256) void k_host_mark(const RmJob* __restrict__ job
             atomicAdd(&s_cnt[slot], 1u);
           }
         } else {
-          while (act) {  // equal slots aggregated within the wave
-            const int lead = __ffsll((unsigned long long)act) - 1;
-            const int ls = __shfl(slot, lead, 64);
-            const uint64_t same = __ballot(hit && slot == ls);
-            if (lane == lead) atomicAdd(&hcnt[ls], (unsigned long long)__popcll(same));
-            act &= ~same;
-          }
+          wave_add_by(hit, slot, hcnt);
         }
       }
     }
   }
-  if (acc_n && lane == 0) atomicAdd(&jrem[acc_c], (unsigned long long)acc_n);
+  per_list.flush(jrem);
   if (LDS && COUNT) {  // one global atomic per hit slot per workgroup
     __syncthreads();
     for (int i = threadIdx.x; i < nh; i += blockDim.x)
@@ -454,22 +509,20 @@ __global__ __launch_bounds__(256) void k_host_flag(const RmJob* __restrict__ job
                                                    int nj, int64_t total, const uint64_t* __restrict__ hset, int nh,
                                                    int32_t* __restrict__ keep) {
   __shared__ uint64_t s_set[LDS ? HOST_LDS_MAX : 1];
-  const uint64_t* hs = stage_set<LDS>(s_set, hset, nh);
+  stage_set<LDS>(s_set, hset, nh);
+  const uint64_t* hs = LDS ? s_set : hset;
   if (blockIdx.x == 0 && threadIdx.x == 0) keep[total] = 0;
   int64_t begin, end;
-  host_span(total, &begin, &end);
+  span_of(total, &begin, &end);
   SegCursor cur;
-  for (int64_t base = begin; base < end; base += HOST_TILE) {
+  for (int64_t base = begin; base < end; base += SPAN_TILE) {
     int slots[4], cs[4];
-    mark_tile<LDS>(cur, jobs, off, nj, total, hs, nh, base, end, slots, cs);
+    mark_tile(cur, jobs, off, nj, total, hs, nh, base, end, slots, cs);
 #pragma unroll
     for (int u = 0; u < 4; u++)
       if (cs[u] >= 0) keep[base + u * 256 + threadIdx.x] = slots[u] < 0;
   }
 }
-
-unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // what the call enqueued (kernels, device-library calls, copies, memsets) and waited for
 struct Tally {
@@ -523,6 +576,79 @@ void rm_table(const ListSel& sel, RmTable* t) {
     t->off.push_back(t->total);
     t->total += R.n;
   }
+}
+
+// ---- the frame of a marking pass: what the maintenance calls do around the launches of their first pass
+struct PassDev {  // the device view of an RmTable, and the pass's result words
+  RmJob* jobs = nullptr;
+  int64_t* off = nullptr;
+  unsigned long long* res = nullptr;
+};
+
+inline bool pass_tables(Lane*, UpEnt*, int&) { return true; }
+template <class T, class... R>
+bool pass_tables(Lane* L, UpEnt* e, int& n, T** dst, const std::vector<T>& v, R&&... rest) {
+  *dst = arena_alloc<T>(L, (int64_t)v.size());
+  e[n++] = UpEnt{*dst, v.data(), v.size() * sizeof(T)};
+  return *dst && pass_tables(L, e, n, std::forward<R>(rest)...);
+}
+
+// The begin of a pass on lane L (a new pass): the list table, the caller's tables (extra: pairs of where the
+// device pointer goes and the host vector) and a result block of zero_bytes (0: none) take their place in the
+// arena; one upload brings every table, one memset zeroes the block.  One sync; one or two launches.
+template <class... Extra>
+int pass_begin(yrwi_ctx* ctx, Lane* L, const RmTable& t, size_t zero_bytes, const char* nomem, PassDev* D, Tally* T,
+               Extra&&... extra) {
+  if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
+  T->syncs++;
+  UpEnt e[2 + sizeof...(Extra) / 2];
+  int n = 0;
+  bool ok = pass_tables(L, e, n, std::forward<Extra>(extra)..., &D->jobs, t.jobs, &D->off, t.off);
+  if (zero_bytes) D->res = reinterpret_cast<unsigned long long*>(L->arena.alloc(zero_bytes));
+  if (!ok || (zero_bytes && !D->res)) return ctx->fail(YRWI_E_NOMEM, nomem);
+  if (int rc = upload_list(L, e, n)) return ctx->take(L, rc);  // (one copy kernel)
+  T->launches++;
+  if (zero_bytes) {
+    HIPCHK(ctx, hipMemsetAsync(D->res, 0, zero_bytes, L->stream));
+    T->launches++;
+  }
+  return 0;
+}
+
+// The end of a pass: the first nres result words read back once and waited for.  *h: the words in the pinned
+// landing buffer, good until the lane's next read-back; a caller that needs them longer copies them.  One
+// launch, one sync.
+int pass_end(yrwi_ctx* ctx, Lane* L, const PassDev& D, int64_t nres, const int64_t** h, Tally* T) {
+  *h = reinterpret_cast<const int64_t*>(readback(L, &L->down_stage, D.res, nres, 8, 8));
+  if (!*h) return ctx->take(L, YRWI_E_HIP);
+  T->launches++;
+  HIPCHK(ctx, lane_sync(L));
+  T->syncs++;
+  return 0;
+}
+
+// The url hashes of a call as keys: as given, and as the set the kernels search, sorted and each once, in the
+// device's two arrays.  YRWI_E_HASH for one that is not well formed.
+struct UrlSet {
+  std::vector<KeyT> in, uk;
+  std::vector<uint64_t> kh;
+  std::vector<uint8_t> kl;
+};
+
+int url_set(yrwi_ctx* ctx, const uint8_t* urls12, int64_t nurls, UrlSet* U) {
+  U->in.resize((size_t)nurls);
+  for (int64_t i = 0; i < nurls; i++)
+    if (!key_of(urls12 + i * 12, &U->in[(size_t)i])) return ctx->fail(YRWI_E_HASH, "url hash is not well-formed Base64");
+  U->uk = U->in;
+  std::sort(U->uk.begin(), U->uk.end());
+  U->uk.erase(std::unique(U->uk.begin(), U->uk.end()), U->uk.end());
+  U->kh.resize(U->uk.size());
+  U->kl.resize(U->uk.size());
+  for (size_t i = 0; i < U->uk.size(); i++) {
+    U->kh[i] = U->uk[i].hi;
+    U->kl[i] = (uint8_t)U->uk[i].lo;
+  }
+  return 0;
 }
 
 // rows compacted at a time: YRWI_RM_CHUNK, read per call (tests force chunk boundaries with it)
@@ -814,46 +940,28 @@ extern "C" int yrwi_remove_postings(yrwi_ctx* ctx, const uint8_t* terms12, int32
   Tally T;
   if (st) std::memset(st, 0, sizeof(*st));
   // ---- the url set, sorted and deduplicated; the named lists, each once
-  std::vector<KeyT> uk((size_t)nurls);
-  for (int64_t i = 0; i < nurls; i++)
-    if (!key_of(urls12 + i * 12, &uk[(size_t)i])) return ctx->fail(YRWI_E_HASH, "url hash is not well-formed Base64");
-  std::sort(uk.begin(), uk.end());
-  uk.erase(std::unique(uk.begin(), uk.end()), uk.end());
+  UrlSet U;
+  if (int rc = url_set(ctx, urls12, nurls, &U)) return rc;
   ListSel sel;
   if (int rc = select_lists(ctx, terms12, nterms, false, &sel)) return rc;
   RmTable t;
   rm_table(sel, &t);
-  const std::vector<RmJob>& jobs = t.jobs;
-  const int64_t total = t.total;
-  if (uk.empty() || jobs.empty()) return 0;
+  if (U.uk.empty() || t.jobs.empty()) return 0;
   Lane* L = ctx->lanes[0];
-  if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
-  T.syncs++;
-  const int nj = (int)jobs.size();
-  const int64_t nu = (int64_t)uk.size();
-  std::vector<uint64_t> h_ukh((size_t)nu);
-  std::vector<uint8_t> h_ukl((size_t)nu);
-  for (int64_t i = 0; i < nu; i++) {
-    h_ukh[(size_t)i] = uk[(size_t)i].hi;
-    h_ukl[(size_t)i] = (uint8_t)uk[(size_t)i].lo;
-  }
-  uint64_t* ukh = arena_alloc<uint64_t>(L, nu);
-  uint8_t* ukl = arena_alloc<uint8_t>(L, nu);
-  RmJob* d_jobs = arena_alloc<RmJob>(L, nj);
-  int64_t* d_off = arena_alloc<int64_t>(L, nj);
-  unsigned long long* jrem = arena_alloc<unsigned long long>(L, nj);
-  if (!ukh || !ukl || !d_jobs || !d_off || !jrem) return ctx->fail(YRWI_E_NOMEM, "device allocation (remove_postings)");
+  const int nj = (int)t.jobs.size();
+  const int64_t nu = (int64_t)U.uk.size();
   // ---- one marking pass over the named lists' keys, the per-list counts read back once
-  if (int rc = upload(L, ukh, h_ukh, ukl, h_ukl, d_jobs, jobs, d_off, t.off)) return ctx->take(L, rc);
-  HIPCHK(ctx, hipMemsetAsync(jrem, 0, (size_t)nj * 8, L->stream));
-  hipLaunchKernelGGL(k_rm_count, dim3(blocks(total)), dim3(256), 0, L->stream, d_jobs, d_off, nj, total, ukh, ukl, nu,
-                     jrem);
+  PassDev D;
+  uint64_t* ukh = nullptr;
+  uint8_t* ukl = nullptr;
+  if (int rc = pass_begin(ctx, L, t, (size_t)nj * 8, "device allocation (remove_postings)", &D, &T, &ukh, U.kh, &ukl, U.kl))
+    return rc;
+  hipLaunchKernelGGL(k_rm_count, dim3(blocks(t.total)), dim3(256), 0, L->stream, D.jobs, D.off, nj, t.total, ukh, ukl,
+                     nu, D.res);
   HIPCHK(ctx, hipGetLastError());
-  const int64_t* hrem = reinterpret_cast<const int64_t*>(readback(L, &L->down_stage, jrem, nj, 8, 8));
-  if (!hrem) return ctx->take(L, YRWI_E_HIP);
-  T.launches += 4;
-  HIPCHK(ctx, lane_sync(L));
-  T.syncs++;
+  T.launches++;
+  const int64_t* hrem = nullptr;
+  if (int rc = pass_end(ctx, L, D, nj, &hrem, &T)) return rc;
   // ---- compaction of only the lists that lost rows, and the bookkeeping
   const std::vector<int64_t> rem(hrem, hrem + nj);  // (the pinned landing buffer may be reused)
   auto flag = [&](const RmJob* dj, const int64_t* doff, int ncj, int64_t n, int32_t* keep, const ChunkAux&) {
@@ -872,8 +980,6 @@ struct HostPass : RmTable {
   std::vector<uint64_t> in;  // the 36-bit key of every host given, in the caller's order
   std::vector<uint64_t> hk;  // the set: sorted, each once
   uint64_t* d_hk = nullptr;
-  RmJob* d_jobs = nullptr;
-  int64_t* d_off = nullptr;
   std::vector<int64_t> res;  // after host_mark: hits per selected list, then (count) postings per set slot
 };
 
@@ -899,38 +1005,28 @@ int host_select(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uin
   return 0;
 }
 
-unsigned mark_blocks(int64_t n) { return (unsigned)std::min<int64_t>((n + HOST_TILE - 1) / HOST_TILE, HOST_MARK_BLOCKS); }
-
 // The marking pass on lane L (a new pass): the set and the list table uploaded once, one launch over
 // the flattened keys, one read-back, one wait.  4 launches, 2 syncs, whatever was selected or given.
 int host_mark(yrwi_ctx* ctx, Lane* L, HostPass* P, bool count, Tally* T) {
-  if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
-  T->syncs++;
   const int nj = (int)P->jobs.size(), nh = (int)P->hk.size();
   const int64_t nres = (int64_t)nj + (count ? nh : 0);
-  P->d_hk = arena_alloc<uint64_t>(L, nh);
-  P->d_jobs = arena_alloc<RmJob>(L, nj);
-  P->d_off = arena_alloc<int64_t>(L, nj);
-  unsigned long long* res = arena_alloc<unsigned long long>(L, nres);
-  if (!P->d_hk || !P->d_jobs || !P->d_off || !res) return ctx->fail(YRWI_E_NOMEM, "device allocation (host marking pass)");
-  if (int rc = upload(L, P->d_hk, P->hk, P->d_jobs, P->jobs, P->d_off, P->off)) return ctx->take(L, rc);
-  HIPCHK(ctx, hipMemsetAsync(res, 0, (size_t)nres * 8, L->stream));
-  const dim3 g(mark_blocks(P->total)), b(256);
+  PassDev D;
+  if (int rc = pass_begin(ctx, L, *P, (size_t)nres * 8, "device allocation (host marking pass)", &D, T, &P->d_hk, P->hk))
+    return rc;
+  const dim3 g(span_blocks(P->total)), b(256);
   const bool lds = nh <= HOST_LDS_MAX;
   if (lds && count)
-    hipLaunchKernelGGL((k_host_mark<true, true>), g, b, 0, L->stream, P->d_jobs, P->d_off, nj, P->total, P->d_hk, nh, res, res + nj);
+    hipLaunchKernelGGL((k_host_mark<true, true>), g, b, 0, L->stream, D.jobs, D.off, nj, P->total, P->d_hk, nh, D.res, D.res + nj);
   else if (lds)
-    hipLaunchKernelGGL((k_host_mark<true, false>), g, b, 0, L->stream, P->d_jobs, P->d_off, nj, P->total, P->d_hk, nh, res, res + nj);
+    hipLaunchKernelGGL((k_host_mark<true, false>), g, b, 0, L->stream, D.jobs, D.off, nj, P->total, P->d_hk, nh, D.res, D.res + nj);
   else if (count)
-    hipLaunchKernelGGL((k_host_mark<false, true>), g, b, 0, L->stream, P->d_jobs, P->d_off, nj, P->total, P->d_hk, nh, res, res + nj);
+    hipLaunchKernelGGL((k_host_mark<false, true>), g, b, 0, L->stream, D.jobs, D.off, nj, P->total, P->d_hk, nh, D.res, D.res + nj);
   else
-    hipLaunchKernelGGL((k_host_mark<false, false>), g, b, 0, L->stream, P->d_jobs, P->d_off, nj, P->total, P->d_hk, nh, res, res + nj);
+    hipLaunchKernelGGL((k_host_mark<false, false>), g, b, 0, L->stream, D.jobs, D.off, nj, P->total, P->d_hk, nh, D.res, D.res + nj);
   HIPCHK(ctx, hipGetLastError());
-  const int64_t* h = reinterpret_cast<const int64_t*>(readback(L, &L->down_stage, res, nres, 8, 8));
-  if (!h) return ctx->take(L, YRWI_E_HIP);
-  T->launches += 4;
-  HIPCHK(ctx, lane_sync(L));
-  T->syncs++;
+  T->launches++;
+  const int64_t* h = nullptr;
+  if (int rc = pass_end(ctx, L, D, nres, &h, T)) return rc;
   P->res.assign(h, h + nres);  // (the pinned landing buffer may be reused)
   return 0;
 }
@@ -973,9 +1069,9 @@ extern "C" int yrwi_remove_hosts(yrwi_ctx* ctx, const uint8_t* terms12, int32_t 
   const int nh = (int)P.hk.size();
   auto flag = [&](const RmJob* dj, const int64_t* doff, int ncj, int64_t n, int32_t* keep, const ChunkAux&) {
     if (nh <= HOST_LDS_MAX)
-      hipLaunchKernelGGL((k_host_flag<true>), dim3(mark_blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, P.d_hk, nh, keep);
+      hipLaunchKernelGGL((k_host_flag<true>), dim3(span_blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, P.d_hk, nh, keep);
     else
-      hipLaunchKernelGGL((k_host_flag<false>), dim3(mark_blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, P.d_hk, nh, keep);
+      hipLaunchKernelGGL((k_host_flag<false>), dim3(span_blocks(n)), dim3(256), 0, L->stream, dj, doff, ncj, n, P.d_hk, nh, keep);
   };
   if (int rc = compact_commit(ctx, L, P, P.res, "device allocation (remove_hosts compaction)", flag, &S, &T)) return rc;
   put_stats(st, S, T);
@@ -1029,27 +1125,16 @@ __device__ __forceinline__ bool census_lds_add(unsigned long long* lk, uint32_t*
   return false;
 }
 
-// One step of a thread, as mark_tile's loads: postings base + 256 u + thread (u < 4) below end -> host36 + 1
-// (0: past end).  The four key loads are issued before the first use.
+// a key tile -> its postings' host36 + 1 (0: past end, told by the posting's number: the census needs no list)
 __device__ __forceinline__ void census_tile(SegCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
                                             int nj, int64_t total, int64_t base, int64_t end, uint64_t key1[4]) {
+  int c[4];
+  int64_t k[4];
   uint64_t h[4];
   uint32_t l[4];
-  bool live[4];
+  key_tile(s, jobs, off, nj, total, base, end, c, k, h, l);
 #pragma unroll
-  for (int u = 0; u < 4; u++) {
-    const int64_t i = base + u * 256 + threadIdx.x;
-    live[u] = i < end;
-    h[u] = 0;
-    l[u] = 0;
-    if (live[u]) {
-      seg_seek(s, jobs, off, nj, total, i);
-      h[u] = s.kh[i - s.lo];
-      l[u] = s.kl[i - s.lo];
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < 4; u++) key1[u] = live[u] ? host36(h[u], l[u]) + 1 : 0;
+  for (int u = 0; u < 4; u++) key1[u] = base + u * 256 + threadIdx.x < end ? host36(h[u], l[u]) + 1 : 0;
 }
 
 // Counting pass: a group-by of the selected postings on their host.  Grid and spans as k_host_mark.  Every
@@ -1072,10 +1157,10 @@ __global__ __launch_bounds__(256) void k_census(const RmJob* __restrict__ jobs, 
   const uint32_t smask = (uint32_t)S - 1;
   const int lane = threadIdx.x & 63;
   int64_t begin, end;
-  host_span(total, &begin, &end);
+  span_of(total, &begin, &end);
   SegCursor cur;
   unsigned long long bypass = 0;  // the same in every lane of the wave
-  for (int64_t base = begin; base < end; base += HOST_TILE) {
+  for (int64_t base = begin; base < end; base += SPAN_TILE) {
     // the pass has overflowed and will be run again: the wave leaves (no barrier waits for it in here)
     if (__any(__hip_atomic_load(&ctr[CEN_OVERFLOW], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) break;
     uint64_t keys[4];
@@ -1093,7 +1178,7 @@ __global__ __launch_bounds__(256) void k_census(const RmJob* __restrict__ jobs, 
       bool pend = false;  // this lane's postings found no place in LDS
       if (uni ? (act && lane == lead) : live) pend = !census_lds_add(lk, lc, smask, key1, n);
       uint64_t left = __ballot(pend);
-      while (left) {  // equal keys aggregated within the wave
+      while (left) {  // equal keys aggregated within the wave (wave_add_by, over 64-bit keys into a hash table)
         const int pl = __ffsll((unsigned long long)left) - 1;
         const uint64_t pk = shfl64(key1, pl);
         const uint64_t same = __ballot(pend && key1 == pk);
@@ -1167,8 +1252,10 @@ extern "C" int yrwi_host_census(yrwi_ctx* ctx, const uint8_t* terms12, int32_t n
   yrwi_census_stats S;
   std::memset(&S, 0, sizeof(S));
   Tally T;
-  HostPass P;
-  if (int rc = host_select(ctx, terms12, nterms, nullptr, 0, &P)) return rc;
+  ListSel sel;
+  if (int rc = select_lists(ctx, terms12, nterms, false, &sel)) return rc;
+  RmTable t;
+  rm_table(sel, &t);
   auto finish = [&](int64_t n) {
     S.launches = T.launches;
     S.syncs = T.syncs;
@@ -1178,20 +1265,15 @@ extern "C" int yrwi_host_census(yrwi_ctx* ctx, const uint8_t* terms12, int32_t n
     if (st) *st = S;
     return 0;
   };
-  if (P.jobs.empty()) return finish(0);
-  const int nj = (int)P.jobs.size();
-  const int64_t total = P.total;
+  if (t.jobs.empty()) return finish(0);
+  const int nj = (int)t.jobs.size();
+  const int64_t total = t.total;
   const unsigned long long minp = (unsigned long long)std::max<int64_t>(min_postings, 1);
   S.lists = nj;
   S.postings = total;
   Lane* L = ctx->lanes[0];
-  if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
-  T.syncs++;
-  P.d_jobs = arena_alloc<RmJob>(L, nj);
-  P.d_off = arena_alloc<int64_t>(L, nj);
-  if (!P.d_jobs || !P.d_off) return ctx->fail(YRWI_E_NOMEM, "device allocation (host census)");
-  if (int rc = upload(L, P.d_jobs, P.jobs, P.d_off, P.off)) return ctx->take(L, rc);
-  T.launches++;
+  PassDev D;  // (the list table alone: every counting pass has a result block of its own)
+  if (int rc = pass_begin(ctx, L, t, 0, "device allocation (host census)", &D, &T)) return rc;
   // ---- counting passes: the table sized and zeroed, one launch over the flattened keys, the table's
   //      hosts flagged and scanned, the four counters read back; on overflow again with four times the slots
   const int lds = (int)census_knob("YRWI_CENSUS_LDS_SLOTS", CENSUS_LDS_DEFAULT, 64, 4096);
@@ -1217,7 +1299,7 @@ extern "C" int yrwi_host_census(yrwi_ctx* ctx, const uint8_t* terms12, int32_t n
     HIPCHK(ctx, hipMemsetAsync(blk, 0, (size_t)(CEN_WORDS + 2 * slots) * 8, L->stream));
     hipEvent_t e0 = L->event(), e1 = L->event();
     HIPCHK(ctx, hipEventRecord(e0, L->stream));
-    hipLaunchKernelGGL(k_census, dim3(mark_blocks(total)), dim3(256), (size_t)lds * 12, L->stream, P.d_jobs, P.d_off, nj,
+    hipLaunchKernelGGL(k_census, dim3(span_blocks(total)), dim3(256), (size_t)lds * 12, L->stream, D.jobs, D.off, nj,
                        total, lds, tab, (uint64_t)(slots - 1), d_ctr);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(e1, L->stream));
@@ -1303,36 +1385,38 @@ enum { RET_MINV = 0, RET_MAX1 = 1, RET_BYPASS = 2, RET_WORDS = 3 };
 // a lane's place in the flattened lists and its list's rows
 struct DayCursor : SegCursor {
   const uint8_t* rows = nullptr;
-  bool moved = false;  // the last seek entered another list
 };
 
-__device__ __forceinline__ void day_seek(DayCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+// -> the lane entered another list
+__device__ __forceinline__ bool day_seek(DayCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
                                          int nj, int64_t total, int64_t i) {
-  s.moved = i >= s.hi;
-  if (!s.moved) return;
+  if (i < s.hi) return false;
   seg_seek(s, jobs, off, nj, total, i);
   s.rows = jobs[s.c].rows;
+  return true;
 }
 
-// One step of a thread: postings base + 256 u + thread (u < 4) below end -> their a cells and lists (-1: past
-// end).  The four loads are issued before the first use.
+// One step of a thread over the rows, key_tile's counterpart: postings base + 256 u + thread (u < 4) below end ->
+// their a cells and lists (-1: past end).  The four loads are issued before the first use.  at(u, entered) is
+// called for every posting below end with the cursor at it, entered: in another list than the lane's last.
+template <class At>
 __device__ __forceinline__ void day_tile(DayCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
-                                         int nj, int64_t total, int64_t base, int64_t end, int a[4], int c[4]) {
+                                         int nj, int64_t total, int64_t base, int64_t end, int a[4], int c[4], At at) {
 #pragma unroll
   for (int u = 0; u < 4; u++) {
     const int64_t i = base + u * 256 + threadIdx.x;
     c[u] = -1;
     a[u] = -1;
     if (i < end) {
-      day_seek(s, jobs, off, nj, total, i);
+      at(u, day_seek(s, jobs, off, nj, total, i));
       c[u] = s.c;
       a[u] = (int)row_lm(s.rows + (i - s.lo) * YRWI_ROW_BYTES);
     }
   }
 }
 
-// Age pass: jage[c] += postings of list c with a < min_day (summed in the wave per list as k_host_mark sums
-// jrem); ctr[RET_MINV] = max(65536 - a), ctr[RET_MAX1] = max(a + 1) (0: no posting; one atomic each per wave);
+// Age pass: jage[c] += postings of list c with a < min_day (summed in the wave per list: ListTally);
+// ctr[RET_MINV] = max(65536 - a), ctr[RET_MAX1] = max(a + 1) (0: no posting; one atomic each per wave);
 // HIST: hist[d] += postings with a == d, through the workgroup's LDS window.  Every wave of a workgroup runs
 // every step whole (the ballots).
 template <bool HIST>
@@ -1345,7 +1429,7 @@ __global__ __launch_bounds__(256) void k_ret_mark(const RmJob* __restrict__ jobs
   __shared__ int s_lo;
   const int lane = threadIdx.x & 63;
   int64_t begin, end;
-  host_span(total, &begin, &end);
+  span_of(total, &begin, &end);
   if (HIST) {
     for (int i = threadIdx.x; i < RET_WIN; i += blockDim.x) s_win[i] = 0;
     if (threadIdx.x == 0) {
@@ -1360,13 +1444,12 @@ __global__ __launch_bounds__(256) void k_ret_mark(const RmJob* __restrict__ jobs
   }
   const int wlo = HIST ? s_lo : 0;
   DayCursor cur;
-  int acc_c = -1;
-  uint32_t acc_n = 0;
+  ListTally per_list;
   int mn = RET_DAYS, mx = -1;
   unsigned long long bypass = 0;  // the same in every lane of the wave
-  for (int64_t base = begin; base < end; base += HOST_TILE) {
+  for (int64_t base = begin; base < end; base += SPAN_TILE) {
     int as[4], cs[4];
-    day_tile(cur, jobs, off, nj, total, base, end, as, cs);
+    day_tile(cur, jobs, off, nj, total, base, end, as, cs, [](int, bool) {});
 #pragma unroll
     for (int u = 0; u < 4; u++) {
       const int a = as[u], c = cs[u];
@@ -1376,21 +1459,9 @@ __global__ __launch_bounds__(256) void k_ret_mark(const RmJob* __restrict__ jobs
         mn = std::min(mn, a);
         mx = std::max(mx, a);
       }
-      uint64_t act = __ballot(hit);
-      while (act) {
-        const int lead = __ffsll((unsigned long long)act) - 1;
-        const int lc = __shfl(c, lead, 64);
-        const uint64_t same = __ballot(hit && c == lc);
-        if (lc != acc_c) {
-          if (acc_n && lane == 0) atomicAdd(&jage[acc_c], (unsigned long long)acc_n);
-          acc_c = lc;
-          acc_n = 0;
-        }
-        acc_n += (uint32_t)__popcll(same);
-        act &= ~same;
-      }
+      per_list.add(hit, c, jage);
       if (HIST) {
-        act = __ballot(live);
+        const uint64_t act = __ballot(live);
         // one day owns the wave's postings (lists written in one crawl): one add; else one per lane
         const int lead = act ? __ffsll((unsigned long long)act) - 1 : 0;
         const int la = __shfl(a, lead, 64);
@@ -1406,20 +1477,12 @@ __global__ __launch_bounds__(256) void k_ret_mark(const RmJob* __restrict__ jobs
           if (!lin) bypass += (unsigned long long)__popcll(act);
         } else {
           if (inwin) atomicAdd(&s_win[a - wlo], 1u);
-          uint64_t left = __ballot(live && !inwin);
-          while (left) {  // equal days aggregated within the wave
-            const int pl = __ffsll((unsigned long long)left) - 1;
-            const int pa = __shfl(a, pl, 64);
-            const uint64_t same = __ballot(live && !inwin && a == pa);
-            if (lane == pl) atomicAdd(&hist[pa], (unsigned long long)__popcll(same));
-            bypass += (unsigned long long)__popcll(same);
-            left &= ~same;
-          }
+          bypass += wave_add_by(live && !inwin, a, hist);  // equal days aggregated within the wave
         }
       }
     }
   }
-  if (acc_n && lane == 0) atomicAdd(&jage[acc_c], (unsigned long long)acc_n);
+  per_list.flush(jage);
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) {
     mn = std::min(mn, __shfl_xor(mn, d, 64));
@@ -1466,38 +1529,24 @@ __global__ __launch_bounds__(256) void k_ret_bins(const RmJob* __restrict__ jobs
     __builtin_amdgcn_wave_barrier();
   };
   int64_t begin, end;
-  host_span(total, &begin, &end);
+  span_of(total, &begin, &end);
   DayCursor cur;
   int b1 = 0;
-  for (int64_t base = begin; base < end; base += HOST_TILE) {
-    int as[4], cs[4], bk[4];
-    if (LEVEL == 1) {
-      day_tile(cur, jobs, off, nj, total, base, end, as, cs);
-#pragma unroll
-      for (int u = 0; u < 4; u++) bk[u] = 0;
-    } else {
-#pragma unroll
-      for (int u = 0; u < 4; u++) {  // (day_tile, with the list's bucket looked up where the lane enters a list)
-        const int64_t i = base + u * 256 + threadIdx.x;
-        cs[u] = -1;
-        as[u] = -1;
-        bk[u] = 0;
-        if (i < end) {
-          day_seek(cur, jobs, off, nj, total, i);
-          if (cur.moved) b1 = pick[2 * (int64_t)cur.c];
-          cs[u] = cur.c;
-          bk[u] = b1;
-          as[u] = (int)row_lm(cur.rows + (i - cur.lo) * YRWI_ROW_BYTES);
-        }
+  for (int64_t base = begin; base < end; base += SPAN_TILE) {
+    int as[4], cs[4], bk[4] = {0, 0, 0, 0};
+    day_tile(cur, jobs, off, nj, total, base, end, as, cs, [&](int u, bool entered) {
+      if (LEVEL == 2) {  // the list's bucket, looked up where the lane enters a list
+        if (entered) b1 = pick[2 * (int64_t)cur.c];
+        bk[u] = b1;
       }
-    }
+    });
 #pragma unroll
     for (int u = 0; u < 4; u++) {
       const int a = as[u], c = cs[u];
       const bool in = c >= 0 && a >= min_day && (LEVEL == 1 || (a >> 8) == bk[u]);
       const int b = (LEVEL == 1 ? a >> 8 : a) & 255;
       uint64_t left = __ballot(in);
-      while (left) {  // the wave's lists ascend: list by list
+      while (left) {  // the wave's lists ascend: list by list, as ListTally::add, with bins to flush for a count
         const int pl = __ffsll((unsigned long long)left) - 1;
         const int lc = __shfl(c, pl, 64);
         const bool mine = in && c == lc;
@@ -1559,17 +1608,17 @@ __global__ __launch_bounds__(256) void k_ret_flag(const RmJob* __restrict__ jobs
                                                   int32_t* __restrict__ out) {
   if (blockIdx.x == 0 && threadIdx.x == 0) out[total] = 0;
   int64_t begin, end;
-  host_span(total, &begin, &end);
+  span_of(total, &begin, &end);
   DayCursor cur;
   int2 dq = make_int2(-1, 0);
   int64_t tbase = 0;
-  for (int64_t base = begin; base < end; base += HOST_TILE) {
+  for (int64_t base = begin; base < end; base += SPAN_TILE) {
 #pragma unroll
-    for (int u = 0; u < 4; u++) {
+    for (int u = 0; u < 4; u++) {  // (not day_tile: a posting's flag is stored before the next one's cell is loaded)
       const int64_t i = base + u * 256 + threadIdx.x;
       if (i >= end) continue;
-      day_seek(cur, jobs, off, nj, total, i);
-      if (MODE != 0 && cur.moved) {
+      const bool entered = day_seek(cur, jobs, off, nj, total, i);
+      if (MODE != 0 && entered) {
         dq = cut[sel[cur.c]];
         if (MODE == 2) tbase = tx[cur.lo];
       }
@@ -1621,33 +1670,25 @@ int retention(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, int32_t min
   const int64_t total = t.total;
   const bool hist = day_hist != nullptr;
   Lane* L = ctx->lanes[0];
-  if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
-  T.syncs++;
   // ---- the age pass: per-list counts, the day range, the bypass count and the histogram in one block, read back once
   const int64_t nres = (int64_t)nj + RET_WORDS + (hist ? RET_DAYS : 0);
-  RmJob* d_jobs = arena_alloc<RmJob>(L, nj);
-  int64_t* d_off = arena_alloc<int64_t>(L, nj);
-  unsigned long long* res = arena_alloc<unsigned long long>(L, nres);
-  if (!d_jobs || !d_off || !res) return ctx->fail(YRWI_E_NOMEM, "device allocation (retention age pass)");
-  if (int rc = upload(L, d_jobs, t.jobs, d_off, t.off)) return ctx->take(L, rc);
-  HIPCHK(ctx, hipMemsetAsync(res, 0, (size_t)nres * 8, L->stream));
+  PassDev D;
+  if (int rc = pass_begin(ctx, L, t, (size_t)nres * 8, "device allocation (retention age pass)", &D, &T)) return rc;
   hipEvent_t e0 = L->event(), e1 = L->event(), e2 = L->event(), e3 = L->event();
   HIPCHK(ctx, hipEventRecord(e0, L->stream));
   {
-    const dim3 g(mark_blocks(total)), b(256);
-    unsigned long long* ctr = res + nj;
+    const dim3 g(span_blocks(total)), b(256);
+    unsigned long long* ctr = D.res + nj;
     if (hist)
-      hipLaunchKernelGGL((k_ret_mark<true>), g, b, 0, L->stream, d_jobs, d_off, nj, total, min_day, res, ctr, ctr + RET_WORDS);
+      hipLaunchKernelGGL((k_ret_mark<true>), g, b, 0, L->stream, D.jobs, D.off, nj, total, min_day, D.res, ctr, ctr + RET_WORDS);
     else
-      hipLaunchKernelGGL((k_ret_mark<false>), g, b, 0, L->stream, d_jobs, d_off, nj, total, min_day, res, ctr, ctr + RET_WORDS);
+      hipLaunchKernelGGL((k_ret_mark<false>), g, b, 0, L->stream, D.jobs, D.off, nj, total, min_day, D.res, ctr, ctr + RET_WORDS);
   }
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipEventRecord(e1, L->stream));
-  const int64_t* h = reinterpret_cast<const int64_t*>(readback(L, &L->down_stage, res, nres, 8, 8));
-  if (!h) return ctx->take(L, YRWI_E_HIP);
-  T.launches += 4;
-  HIPCHK(ctx, lane_sync(L));
-  T.syncs++;
+  T.launches++;
+  const int64_t* h = nullptr;
+  if (int rc = pass_end(ctx, L, D, nres, &h, &T)) return rc;
   float msf = 0.f;
   if (hipEventElapsedTime(&msf, e0, e1) == hipSuccess) R.t_mark_ns = (int64_t)((double)msf * 1e6);
   // ---- every list's final length: rem = age + max(0, n - age - max_refs)
@@ -1697,7 +1738,7 @@ int retention(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, int32_t min
     HIPCHK(ctx, hipMemsetAsync(bins, 0, (size_t)nb * 4, L->stream));
     HIPCHK(ctx, hipMemsetAsync(cut, 0xFF, (size_t)nj * sizeof(int2), L->stream));  // d* = -1: no cut
     HIPCHK(ctx, hipEventRecord(e2, L->stream));
-    const dim3 g(std::max(mark_blocks(ctotal), 1u)), gp(std::max(blocks(ncap), 1u)), b(256);
+    const dim3 g(std::max(span_blocks(ctotal), 1u)), gp(std::max(blocks(ncap), 1u)), b(256);
     const int32_t K = (int32_t)std::min<int64_t>(max_refs, INT32_MAX);  // (a capped list is longer than max_refs)
     hipLaunchKernelGGL((k_ret_bins<1>), g, b, 0, L->stream, d_capj, d_capoff, ncap, ctotal, min_day, pick, bins);
     hipLaunchKernelGGL((k_ret_pick<1>), gp, b, 0, L->stream, ncap, bins, K, pick, d_capsel, cut);
@@ -1710,7 +1751,7 @@ int retention(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, int32_t min
   // ---- compaction: with a cap a chunk is flagged in two steps (the cut-day marks scanned for the ranks)
   hipError_t ferr = hipSuccess;
   auto flag = [&](const RmJob* dj, const int64_t* doff, int ncj, int64_t n, int32_t* keep, const ChunkAux& x) {
-    const dim3 g(mark_blocks(n)), b(256);
+    const dim3 g(span_blocks(n)), b(256);
     if (max_refs == 0) {
       hipLaunchKernelGGL((k_ret_flag<0>), g, b, 0, L->stream, dj, doff, ncj, n, min_day, cut, x.sel, x.kx, keep);
       return;
@@ -1750,7 +1791,7 @@ extern "C" int yrwi_retain(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms
 // STREAM (k_ref_stream): the grid, spans, SegCursor and four loads in flight of k_host_mark over khi / klo of
 // the selected lists in term order, 9 B per posting and no row read; the lookup is the slot of the 72-bit key
 // in the sorted url set, staged in LDS (8 B + 1 B per url) up to REF_LDS_MAX urls and searched in global
-// memory above.  Per-list hits are summed in the wave and added on leaving the list, as jrem is; per-url
+// memory above.  Per-list hits are summed in the wave and added on leaving the list (ListTally); per-url
 // hits take one atomic per distinct slot of a wave's step.
 // PROBE (k_ref_probe): one thread per (list, slot) pair, list-major, searches the list for the url (lb_key).
 //
@@ -1783,29 +1824,6 @@ struct RefOut {  // where the pack pass writes (REF_PACK: rows, terms; REF_KEYS:
   uint64_t* sval;
 };
 
-// slot of (h, l) in the ascending 72-bit set, -1: not in it
-__device__ __forceinline__ int ref_slot(const uint64_t* kh, const uint8_t* kl, int nu, uint64_t h, uint32_t l) {
-  int lo = 0, hi = nu;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (key_lt(kh[mid], kl[mid], h, l)) lo = mid + 1; else hi = mid;
-  }
-  return lo < nu && kh[lo] == h && (uint32_t)kl[lo] == l ? lo : -1;
-}
-
-// cnt[key] += the wave's hits of that key: one atomic per distinct key.  Called by the whole wave.
-__device__ __forceinline__ void wave_add_by(bool hit, int key, unsigned long long* __restrict__ cnt) {
-  const int lane = threadIdx.x & 63;
-  uint64_t act = __ballot(hit);
-  while (act) {
-    const int lead = __ffsll((unsigned long long)act) - 1;
-    const int lk = __shfl(key, lead, 64);
-    const uint64_t same = __ballot(hit && key == lk);
-    if (lane == lead) atomicAdd(&cnt[lk], (unsigned long long)__popcll(same));
-    act &= ~same;
-  }
-}
-
 __device__ __forceinline__ uint32_t lanes_below(uint64_t ballot) {
   return (uint32_t)__popcll(ballot & (((uint64_t)1 << (threadIdx.x & 63)) - 1));
 }
@@ -1824,30 +1842,15 @@ __device__ __forceinline__ void ref_emit(const RefOut& O, const RmJob* __restric
   }
 }
 
-// One step of a thread, as mark_tile: postings base + 256 u + thread (u < 4) below end -> their slots in the
-// url set (-1: not of the set, or past end), lists and rows.  The four key loads are issued before the first search.
+// a key tile -> its postings' slots in the url set (-1: not of the set, or past end), lists and rows
 __device__ __forceinline__ void ref_tile(SegCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
                                          int nj, int64_t total, const uint64_t* kh, const uint8_t* kl, int nu,
                                          int64_t base, int64_t end, int slot[4], int c[4], int64_t k[4]) {
   uint64_t h[4];
   uint32_t l[4];
+  key_tile(s, jobs, off, nj, total, base, end, c, k, h, l);
 #pragma unroll
-  for (int u = 0; u < 4; u++) {
-    const int64_t i = base + u * 256 + threadIdx.x;
-    c[u] = -1;
-    k[u] = 0;
-    h[u] = 0;
-    l[u] = 0;
-    if (i < end) {
-      seg_seek(s, jobs, off, nj, total, i);
-      c[u] = s.c;
-      k[u] = i - s.lo;
-      h[u] = s.kh[k[u]];
-      l[u] = s.kl[k[u]];
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < 4; u++) slot[u] = c[u] >= 0 ? ref_slot(kh, kl, nu, h[u], l[u]) : -1;
+  for (int u = 0; u < 4; u++) slot[u] = c[u] >= 0 ? set_slot(kh, kl, nu, h[u], l[u]) : -1;
 }
 
 // STREAM.  REF_COUNT / REF_TILES: jcnt[c] += references in list c, ucnt[slot] += references of url slot,
@@ -1864,25 +1867,16 @@ __global__ __launch_bounds__(256) void k_ref_stream(const RmJob* __restrict__ jo
   __shared__ uint8_t s_kl[LDS ? REF_LDS_MAX : 1];
   __shared__ uint32_t s_w[16];
   if (MODE >= REF_PACK && O.tile_start[O.tiles] > O.cap) return;  // (the same in every thread of the grid)
-  const uint64_t* kh = ukh;
-  const uint8_t* kl = ukl;
-  if (LDS) {
-    for (int i = threadIdx.x; i < nu; i += blockDim.x) {
-      s_kh[i] = ukh[i];
-      s_kl[i] = ukl[i];
-    }
-    __syncthreads();
-    kh = s_kh;
-    kl = s_kl;
-  }
+  stage_set<LDS, true>(s_kh, ukh, nu, s_kl, ukl);
+  const uint64_t* kh = LDS ? s_kh : ukh;
+  const uint8_t* kl = LDS ? s_kl : ukl;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int64_t begin, end;
-  host_span(total, &begin, &end);
+  span_of(total, &begin, &end);
   SegCursor cur;
-  int acc_c = -1;
-  uint32_t acc_n = 0;
-  for (int64_t base = begin; base < end; base += HOST_TILE) {
-    const int64_t t = base / HOST_TILE;
+  ListTally per_list;
+  for (int64_t base = begin; base < end; base += SPAN_TILE) {
+    const int64_t t = base / SPAN_TILE;
     int64_t tstart = 0;
     if (MODE >= REF_PACK) {
       tstart = O.tile_start[t];
@@ -1895,23 +1889,9 @@ __global__ __launch_bounds__(256) void k_ref_stream(const RmJob* __restrict__ jo
       uint32_t tile_n = 0;
 #pragma unroll
       for (int u = 0; u < 4; u++) {
-        const int c = cs[u];
         const bool hit = slots[u] >= 0;
-        // per list: as k_host_mark sums jrem (acc_c, acc_n: the same in every lane)
-        uint64_t act = __ballot(hit);
-        tile_n += (uint32_t)__popcll(act);
-        while (act) {
-          const int lead = __ffsll((unsigned long long)act) - 1;
-          const int lc = __shfl(c, lead, 64);
-          const uint64_t same = __ballot(hit && c == lc);
-          if (lc != acc_c) {
-            if (acc_n && lane == 0) atomicAdd(&jcnt[acc_c], (unsigned long long)acc_n);
-            acc_c = lc;
-            acc_n = 0;
-          }
-          acc_n += (uint32_t)__popcll(same);
-          act &= ~same;
-        }
+        tile_n += (uint32_t)__popcll(__ballot(hit));
+        per_list.add(hit, cs[u], jcnt);
         wave_add_by(hit, slots[u], ucnt);
       }
       if (MODE == REF_TILES && tile_n && lane == 0) atomicAdd(&tile_cnt[t], (int32_t)tile_n);
@@ -1939,7 +1919,7 @@ __global__ __launch_bounds__(256) void k_ref_stream(const RmJob* __restrict__ jo
       __syncthreads();  // (s_w is written again in the next tile that has hits)
     }
   }
-  if (MODE <= REF_TILES && acc_n && lane == 0) atomicAdd(&jcnt[acc_c], (unsigned long long)acc_n);
+  if (MODE <= REF_TILES) per_list.flush(jcnt);
 }
 
 // PROBE: pair p = list p / nu, slot p % nu; tile t = pairs [256 t, 256 t + 256).  Modes as k_ref_stream.
@@ -2064,10 +2044,10 @@ void ref_find(const RefPass& P, const RefOut& O, hipStream_t s) {
     hipLaunchKernelGGL((k_ref_probe<MODE>), dim3((unsigned)P.tiles), dim3(REF_PAIR_TILE), 0, s, P.jobs, P.ukh, P.ukl,
                        P.nu, P.pairs, P.jcnt, P.ucnt, P.tile_cnt, O);
   } else if (P.nu <= REF_LDS_MAX) {
-    hipLaunchKernelGGL((k_ref_stream<true, MODE>), dim3(mark_blocks(P.total)), dim3(256), 0, s, P.jobs, P.off, P.nj,
+    hipLaunchKernelGGL((k_ref_stream<true, MODE>), dim3(span_blocks(P.total)), dim3(256), 0, s, P.jobs, P.off, P.nj,
                        P.total, P.ukh, P.ukl, P.nu, P.jcnt, P.ucnt, P.tile_cnt, O);
   } else {
-    hipLaunchKernelGGL((k_ref_stream<false, MODE>), dim3(mark_blocks(P.total)), dim3(256), 0, s, P.jobs, P.off, P.nj,
+    hipLaunchKernelGGL((k_ref_stream<false, MODE>), dim3(span_blocks(P.total)), dim3(256), 0, s, P.jobs, P.off, P.nj,
                        P.total, P.ukh, P.ukl, P.nu, P.jcnt, P.ucnt, P.tile_cnt, O);
   }
 }
@@ -2088,12 +2068,9 @@ extern "C" int yrwi_url_references(yrwi_ctx* ctx, const uint8_t* terms12, int32_
   std::memset(&S, 0, sizeof(S));
   Tally T;
   // ---- the urls as given (for counts) and as a set, sorted and each once; the selected lists in term order
-  std::vector<KeyT> in((size_t)nurls);
-  for (int64_t i = 0; i < nurls; i++)
-    if (!key_of(urls12 + i * 12, &in[(size_t)i])) return ctx->fail(YRWI_E_HASH, "url hash is not well-formed Base64");
-  std::vector<KeyT> uk = in;
-  std::sort(uk.begin(), uk.end());
-  uk.erase(std::unique(uk.begin(), uk.end()), uk.end());
+  UrlSet U;
+  if (int rc = url_set(ctx, urls12, nurls, &U)) return rc;
+  const std::vector<KeyT>&in = U.in, &uk = U.uk;
   ListSel sel;
   if (int rc = select_lists(ctx, terms12, nterms, true, &sel)) return rc;
   RmTable t;
@@ -2125,7 +2102,7 @@ extern "C" int yrwi_url_references(yrwi_ctx* ctx, const uint8_t* terms12, int32_
   const char* forced = getenv("YRWI_REFS_PATH");
   if (forced && !strcmp(forced, "stream")) probe = false;
   if (forced && !strcmp(forced, "probe")) probe = true;
-  const int64_t tiles = probe ? ceil_div(pairs, REF_PAIR_TILE) : ceil_div(total, HOST_TILE);
+  const int64_t tiles = probe ? ceil_div(pairs, REF_PAIR_TILE) : ceil_div(total, SPAN_TILE);
   if (probe && tiles > (int64_t)INT32_MAX) return ctx->fail(YRWI_E_LIMIT, "2^39 (list, url) pairs or more on the probe path");
   S.path = probe ? YRWI_REFS_PROBE : YRWI_REFS_STREAM;
   const bool fetch = cap_refs > 0, by_url = order == YRWI_REFS_BY_URL;
@@ -2133,29 +2110,23 @@ extern "C" int yrwi_url_references(yrwi_ctx* ctx, const uint8_t* terms12, int32_
   const int64_t room = std::min(cap_refs, std::min(total, pairs));
   const bool direct = fetch && (reinterpret_cast<uintptr_t>(rows40_out) & 7) == 0 &&
                       ctx->hostreg.contains(rows40_out, (size_t)room * YRWI_ROW_BYTES);
-  if (begin_pass(L)) return ctx->take(L, YRWI_E_HIP);
-  T.syncs++;
-  std::vector<uint64_t> h_ukh((size_t)nu);
-  std::vector<uint8_t> h_ukl((size_t)nu);
-  for (int i = 0; i < nu; i++) {
-    h_ukh[(size_t)i] = uk[(size_t)i].hi;
-    h_ukl[(size_t)i] = (uint8_t)uk[(size_t)i].lo;
-  }
   std::vector<uint32_t> lterm((size_t)nj * 3);  // the lists' term hashes, as the pack pass stores them
   for (int j = 0; j < nj; j++) key_chars(t.jkey[(size_t)j], reinterpret_cast<uint8_t*>(&lterm[(size_t)j * 3]));
-  // ---- device tables; the counters (per list, per url, the total) and the tile counts are one block, zeroed at once
+  // ---- device tables; the counters (per list, per url, the total) and the tile counts are one block, zeroed at
+  //      once; find: one upload, one memset, the count pass; fetch: the scan and, by term, the pack pass behind it
   const int64_t nres = (int64_t)nj + nu + 1;
   const size_t zero_bytes = (size_t)nres * 8 + (fetch ? (size_t)tiles * 4 : 0);
-  uint64_t* ukh = arena_alloc<uint64_t>(L, nu);
-  uint8_t* ukl = arena_alloc<uint8_t>(L, nu);
-  RmJob* d_jobs = arena_alloc<RmJob>(L, nj);
-  int64_t* d_off = arena_alloc<int64_t>(L, nj);
-  uint32_t* d_lterm = arena_alloc<uint32_t>(L, (int64_t)nj * 3);
-  unsigned long long* res = reinterpret_cast<unsigned long long*>(L->arena.alloc(zero_bytes));
+  const char* nomem = "device allocation (url references)";
+  PassDev D;
+  uint64_t* ukh = nullptr;
+  uint8_t* ukl = nullptr;
+  uint32_t* d_lterm = nullptr;
+  if (int rc = pass_begin(ctx, L, t, zero_bytes, nomem, &D, &T, &ukh, U.kh, &ukl, U.kl, &d_lterm, lterm)) return rc;
+  RmJob* d_jobs = D.jobs;
+  unsigned long long* res = D.res;
   int64_t* tile_start = fetch ? arena_alloc<int64_t>(L, tiles + 1) : nullptr;
-  if (!ukh || !ukl || !d_jobs || !d_off || !d_lterm || !res || (fetch && !tile_start))
-    return ctx->fail(YRWI_E_NOMEM, "device allocation (url references)");
-  RefPass P{d_jobs, d_off, nj, nu, total, pairs, tiles, ukh, ukl, res, res + nj,
+  if (fetch && !tile_start) return ctx->fail(YRWI_E_NOMEM, nomem);
+  RefPass P{d_jobs, D.off, nj, nu, total, pairs, tiles, ukh, ukl, res, res + nj,
             reinterpret_cast<int32_t*>(res + nres), probe};
   RefOut O{tile_start, tiles, cap_refs, d_lterm, nullptr, nullptr, nullptr, nullptr};
   uint8_t* d_rows = nullptr;  // where the rows are written: the caller's pinned buffer or scratch
@@ -2169,16 +2140,13 @@ extern "C" int yrwi_url_references(yrwi_ctx* ctx, const uint8_t* terms12, int32_
     O.terms = arena_alloc<uint32_t>(L, n * 3);
     return d_rows && O.terms;
   };
-  if (fetch && !by_url && !out_buffers(room)) return ctx->fail(YRWI_E_NOMEM, "device allocation (url references)");
-  // ---- find: one upload, one memset, the count pass; fetch: the scan and, by term, the pack pass behind it
-  if (int rc = upload(L, ukh, h_ukh, ukl, h_ukl, d_jobs, t.jobs, d_off, t.off, d_lterm, lterm)) return ctx->take(L, rc);
-  HIPCHK(ctx, hipMemsetAsync(res, 0, zero_bytes, L->stream));
+  if (fetch && !by_url && !out_buffers(room)) return ctx->fail(YRWI_E_NOMEM, nomem);
   hipEvent_t e0 = L->event(), e1 = L->event();
   HIPCHK(ctx, hipEventRecord(e0, L->stream));
   if (fetch) ref_find<REF_TILES>(P, O, L->stream); else ref_find<REF_COUNT>(P, O, L->stream);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipEventRecord(e1, L->stream));
-  T.launches += 3;
+  T.launches++;
   if (fetch) {
     hipLaunchKernelGGL(k_ref_scan, dim3(1), dim3(256), 0, L->stream, P.tile_cnt, tiles, tile_start, res + nres - 1);
     T.launches++;
@@ -2188,11 +2156,8 @@ extern "C" int yrwi_url_references(yrwi_ctx* ctx, const uint8_t* terms12, int32_
     }
     HIPCHK(ctx, hipGetLastError());
   }
-  const int64_t* h = reinterpret_cast<const int64_t*>(readback(L, &L->down_stage, res, nres, 8, 8));
-  if (!h) return ctx->take(L, YRWI_E_HIP);
-  T.launches++;
-  HIPCHK(ctx, lane_sync(L));
-  T.syncs++;
+  const int64_t* h = nullptr;
+  if (int rc = pass_end(ctx, L, D, nres, &h, &T)) return rc;
   float msf = 0.f;
   if (hipEventElapsedTime(&msf, e0, e1) == hipSuccess) S.t_find_ns = (int64_t)((double)msf * 1e6);
   (void)hipGetLastError();  // a statistics event that could not be read is not the call's error
