@@ -318,7 +318,8 @@ int yrwi_count_hosts(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, cons
  * table cannot be allocated, the call returns YRWI_E_NOMEM.  The hosts that pass are compacted and sorted on
  * the device and only the first min(hosts_passing, cap) cross PCIe.  A sharded context counts what it holds:
  * no collective is involved, every rank is asked the same thing, the ranks' counts of a host add up and the
- * caller merges them.  Per-host distinct url counts and per-host list counts are not part of this. */
+ * caller merges them.  Per-host distinct url counts are yrwi_host_url_census below; per-host list counts are
+ * not part of this. */
 #define YRWI_CENSUS_BY_HOST 0   /* ascending host hash (Base64Order of the 6 characters = the 36-bit key order) */
 #define YRWI_CENSUS_BY_COUNT 1  /* postings descending; equal counts by ascending host hash */
 typedef struct yrwi_census_stats {
@@ -334,6 +335,68 @@ typedef struct yrwi_census_stats {
 } yrwi_census_stats;
 int yrwi_host_census(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, int32_t order, int64_t min_postings,
                      uint8_t* hosts6_out, int64_t* counts_out, int64_t cap, int64_t* nout, yrwi_census_stats* st);
+/* Census of the urls: which documents the selected lists hold, in how many of them each, and how many
+ * documents and postings every host has.  UNVERIFIED against a reference line: the reference has no method
+ * that groups the whole RWI by url; both calls are defined through calls of this header instead.
+ *   Selection: exactly that of yrwi_host_census (nterms == 0 every list, otherwise the named lists, duplicates
+ * once, unknown terms ignored).  An ill-formed term or host hash: YRWI_E_HASH with nothing written.  Both calls
+ * wait for the batches in flight, bring the url ids up to date as yrwi_build_url_ids does, and otherwise change
+ * nothing in the context.
+ *   yrwi_url_census: the references of a url are the selected lists that hold a posting of it -- counts[i] of
+ * yrwi_url_references over the same selection.  The result is the urls with at least max(min_refs, 1)
+ * references and, with nhosts > 0, with url-hash characters 6..11 in the host set (hosts6 + 6 i, as
+ * yrwi_remove_hosts takes them: duplicates once, hosts nobody has ignored; the set is sorted and deduplicated
+ * on the host, searched in LDS up to YRWI_HOST_LDS_MAX hosts and in global memory above), in `order`.  The
+ * first min(urls_passing, cap) are written: urls12_out + 12 i the 12 characters, refs_out[i] the references,
+ * *nout the number written.  cap < urls_passing is not an error (the top N); cap == 0 with NULL buffers only
+ * fills st.
+ *   yrwi_host_url_census: the hosts with at least max(min_urls, 1) distinct urls in the selection, in `order`
+ * (YRWI_CENSUS_BY_HOST: ascending host hash; YRWI_CENSUS_BY_COUNT: here distinct urls descending, equal counts
+ * by ascending host hash).  hosts6_out + 6 i the host hash, urls_out[i] its distinct urls, postings_out[i]
+ * its postings -- what yrwi_host_census reports for that host over the same selection.
+ *   `order` outside the two values, cap < 0, or cap > 0 with a NULL buffer: YRWI_E_ARG.  On any error no
+ * output buffer and not *nout is written.  st and nout may be NULL.  Nothing selected: a successful empty
+ * result that enqueues nothing (st: zeros).  YRWI_E_LIMIT: the limit of the url ids (2^31 postings in the
+ * context), or 2^31 - 1 selected postings or dictionary urls or more.
+ *   No list is read back and no key is sorted: the group-by runs over the 32-bit url ids of the postings, and
+ * ascending id is ascending url hash.  Two ways to count.  YRWI_UCENSUS_HIST: one streaming pass over the
+ * 4-byte id of every selected posting (grid and spans of the other maintenance passes) adds 1 to a zeroed
+ * 32-bit count per dictionary id; its tail walks the dictionary.  YRWI_UCENSUS_SORT: the selected ids are
+ * gathered, radix-sorted over ceil(log2 dict_urls) bits and run-length encoded; its cost follows the selected
+ * postings, never the dictionary.  The call takes SORT when postings * UC_SORT_WEIGHT (yrwi_update.hip)
+ * <= dict_urls; the environment's YRWI_UCENSUS_PATH = hist | sort, read per call, forces a path; st->path says
+ * which ran.  Both paths return the same bytes.  One tail: the urls that pass are flagged, scanned and
+ * compacted in id order (YRWI_UCENSUS_BY_URL as it is; BY_REFS: one stable radix sort), the characters of the
+ * first min(urls_passing, cap) are written on the device from their dictionary keys, and only those cross
+ * PCIe.  The host form sorts the distinct urls by the host of their dictionary key and reduces the runs; the
+ * postings are read once.  All scratch is the lane's arena: a steady sequence of calls makes no device-wide
+ * allocation after the first.  A sharded context reports what it holds, without a collective: a url lies in
+ * one rank's range, so the ranks' urls are disjoint, and a host's url and posting counts add up over the
+ * ranks. */
+#define YRWI_UCENSUS_BY_URL  0  /* ascending url hash (72-bit key order) */
+#define YRWI_UCENSUS_BY_REFS 1  /* references descending; equal references by ascending url hash */
+#define YRWI_UCENSUS_HIST 0     /* stats.path: a count per dictionary id */
+#define YRWI_UCENSUS_SORT 1     /* stats.path: the selected ids sorted */
+typedef struct yrwi_ucensus_stats {
+  int64_t lists, postings;  /* selected non-empty lists, rows in them: the references of ALL urls add up to postings */
+  int64_t dict_urls;        /* ids of the url dictionary at the call (keys of removed postings stay in it) */
+  int64_t urls;             /* distinct urls in the selection, before the host set and the minimum; an id without a selected posting is never counted or returned */
+  int64_t urls_hosted;      /* of which with their host in the set; == urls when nhosts == 0 and in the host form */
+  int64_t urls_passing;     /* of which with at least min_refs references: what a cap must hold to get all (host form: == urls) */
+  int64_t max_refs;         /* the most references of one of the urls_hosted; 0 when there is none */
+  int64_t hosts;            /* host form: distinct hosts in the selection */
+  int64_t hosts_passing;    /* host form: of which with at least min_urls urls */
+  int32_t path;             /* YRWI_UCENSUS_HIST / YRWI_UCENSUS_SORT */
+  int32_t launches, syncs;  /* functions of the path, the order and the form alone, never of lists, urls or postings */
+  int64_t t_count_ns;       /* device time of the counting kernels (HIP events): k_uc_hist, or gather, sort and run lengths */
+  int64_t t_total_ns;
+} yrwi_ucensus_stats;
+int yrwi_url_census(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uint8_t* hosts6, int32_t nhosts,
+                    int32_t order, int64_t min_refs, uint8_t* urls12_out, int64_t* refs_out, int64_t cap,
+                    int64_t* nout, yrwi_ucensus_stats* st);
+int yrwi_host_url_census(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, int32_t order, int64_t min_urls,
+                         uint8_t* hosts6_out, int64_t* urls_out, int64_t* postings_out, int64_t cap, int64_t* nout,
+                         yrwi_ucensus_stats* st);
 /* Retention: keeps the device index inside a budget by two rules on the lastModified day of a posting (the `a`
  * cell: bytes 12-13 of the row, big endian, days; the raw unsigned 16-bit value, not clamped to today -- that
  * clamp belongs to ranking).  UNVERIFIED against a reference line: the reference has no method that drops

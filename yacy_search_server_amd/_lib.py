@@ -163,6 +163,19 @@ class CCensusStats(ctypes.Structure):
                 ("t_count_ns", ctypes.c_int64), ("t_total_ns", ctypes.c_int64)]
 
 
+UCENSUS_BY_URL, UCENSUS_BY_REFS = 0, 1  # YRWI_UCENSUS_BY_*: the orders of yrwi_url_census
+UCENSUS_ORDERS = {"url": UCENSUS_BY_URL, "refs": UCENSUS_BY_REFS}
+UCENSUS_HIST, UCENSUS_SORT = 0, 1  # yrwi_ucensus_stats.path; YRWI_UCENSUS_PATH = hist | sort forces one
+UCENSUS_PATHS = {"hist": UCENSUS_HIST, "sort": UCENSUS_SORT}
+
+
+class CUCensusStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("lists", "postings", "dict_urls", "urls", "urls_hosted",
+                                              "urls_passing", "max_refs", "hosts", "hosts_passing")] + \
+        [(n, ctypes.c_int32) for n in ("path", "launches", "syncs")] + \
+        [(n, ctypes.c_int64) for n in ("t_count_ns", "t_total_ns")]
+
+
 RETENTION_DAYS = 65536  # entries of yrwi_retention_count's day histogram: one per value of the 16-bit `a` cell
 RETENTION_LDS_WINDOW = 8192  # days a workgroup of the histogram pass counts in LDS; days outside it: hist_bypass
 
@@ -233,6 +246,12 @@ SIGNATURES = {
     "yrwi_host_census": (ctypes.c_int, [_VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _VP, _VP,
                                         ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
                                         ctypes.POINTER(CCensusStats)]),
+    "yrwi_url_census": (ctypes.c_int, [_VP, _VP, ctypes.c_int32, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                       _VP, _VP, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                                       ctypes.POINTER(CUCensusStats)]),
+    "yrwi_host_url_census": (ctypes.c_int, [_VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _VP, _VP, _VP,
+                                            ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                                            ctypes.POINTER(CUCensusStats)]),
     "yrwi_retention_count": (ctypes.c_int, [_VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _VP,
                                             ctypes.POINTER(CRetentionStats)]),
     "yrwi_retain": (ctypes.c_int, [_VP, _VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,

@@ -60,6 +60,10 @@
 // count descending), and only the first min(hosts_passing, cap) cross PCIe.  All scratch is the
 // lane's arena; 5 launches and one sync per counting pass, 5 or 6 launches and one sync after them.
 //
+// yrwi_url_census / yrwi_host_url_census: which urls the selected lists hold, in how many of them each, and
+// the distinct urls and postings of every host; a group-by over the 4-byte url ids, described with its kernels
+// behind the census of the hosts.  It shares the selection, the spans, the cursor and the frame of a pass.
+//
 // yrwi_retain / yrwi_retention_count: removal by the age of a posting and a cap on the length of a list;
 // described with their kernels at the end of this file.  They share the selection, the spans and
 // compact_commit with the host calls.
@@ -1356,6 +1360,572 @@ extern "C" int yrwi_host_census(yrwi_ctx* ctx, const uint8_t* terms12, int32_t n
     counts_out[i] = hc[i];
   }
   return finish(nw);
+}
+
+// ---------------------------------------------------------------- census of the urls
+//
+// yrwi_url_census / yrwi_host_url_census: which urls the selected lists hold and in how many of them each
+// (its references), and how many distinct urls and postings every host has (UNVERIFIED against a reference
+// line: the reference has no method that groups the RWI by url).  A group-by over the 32-bit url ids
+// (ListRec::uid, brought up to date first), never over the 9-byte keys: the key of an id is read from the
+// dictionary (dkhi / dklo) only for the host test and for the urls that leave the device, and ascending id is
+// ascending url hash, so YRWI_UCENSUS_BY_URL needs no sort.
+//
+// HIST (k_uc_hist): grid, spans and cursor of the other streaming passes over the uid of every selected
+// posting, 4 B each (the lists' uid pointers are a table beside the list table); one 32-bit global atomic add
+// per posting into a zeroed count per dictionary id.  The ids of a list ascend and are distinct, so a wave's
+// adds collide only where it covers several short lists.  Its tail walks the dictionary.
+// SORT (k_uc_gather): the selected ids into one array, radix-sorted over ceil(log2 dict_urls) bits; the heads
+// of the runs of equal ids are flagged and scanned, and every head stores its id and its place: the
+// references of a run are the distance to the next head.  Its cost follows the selected postings alone.
+//
+// One tail over the candidates of either path (UcCand: every dictionary id with its count, or every run):
+// flag (references >= min, host in the sorted set: host_slot over the set staged in LDS or left in global
+// memory), scan, compact to (id, refs) in id order; BY_REFS: one stable radix sort by refs descending;
+// k_uc_place writes the characters of the first min(passing, cap) from their dictionary keys.
+// The host form groups the compacted urls by host36 of their key: one radix sort of (host, refs) over 36
+// bits, then the head flag, scan and run step of SORT over the hosts: a host's urls are its run's length, its
+// postings the difference of the scanned refs at its run's ends; then the same flag, scan and compact over
+// the runs, a stable sort by urls descending for BY_COUNT, and k_uc_hplace.  The postings are read once.
+namespace {
+
+// the call takes SORT when postings * UC_SORT_WEIGHT <= dict_urls.  UNMEASURED: tools/url_census.py has not
+// run on the device yet; 8 is the placeholder the table is to replace
+constexpr int64_t UC_SORT_WEIGHT = 8;
+// the counters of a flagging pass
+enum { UC_URLS = 0, UC_HOSTED = 1, UC_PASSING = 2, UC_MAXREFS = 3, UC_WORDS = 4 };
+
+// a lane's place in the flattened lists and its list's url ids
+struct UidCursor : SegCursor {
+  const uint32_t* ids = nullptr;
+};
+
+// One step of a thread over the url ids, key_tile's counterpart: postings base + 256 u + thread (u < 4) below
+// end -> their ids (live[u]: below end).  The four loads are issued before the caller's first use of one.
+__device__ __forceinline__ void uid_tile(UidCursor& s, const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                         const uint32_t* const* __restrict__ uid, int nj, int64_t total, int64_t base,
+                                         int64_t end, uint32_t id[4], bool live[4]) {
+#pragma unroll
+  for (int u = 0; u < 4; u++) {
+    const int64_t i = base + u * 256 + threadIdx.x;
+    live[u] = i < end;
+    id[u] = 0;
+    if (live[u]) {
+      if (i >= s.hi) {
+        seg_seek(s, jobs, off, nj, total, i);
+        s.ids = uid[s.c];
+      }
+      id[u] = s.ids[i - s.lo];
+    }
+  }
+}
+
+// HIST: cnt[id] += 1 for every selected posting (cnt zeroed by the caller; an id is below nd)
+__global__ __launch_bounds__(256) void k_uc_hist(const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                                 const uint32_t* const* __restrict__ uid, int nj, int64_t total,
+                                                 int64_t nd, uint32_t* __restrict__ cnt) {
+  int64_t begin, end;
+  span_of(total, &begin, &end);
+  UidCursor cur;
+  for (int64_t base = begin; base < end; base += SPAN_TILE) {
+    uint32_t id[4];
+    bool live[4];
+    uid_tile(cur, jobs, off, uid, nj, total, base, end, id, live);
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+      if (live[u] && (int64_t)id[u] < nd) atomicAdd(&cnt[id[u]], 1u);
+  }
+}
+
+// SORT: out[i] = the url id of flattened posting i
+__global__ __launch_bounds__(256) void k_uc_gather(const RmJob* __restrict__ jobs, const int64_t* __restrict__ off,
+                                                   const uint32_t* const* __restrict__ uid, int nj, int64_t total,
+                                                   uint32_t* __restrict__ out) {
+  int64_t begin, end;
+  span_of(total, &begin, &end);
+  UidCursor cur;
+  for (int64_t base = begin; base < end; base += SPAN_TILE) {
+    uint32_t id[4];
+    bool live[4];
+    uid_tile(cur, jobs, off, uid, nj, total, base, end, id, live);
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+      if (live[u]) out[base + u * 256 + threadIdx.x] = id[u];
+  }
+}
+
+// flag[i] = s[i] begins a run of equal keys of the ascending s[0, n); flag[n] = 0 (the scan's last element)
+template <class K>
+__global__ __launch_bounds__(256) void k_uc_heads(const K* __restrict__ s, int64_t n, int32_t* __restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n) return;
+  flag[i] = i < n && (i == 0 || s[i] != s[i - 1]) ? 1 : 0;
+}
+
+// hx = the exclusive scan of flag: run r = hx[i] of head i gets its key and its place; *nruns = hx[n] and
+// rpos[*nruns] = n, so run r holds rpos[r + 1] - rpos[r] elements
+template <class K>
+__global__ __launch_bounds__(256) void k_uc_runs(const K* __restrict__ s, int64_t n, const int32_t* __restrict__ flag,
+                                                 const int64_t* __restrict__ hx, K* __restrict__ rkey,
+                                                 uint32_t* __restrict__ rpos, int64_t* __restrict__ nruns) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n) return;
+  if (i == n) {
+    rpos[hx[n]] = (uint32_t)n;
+    *nruns = hx[n];
+  } else if (flag[i]) {
+    rkey[hx[i]] = s[i];
+    rpos[hx[i]] = (uint32_t)i;
+  }
+}
+
+// The candidates of a flagging pass, i < m: (cnt) dictionary id i with cnt[i] references, none: no candidate;
+// (rpos) run i of *nruns with the id rid[i] (rid null: i itself) and rpos[i + 1] - rpos[i] references.
+struct UcCand {
+  int64_t m;
+  const uint32_t* cnt;
+  const uint32_t* rid;
+  const uint32_t* rpos;
+  const int64_t* nruns;
+};
+
+template <bool RUNS>
+__device__ __forceinline__ bool uc_cand(const UcCand& C, int64_t i, uint32_t* id, uint32_t* refs) {
+  if (i >= C.m) return false;
+  if (RUNS) {
+    if (i >= *C.nruns) return false;
+    *id = C.rid ? C.rid[i] : (uint32_t)i;
+    *refs = C.rpos[i + 1] - C.rpos[i];
+    return true;
+  }
+  *id = (uint32_t)i;
+  *refs = C.cnt[i];
+  return *refs != 0;
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
+  return v;
+}
+
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v = std::max(v, (uint32_t)__shfl_xor((int)v, d, 64));
+  return v;
+}
+
+// flag[i] = candidate i has at least minr references and (nh > 0) the host of its dictionary key is in the
+// set; flag[m] = 0.  ctr: candidates, of which with the host in the set, of which flagged, and the most
+// references of one with the host in the set; one atomic each per wave.  At most SPAN_BLOCKS workgroups
+// stride over the candidates, so the set is staged once per workgroup.
+template <bool RUNS, bool LDS>
+__global__ __launch_bounds__(256) void k_uc_flag(UcCand C, const uint64_t* __restrict__ dkhi,
+                                                 const uint8_t* __restrict__ dklo, const uint64_t* __restrict__ hset,
+                                                 int nh, uint32_t minr, int32_t* __restrict__ flag,
+                                                 unsigned long long* __restrict__ ctr) {
+  __shared__ uint64_t s_set[LDS ? HOST_LDS_MAX : 1];
+  stage_set<LDS>(s_set, hset, nh);
+  const uint64_t* hs = LDS ? s_set : hset;
+  uint32_t n_url = 0, n_hosted = 0, n_pass = 0, most = 0;
+  for (int64_t b = (int64_t)blockIdx.x * 256; b <= C.m; b += (int64_t)gridDim.x * 256) {
+    const int64_t i = b + threadIdx.x;
+    uint32_t id = 0, refs = 0;
+    const bool url = uc_cand<RUNS>(C, i, &id, &refs);
+    bool hosted = url;
+    if (url && nh > 0) hosted = host_slot(hs, nh, host36(dkhi[id], dklo[id])) >= 0;
+    const bool pass = hosted && refs >= minr;
+    if (i <= C.m) flag[i] = pass ? 1 : 0;
+    n_url += url;
+    n_hosted += hosted;
+    n_pass += pass;
+    if (hosted) most = std::max(most, refs);
+  }
+  n_url = wave_sum(n_url);
+  n_hosted = wave_sum(n_hosted);
+  n_pass = wave_sum(n_pass);
+  most = wave_max(most);
+  if ((threadIdx.x & 63) == 0) {
+    if (n_url) atomicAdd(&ctr[UC_URLS], (unsigned long long)n_url);
+    if (n_hosted) atomicAdd(&ctr[UC_HOSTED], (unsigned long long)n_hosted);
+    if (n_pass) atomicAdd(&ctr[UC_PASSING], (unsigned long long)n_pass);
+    if (most) atomicMax(&ctr[UC_MAXREFS], (unsigned long long)most);
+  }
+}
+
+// the flagged candidates, in their order: px = the exclusive scan of flag
+template <bool RUNS>
+__global__ __launch_bounds__(256) void k_uc_compact(UcCand C, const int32_t* __restrict__ flag,
+                                                    const int64_t* __restrict__ px, uint32_t* __restrict__ oid,
+                                                    uint32_t* __restrict__ oref) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= C.m || !flag[i]) return;
+  uint32_t id = 0, refs = 0;
+  uc_cand<RUNS>(C, i, &id, &refs);
+  oid[px[i]] = id;
+  oref[px[i]] = refs;
+}
+
+// character v of Base64Order.enhancedCoder's alphabet (ALPHA, yrwi_host.h)
+__device__ __forceinline__ uint32_t b64_char(uint32_t v) {
+  return v < 26 ? 'A' + v : v < 52 ? 'a' + (v - 26) : v < 62 ? '0' + (v - 52) : v == 62 ? '-' : '_';
+}
+
+// result i < n: the 12 characters of the dictionary key of id[i] (key_chars' rule; three words) and its references
+__global__ __launch_bounds__(256) void k_uc_place(const uint32_t* __restrict__ id, const uint32_t* __restrict__ refs,
+                                                  int64_t n, const uint64_t* __restrict__ dkhi,
+                                                  const uint8_t* __restrict__ dklo, uint32_t* __restrict__ urls12,
+                                                  int64_t* __restrict__ refs_out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t hi = dkhi[id[i]];
+  const uint32_t lo = dklo[id[i]];
+  const uint64_t x = hi >> 4;
+  uint32_t w[3] = {0, 0, 0};
+#pragma unroll
+  for (int j = 0; j < 12; j++) {
+    const uint32_t v = j < 10 ? (uint32_t)(x >> (6 * (9 - j))) & 63u
+                              : j == 10 ? (((uint32_t)hi & 15u) << 2) | (lo >> 6) : lo & 63u;
+    w[j >> 2] |= b64_char(v) << (8 * (j & 3));
+  }
+#pragma unroll
+  for (int k = 0; k < 3; k++) urls12[i * 3 + k] = w[k];
+  refs_out[i] = (int64_t)refs[i];
+}
+
+// hk[i] = the host of url id[i]
+__global__ __launch_bounds__(256) void k_uc_hostkeys(const uint32_t* __restrict__ id, int64_t n,
+                                                     const uint64_t* __restrict__ dkhi,
+                                                     const uint8_t* __restrict__ dklo, uint64_t* __restrict__ hk) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) hk[i] = host36(dkhi[id[i]], dklo[id[i]]);
+}
+
+// result i < n: host run r = run[i]: its key, its urls (the run's length) and its postings (psum: the
+// exclusive scan of the urls' references in host order), three words
+__global__ __launch_bounds__(256) void k_uc_hplace(const uint32_t* __restrict__ run, int64_t n,
+                                                   const uint64_t* __restrict__ rkey, const uint32_t* __restrict__ rpos,
+                                                   const uint32_t* __restrict__ psum, uint64_t* __restrict__ rec) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t r = run[i], lo = rpos[r], hi = rpos[r + 1];
+  rec[i * 3] = rkey[r];
+  rec[i * 3 + 1] = hi - lo;
+  rec[i * 3 + 2] = psum[hi] - psum[lo];
+}
+
+// scratch of a flag / scan over m + 1 elements
+struct UcScan {
+  int32_t* flag = nullptr;
+  int64_t* px = nullptr;
+  void* tmp = nullptr;
+  size_t tb = 0;
+};
+
+int uc_scan_alloc(yrwi_ctx* ctx, Lane* L, int64_t m, UcScan* X) {
+  X->flag = arena_alloc<int32_t>(L, m + 1);
+  X->px = arena_alloc<int64_t>(L, m + 1);
+  HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, X->tb, X->flag, X->px, (int)(m + 1), L->stream));
+  X->tmp = L->arena.alloc(X->tb);
+  if (!X->flag || !X->px || !X->tmp) return ctx->fail(YRWI_E_NOMEM, "device allocation (url census scan)");
+  return 0;
+}
+
+// flag, scan, the counters read back and waited for, the flagged candidates compacted: 4 launches, one sync.
+// -> *oid / *oref: the np flagged candidates in their order (at least one element each), ctr: the counters
+template <bool RUNS>
+int uc_tail(yrwi_ctx* ctx, Lane* L, const UcCand& C, const uint64_t* d_hk, int nh, uint32_t minr, UcScan& X,
+            unsigned long long* d_ctr, int64_t ctr[UC_WORDS], uint32_t** oid, uint32_t** oref, int64_t* np, Tally* T) {
+  const dim3 g((unsigned)std::min<int64_t>(blocks(C.m + 1), SPAN_BLOCKS)), b(256);
+  if (nh <= HOST_LDS_MAX)
+    hipLaunchKernelGGL((k_uc_flag<RUNS, true>), g, b, 0, L->stream, C, ctx->dkhi, ctx->dklo, d_hk, nh, minr, X.flag, d_ctr);
+  else
+    hipLaunchKernelGGL((k_uc_flag<RUNS, false>), g, b, 0, L->stream, C, ctx->dkhi, ctx->dklo, d_hk, nh, minr, X.flag, d_ctr);
+  HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(X.tmp, X.tb, X.flag, X.px, (int)(C.m + 1), L->stream));
+  HIPCHK(ctx, hipGetLastError());
+  const int64_t* h = reinterpret_cast<const int64_t*>(readback(L, &L->down_stage, d_ctr, UC_WORDS, 8, 8));
+  if (!h) return ctx->take(L, YRWI_E_HIP);
+  T->launches += 3;
+  HIPCHK(ctx, lane_sync(L));
+  T->syncs++;
+  std::memcpy(ctr, h, UC_WORDS * sizeof(int64_t));  // (the pinned landing buffer is reused)
+  *np = ctr[UC_PASSING];
+  *oid = arena_alloc<uint32_t>(L, *np);
+  *oref = arena_alloc<uint32_t>(L, *np);
+  if (!*oid || !*oref) return ctx->fail(YRWI_E_NOMEM, "device allocation (url census result)");
+  hipLaunchKernelGGL((k_uc_compact<RUNS>), dim3(std::max(blocks(C.m), 1u)), b, 0, L->stream, C, X.flag, X.px, *oid, *oref);
+  HIPCHK(ctx, hipGetLastError());
+  T->launches++;
+  return 0;
+}
+
+int bits_for(int64_t values) {  // bits that hold 0 .. values - 1, at least one
+  int b = 1;
+  while (b < 63 && ((int64_t)1 << b) < values) b++;
+  return b;
+}
+
+// What both calls share: arguments -> selection, url ids up to date, the counting pass on the chosen path and
+// the tail over its candidates.  -> *done: nothing was selected (S holds the empty result); else *oid / *oref:
+// the S->urls_passing urls with at least minr references and their host in the set, in id order.
+struct UcCall {
+  Tally T;
+  yrwi_ucensus_stats S;
+  HostPass P;
+  Lane* L = nullptr;
+  unsigned long long* d_ctr = nullptr;  // two counter blocks, zeroed: the urls' tail, the hosts' tail
+  uint32_t *oid = nullptr, *oref = nullptr;
+};
+
+int uc_urls(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uint8_t* hosts6, int32_t nhosts,
+            int64_t min_refs, UcCall* U, bool* done) {
+  std::memset(&U->S, 0, sizeof(U->S));
+  yrwi_ucensus_stats& S = U->S;
+  HostPass& P = U->P;
+  *done = true;
+  if (int rc = host_select(ctx, terms12, nterms, hosts6, nhosts, &P)) return rc;
+  if (P.jobs.empty()) return 0;
+  if (int rc = ensure_url_ids(ctx)) return rc;
+  // the repack behind new ids may have moved the lists: they are flattened again, with their ids beside them
+  ListSel sel;
+  if (int rc = select_lists(ctx, terms12, nterms, false, &sel)) return rc;
+  static_cast<RmTable&>(P) = RmTable();
+  rm_table(sel, &P);
+  std::vector<const uint32_t*> uids;
+  for (const auto& s : sel) uids.push_back(s.second->uid);
+  *done = false;
+  const int nj = (int)P.jobs.size(), nh = (int)P.hk.size();
+  const int64_t total = P.total, nd = ctx->nurls;
+  if (total >= (int64_t)INT32_MAX || nd >= (int64_t)INT32_MAX)
+    return ctx->fail(YRWI_E_LIMIT, "2^31 - 1 selected postings or dictionary urls or more");
+  S.lists = nj;
+  S.postings = total;
+  S.dict_urls = nd;
+  bool sort = total * UC_SORT_WEIGHT <= nd;
+  const char* forced = getenv("YRWI_UCENSUS_PATH");
+  if (forced && !strcmp(forced, "hist")) sort = false;
+  if (forced && !strcmp(forced, "sort")) sort = true;
+  S.path = sort ? YRWI_UCENSUS_SORT : YRWI_UCENSUS_HIST;
+  Lane* L = U->L = ctx->lanes[0];
+  const char* nomem = "device allocation (url census)";
+  PassDev D;
+  const uint32_t** d_uid = nullptr;
+  uint64_t* d_hk = nullptr;
+  if (int rc = pass_begin(ctx, L, P, 0, nomem, &D, &U->T, &d_uid, uids, &d_hk, P.hk)) return rc;
+  Tally& T = U->T;
+  const uint32_t minr = (uint32_t)std::min<int64_t>(std::max<int64_t>(min_refs, 1), (int64_t)UINT32_MAX);
+  const int64_t m = sort ? total : nd;  // the candidates of the tail: runs (no more than postings) or ids
+  // the counters sit in front of HIST's counts: one memset zeroes both
+  unsigned long long* blk = arena_alloc<unsigned long long>(L, 2 * UC_WORDS + (sort ? 0 : (nd + 1) / 2));
+  UcScan X;
+  if (!blk) return ctx->fail(YRWI_E_NOMEM, nomem);
+  if (int rc = uc_scan_alloc(ctx, L, m, &X)) return rc;
+  U->d_ctr = blk;
+  HIPCHK(ctx, hipMemsetAsync(blk, 0, (size_t)(2 * UC_WORDS + (sort ? 0 : (nd + 1) / 2)) * 8, L->stream));
+  T.launches++;
+  UcCand C{m, nullptr, nullptr, nullptr, nullptr};
+  const dim3 g(span_blocks(total)), b(256);
+  hipEvent_t e0 = L->event(), e1 = L->event();
+  if (!sort) {
+    uint32_t* cnt = reinterpret_cast<uint32_t*>(blk + 2 * UC_WORDS);
+    HIPCHK(ctx, hipEventRecord(e0, L->stream));
+    hipLaunchKernelGGL(k_uc_hist, g, b, 0, L->stream, D.jobs, D.off, d_uid, nj, total, nd, cnt);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(e1, L->stream));
+    T.launches++;
+    C.cnt = cnt;
+  } else {
+    uint32_t* ids = arena_alloc<uint32_t>(L, total);
+    uint32_t* sorted = arena_alloc<uint32_t>(L, total);
+    uint32_t* rid = arena_alloc<uint32_t>(L, total);
+    uint32_t* rpos = arena_alloc<uint32_t>(L, total + 1);
+    size_t tb = 0;
+    const int bits = bits_for(nd);
+    HIPCHK(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, tb, ids, sorted, (int)total, 0, bits, L->stream));
+    void* tmp = L->arena.alloc(tb);
+    int64_t* nruns = arena_alloc<int64_t>(L, 1);
+    if (!ids || !sorted || !rid || !rpos || !tmp || !nruns) return ctx->fail(YRWI_E_NOMEM, nomem);
+    HIPCHK(ctx, hipEventRecord(e0, L->stream));
+    hipLaunchKernelGGL(k_uc_gather, g, b, 0, L->stream, D.jobs, D.off, d_uid, nj, total, ids);
+    HIPCHK(ctx, hipcub::DeviceRadixSort::SortKeys(tmp, tb, ids, sorted, (int)total, 0, bits, L->stream));
+    hipLaunchKernelGGL((k_uc_heads<uint32_t>), dim3(blocks(total + 1)), b, 0, L->stream, sorted, total, X.flag);
+    HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(X.tmp, X.tb, X.flag, X.px, (int)(total + 1), L->stream));
+    // (the number of runs stays on the device: the tail reads it there)
+    hipLaunchKernelGGL((k_uc_runs<uint32_t>), dim3(blocks(total + 1)), b, 0, L->stream, sorted, total, X.flag, X.px, rid,
+                       rpos, nruns);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(e1, L->stream));
+    T.launches += 5;
+    C.rid = rid;
+    C.rpos = rpos;
+    C.nruns = nruns;
+  }
+  int64_t ctr[UC_WORDS], np = 0;
+  if (int rc = sort ? uc_tail<true>(ctx, L, C, d_hk, nh, minr, X, blk, ctr, &U->oid, &U->oref, &np, &T)
+                    : uc_tail<false>(ctx, L, C, d_hk, nh, minr, X, blk, ctr, &U->oid, &U->oref, &np, &T))
+    return rc;
+  float msf = 0.f;
+  if (hipEventElapsedTime(&msf, e0, e1) == hipSuccess) S.t_count_ns = (int64_t)((double)msf * 1e6);
+  (void)hipGetLastError();  // a statistics event that could not be read is not the call's error
+  S.urls = ctr[UC_URLS];
+  S.urls_hosted = ctr[UC_HOSTED];
+  S.urls_passing = ctr[UC_PASSING];
+  S.max_refs = ctr[UC_MAXREFS];
+  return 0;
+}
+
+void uc_finish(UcCall& U, std::chrono::steady_clock::time_point t_begin, int64_t n, int64_t* nout,
+               yrwi_ucensus_stats* st) {
+  U.S.launches = U.T.launches;
+  U.S.syncs = U.T.syncs;
+  U.S.t_total_ns =
+      std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_begin).count();
+  if (nout) *nout = n;
+  if (st) *st = U.S;
+}
+
+}  // namespace
+
+extern "C" int yrwi_url_census(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, const uint8_t* hosts6,
+                               int32_t nhosts, int32_t order, int64_t min_refs, uint8_t* urls12_out, int64_t* refs_out,
+                               int64_t cap, int64_t* nout, yrwi_ucensus_stats* st) {
+  if (!ctx || nterms < 0 || nhosts < 0 || (nterms > 0 && !terms12) || (nhosts > 0 && !hosts6)) return YRWI_E_ARG;
+  if (order != YRWI_UCENSUS_BY_URL && order != YRWI_UCENSUS_BY_REFS) return ctx->fail(YRWI_E_ARG, "unknown url census order");
+  if (cap < 0 || (cap > 0 && (!urls12_out || !refs_out))) return ctx->fail(YRWI_E_ARG, "url census capacity without buffers");
+  const auto t_begin = std::chrono::steady_clock::now();
+  UcCall U;
+  bool done = false;
+  if (int rc = uc_urls(ctx, terms12, nterms, hosts6, nhosts, min_refs, &U, &done)) return rc;
+  if (done) {
+    uc_finish(U, t_begin, 0, nout, st);
+    return 0;
+  }
+  Lane* L = U.L;
+  Tally& T = U.T;
+  // ---- BY_REFS: one stable sort by references descending (equal references stay in url order); the first
+  //      min(urls_passing, cap) get their characters and cross to the host
+  const int64_t np = U.S.urls_passing, nw = std::min(np, cap);
+  const int ns = (int)std::max<int64_t>(np, 1);  // (no url passes: the sort runs over one unused element)
+  const uint32_t *rid = U.oid, *rref = U.oref;
+  if (order == YRWI_UCENSUS_BY_REFS) {
+    uint32_t* sid = arena_alloc<uint32_t>(L, ns);
+    uint32_t* sref = arena_alloc<uint32_t>(L, ns);
+    const int rb = bits_for(U.S.lists + 1);  // no url has more references than there are lists
+    size_t tb = 0;
+    HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb, U.oref, sref, U.oid, sid, ns, 0, rb, L->stream));
+    void* tmp = L->arena.alloc(tb);
+    if (!sid || !sref || !tmp) return ctx->fail(YRWI_E_NOMEM, "device allocation (url census sort)");
+    HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairsDescending(tmp, tb, U.oref, sref, U.oid, sid, ns, 0, rb, L->stream));
+    T.launches++;
+    rid = sid;
+    rref = sref;
+  }
+  uint32_t* d_urls = arena_alloc<uint32_t>(L, nw * 3);
+  int64_t* d_refs = arena_alloc<int64_t>(L, nw);
+  if (!d_urls || !d_refs) return ctx->fail(YRWI_E_NOMEM, "device allocation (url census output)");
+  hipLaunchKernelGGL(k_uc_place, dim3(std::max(blocks(nw), 1u)), dim3(256), 0, L->stream, rid, rref, nw, ctx->dkhi,
+                     ctx->dklo, d_urls, d_refs);
+  HIPCHK(ctx, hipGetLastError());
+  const uint8_t* hu = readback(L, &L->out_stage, d_urls, nw, 12, 12);
+  const uint8_t* hr = readback(L, &L->down_stage, d_refs, nw, 8, 8);
+  if (!hu || !hr) return ctx->take(L, YRWI_E_HIP);
+  T.launches += 3;
+  HIPCHK(ctx, lane_sync(L));
+  T.syncs++;
+  if (nw > 0) {
+    std::memcpy(urls12_out, hu, (size_t)nw * 12);
+    std::memcpy(refs_out, hr, (size_t)nw * 8);
+  }
+  uc_finish(U, t_begin, nw, nout, st);
+  return 0;
+}
+
+extern "C" int yrwi_host_url_census(yrwi_ctx* ctx, const uint8_t* terms12, int32_t nterms, int32_t order,
+                                    int64_t min_urls, uint8_t* hosts6_out, int64_t* urls_out, int64_t* postings_out,
+                                    int64_t cap, int64_t* nout, yrwi_ucensus_stats* st) {
+  if (!ctx || nterms < 0 || (nterms > 0 && !terms12)) return YRWI_E_ARG;
+  if (order != YRWI_CENSUS_BY_HOST && order != YRWI_CENSUS_BY_COUNT) return ctx->fail(YRWI_E_ARG, "unknown census order");
+  if (cap < 0 || (cap > 0 && (!hosts6_out || !urls_out || !postings_out)))
+    return ctx->fail(YRWI_E_ARG, "url census capacity without buffers");
+  const auto t_begin = std::chrono::steady_clock::now();
+  UcCall U;
+  bool done = false;
+  if (int rc = uc_urls(ctx, terms12, nterms, nullptr, 0, 1, &U, &done)) return rc;
+  if (done) {
+    uc_finish(U, t_begin, 0, nout, st);
+    return 0;
+  }
+  Lane* L = U.L;
+  Tally& T = U.T;
+  const char* nomem = "device allocation (host url census)";
+  // ---- the nu distinct urls as (host, refs), sorted by host; the runs of a host: its urls; the scanned refs
+  //      at a run's ends: its postings
+  const int64_t nu = U.S.urls_passing;
+  const int ns = (int)std::max<int64_t>(nu, 1);
+  const dim3 b(256);
+  uint64_t* hk = arena_alloc<uint64_t>(L, ns);
+  uint64_t* hk2 = arena_alloc<uint64_t>(L, ns);
+  uint32_t* ref2 = arena_alloc<uint32_t>(L, ns + 1);
+  uint32_t* psum = arena_alloc<uint32_t>(L, ns + 1);
+  uint64_t* rkey = arena_alloc<uint64_t>(L, ns);
+  uint32_t* rpos = arena_alloc<uint32_t>(L, ns + 1);
+  int64_t* nruns = arena_alloc<int64_t>(L, 1);
+  UcScan X;
+  if (int rc = uc_scan_alloc(ctx, L, nu, &X)) return rc;
+  size_t t1 = 0, t2 = 0;
+  HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, t1, hk, hk2, U.oref, ref2, ns, 0, 36, L->stream));
+  HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t2, ref2, psum, ns + 1, L->stream));
+  void* tmp = L->arena.alloc(std::max(t1, t2));
+  if (!hk || !hk2 || !ref2 || !psum || !rkey || !rpos || !nruns || !tmp) return ctx->fail(YRWI_E_NOMEM, nomem);
+  hipLaunchKernelGGL(k_uc_hostkeys, dim3(std::max(blocks(nu), 1u)), b, 0, L->stream, U.oid, nu, ctx->dkhi, ctx->dklo, hk);
+  HIPCHK(ctx, hipMemsetAsync(ref2, 0, (size_t)(ns + 1) * 4, L->stream));  // (the scan reads one element more than the sort writes)
+  HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairs(tmp, t1, hk, hk2, U.oref, ref2, ns, 0, 36, L->stream));
+  HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(tmp, t2, ref2, psum, ns + 1, L->stream));
+  hipLaunchKernelGGL((k_uc_heads<uint64_t>), dim3(blocks(nu + 1)), b, 0, L->stream, hk2, nu, X.flag);
+  HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(X.tmp, X.tb, X.flag, X.px, (int)(nu + 1), L->stream));
+  hipLaunchKernelGGL((k_uc_runs<uint64_t>), dim3(blocks(nu + 1)), b, 0, L->stream, hk2, nu, X.flag, X.px, rkey, rpos,
+                     nruns);
+  HIPCHK(ctx, hipGetLastError());
+  T.launches += 7;
+  // ---- the hosts with at least min_urls urls: the tail of the urls over the runs (a run's "references" are its urls)
+  const uint32_t minu = (uint32_t)std::min<int64_t>(std::max<int64_t>(min_urls, 1), (int64_t)UINT32_MAX);
+  const UcCand C{nu, nullptr, nullptr, rpos, nruns};
+  int64_t ctr[UC_WORDS], np = 0;
+  uint32_t *orun = nullptr, *ourls = nullptr;
+  if (int rc = uc_tail<true>(ctx, L, C, nullptr, 0, minu, X, U.d_ctr + UC_WORDS, ctr, &orun, &ourls, &np, &T)) return rc;
+  U.S.hosts = ctr[UC_URLS];
+  U.S.hosts_passing = np;
+  const int64_t nw = std::min(np, cap);
+  const int nr = (int)std::max<int64_t>(np, 1);
+  const uint32_t* run = orun;  // already BY_HOST: the runs ascend by host
+  if (order == YRWI_CENSUS_BY_COUNT) {  // stable: equal url counts stay in host order
+    uint32_t* srun = arena_alloc<uint32_t>(L, nr);
+    uint32_t* surls = arena_alloc<uint32_t>(L, nr);
+    const int cb = bits_for(nu + 1);
+    size_t tb = 0;
+    HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb, ourls, surls, orun, srun, nr, 0, cb, L->stream));
+    void* stmp = L->arena.alloc(tb);
+    if (!srun || !surls || !stmp) return ctx->fail(YRWI_E_NOMEM, nomem);
+    HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairsDescending(stmp, tb, ourls, surls, orun, srun, nr, 0, cb, L->stream));
+    T.launches++;
+    run = srun;
+  }
+  uint64_t* rec = arena_alloc<uint64_t>(L, nw * 3);
+  if (!rec) return ctx->fail(YRWI_E_NOMEM, nomem);
+  hipLaunchKernelGGL(k_uc_hplace, dim3(std::max(blocks(nw), 1u)), b, 0, L->stream, run, nw, rkey, rpos, psum, rec);
+  HIPCHK(ctx, hipGetLastError());
+  const uint64_t* hrec = reinterpret_cast<const uint64_t*>(readback(L, &L->out_stage, rec, nw, 24, 24));
+  if (!hrec) return ctx->take(L, YRWI_E_HIP);
+  T.launches += 2;
+  HIPCHK(ctx, lane_sync(L));
+  T.syncs++;
+  for (int64_t i = 0; i < nw; i++) {
+    for (int j = 0; j < 6; j++) hosts6_out[i * 6 + j] = (uint8_t)ALPHA[(hrec[i * 3] >> (6 * (5 - j))) & 63];
+    urls_out[i] = (int64_t)hrec[i * 3 + 1];
+    postings_out[i] = (int64_t)hrec[i * 3 + 2];
+  }
+  uc_finish(U, t_begin, nw, nout, st);
+  return 0;
 }
 
 // ---------------------------------------------------------------- retention: age and cap

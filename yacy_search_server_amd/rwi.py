@@ -500,6 +500,68 @@ class RWIIndex:
         return ([bytes(h) for h in hosts[:n.value]], counts[:n.value].copy(),
                 {f: getattr(st, f) for f, _ in _lib.CCensusStats._fields_})
 
+    def url_census(self, terms: Optional[Sequence[bytes]] = None, hosts: Optional[Sequence[bytes]] = None,
+                   order: str = "refs", min_refs: int = 1,
+                   top: Optional[int] = None) -> Tuple[List[bytes], np.ndarray, dict]:
+        """Which urls have postings in the lists of `terms`, or with terms=None in every list, and in
+        how many of those lists each (yrwi_url_census): the urls with at least min_refs references
+        and, with `hosts` (6-byte host hashes), of those hosts only, by order="refs" (references
+        descending, equal references by url hash) or "url" (ascending url hash), all of them or the
+        first `top`.  Returns (12-byte url hashes, their references as int64 -- the counts
+        url_references gives for them --, the call's yrwi_ucensus_stats as a dict).  No list leaves
+        the device; with top=None a first call asks how many urls pass (cap 0) and a second one
+        fetches them."""
+        o = _lib.UCENSUS_ORDERS[order]
+        if top is not None and top < 0:
+            raise ValueError("top must not be negative")
+        hb, tb = self._host_args(hosts or (), terms)
+        st = _lib.CUCensusStats()
+        if terms is not None and len(terms) == 0:  # no term named (nterms == 0 would mean every list)
+            return [], np.zeros(0, dtype=np.int64), {f: 0 for f, _ in _lib.CUCensusStats._fields_}
+        call = lambda urls, refs, cap, n: _check(self._h, _lib.lib().yrwi_url_census(
+            self._h, tb.ctypes.data if len(tb) else None, len(tb) // 12, hb.ctypes.data if len(hb) else None,
+            len(hb) // 6, o, min_refs, urls, refs, cap, n, ctypes.byref(st)))
+        if top is None:
+            call(None, None, 0, None)
+            top = st.urls_passing
+        urls = np.zeros((top, 12), dtype=np.uint8)
+        refs = np.zeros(top, dtype=np.int64)
+        n = ctypes.c_int64()
+        call(urls.ctypes.data if top else None, refs.ctypes.data if top else None, top, ctypes.byref(n))
+        return ([bytes(u) for u in urls[:n.value]], refs[:n.value].copy(),
+                {f: getattr(st, f) for f, _ in _lib.CUCensusStats._fields_})
+
+    def host_url_census(self, terms: Optional[Sequence[bytes]] = None, order: str = "count", min_urls: int = 1,
+                        top: Optional[int] = None) -> Tuple[List[bytes], np.ndarray, np.ndarray, dict]:
+        """Which hosts have urls in the lists of `terms`, or with terms=None in every list, how many
+        distinct urls and how many postings each (yrwi_host_url_census): the hosts with at least
+        min_urls urls, by order="count" (urls descending, equal counts by host hash) or "host"
+        (ascending host hash), all of them or the first `top`.  Returns (6-byte host hashes, their
+        distinct urls as int64, their postings as int64 -- what host_census gives for them --, the
+        call's yrwi_ucensus_stats as a dict).  With top=None a first call asks how many hosts pass."""
+        o = _lib.CENSUS_ORDERS[order]
+        if top is not None and top < 0:
+            raise ValueError("top must not be negative")
+        tb = np.frombuffer(_hashes(terms or ()), dtype=np.uint8)
+        st = _lib.CUCensusStats()
+        if terms is not None and len(terms) == 0:  # no term named (nterms == 0 would mean every list)
+            none = np.zeros(0, dtype=np.int64)
+            return [], none, none.copy(), {f: 0 for f, _ in _lib.CUCensusStats._fields_}
+        call = lambda hosts, urls, posts, cap, n: _check(self._h, _lib.lib().yrwi_host_url_census(
+            self._h, tb.ctypes.data if len(tb) else None, len(tb) // 12, o, min_urls, hosts, urls, posts, cap, n,
+            ctypes.byref(st)))
+        if top is None:
+            call(None, None, None, 0, None)
+            top = st.hosts_passing
+        hosts = np.zeros((top, 6), dtype=np.uint8)
+        urls = np.zeros(top, dtype=np.int64)
+        posts = np.zeros(top, dtype=np.int64)
+        n = ctypes.c_int64()
+        call(hosts.ctypes.data if top else None, urls.ctypes.data if top else None,
+             posts.ctypes.data if top else None, top, ctypes.byref(n))
+        return ([bytes(h) for h in hosts[:n.value]], urls[:n.value].copy(), posts[:n.value].copy(),
+                {f: getattr(st, f) for f, _ in _lib.CUCensusStats._fields_})
+
     @staticmethod
     def _retention_noop() -> dict:
         st = {f: 0 for f, _ in _lib.CRetentionStats._fields_}
