@@ -1004,6 +1004,59 @@ typedef struct yrwi_tsb_stats {
 } yrwi_tsb_stats;
 int yrwi_term_search_batch(yrwi_ctx* ctx, const yrwi_query_desc* q, int32_t nq, uint8_t* rows40_out,
                            int64_t cap_rows, int64_t* row_off /* nq + 1 */, yrwi_tsb_stats* st);
+/* Host facets of a query batch: per descriptor the hosts of its joined container and how many
+ * postings each has -- the per-host score map a search event keeps for its "results by domain"
+ * navigator (UNVERIFIED against a reference line: the reference counts hosts per search event
+ * while results arrive and has no batch method for this).  Defined through this header: let R_i
+ * be the rows yrwi_term_search_batch returns for descriptor i (exclusions, max_distance,
+ * urlselection and now_ms honoured; k, profile, language and filter unused).  R_i is grouped by
+ * host hash, the url-hash characters 6..11 (as yrwi_filter.sitehash).  nrows[i] = |R_i|,
+ * nhosts[i] = its distinct hosts.  The hosts of query i are put in `order` and the first
+ * min(nhosts[i], max_hosts) of them (max_hosts == 0: all) are written at index host_off[i] up to
+ * host_off[i + 1]: six characters into hosts6_out, the host's postings in R_i into counts_out
+ * and, when urls12_out is given, the smallest url hash of that host in R_i (a host name can
+ * only be resolved through a url).  host_off[0] = 0; an empty R_i (an absent include term, an
+ * empty join, a fully excluded container) is an empty range, not an error; identical
+ * descriptors each get their own range; a host of several queries is counted per query.
+ *   Capacity: hosts6_out == NULL && counts_out == NULL only counts (host_off, nhosts, nrows and
+ * st are filled; the total is not compared with cap; urls12_out must be NULL too).  Otherwise both are given
+ * and hold cap entries each (urls12_out 12 cap bytes); when host_off[nq] > cap the call returns
+ * YRWI_E_ARG with host_off, nhosts and nrows filled and no byte of the three buffers written.
+ *   Errors: planning errors return before anything is written and yrwi_last_error starts with
+ * "query <index>: ".  An order outside YRWI_FACETS_BY_*, max_hosts < 0, cap < 0, nq < 0, a NULL q
+ * or host_off with nq > 0, or only one of hosts6_out / counts_out: YRWI_E_ARG.  nq == 0 returns 0
+ * with host_off[0] = 0; nq > 2^27 or 2^31 container rows in one call: YRWI_E_LIMIT.  A context
+ * of a shard group (world > 1): YRWI_E_UNSUPPORTED, as yrwi_term_search_batch.  Waits for the
+ * batches in flight and changes nothing in the context -- the dense host ids of the authority
+ * path are neither needed nor built; scratch comes from lane 0's arena.  nhosts, nrows and st
+ * may be NULL.
+ *   Shape of the call: after the join phase one upload, the three kernels of the counting
+ * yrwi_term_search_batch (the kept rows per query), seven launches of the group-by
+ * (k_facet_keys, sort, k_facet_flag, scan, k_facet_runs, k_facet_query, scan) and ONE readback
+ * of 3 nq + 2 words (host_off, nhosts, the kept-row offsets): launches_tail = 12 and one host
+ * wait for a counting call, for one whose total exceeds cap and for one that has no host to
+ * write.  A call that writes adds k_facet_pack and two copies (three with urls12_out), sized by
+ * the total and so behind the first wait, and YRWI_FACETS_BY_COUNT two more launches (count
+ * keys, sort) in front of them:
+ *     launches_tail = 15 + (urls12_out ? 1 : 0) + (BY_COUNT ? 2 : 0), syncs = 2.
+ * Neither depends on nq, on the lists or on their lengths.  A call whose containers are all
+ * empty before the exclusion enqueues nothing after the join phase.  bytes_d2h = 8 (3 nq + 2)
+ * + 14 hosts_out (26 hosts_out with urls12_out); a urlselection's planning reads its url ids
+ * back besides. */
+#define YRWI_FACETS_BY_HOST  0   /* ascending host hash (36-bit key order) */
+#define YRWI_FACETS_BY_COUNT 1   /* postings descending; equal counts by ascending host hash */
+typedef struct yrwi_facet_stats {
+  int64_t rows_joined, rows_kept;  /* as yrwi_tsb_stats.rows_joined / rows_out */
+  int64_t hosts, hosts_out;        /* sum over the queries of distinct hosts / of hosts written (host_off[nq]) */
+  int64_t bytes_h2d, bytes_d2h;    /* everything the call moved over PCIe */
+  int32_t launches_tail, syncs;    /* launches and copies enqueued, and host waits, after the join phase */
+  int64_t device_allocs;           /* yrwi_realloc_events of the call */
+  int64_t t_group_ns, t_total_ns;  /* HIP events around key, sort, heads, order, pack; wall time */
+} yrwi_facet_stats;
+int yrwi_host_facets_batch(yrwi_ctx* ctx, const yrwi_query_desc* q, int32_t nq, int32_t order, int32_t max_hosts,
+                           uint8_t* hosts6_out, int64_t* counts_out, uint8_t* urls12_out /* may be NULL */,
+                           int64_t cap, int64_t* host_off /* nq + 1 */, int64_t* nhosts /* nq, may be NULL */,
+                           int64_t* nrows /* nq, may be NULL */, yrwi_facet_stats* st);
 int yrwi_normalize_score(yrwi_ctx* ctx, const uint8_t* rows40, int64_t m, const yrwi_profile* prof,
                          const char* language, int64_t now_ms, int64_t* score_out);
 

@@ -410,6 +410,108 @@ JNIEXPORT jbyteArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_termSearchBatch(
   return res;
 }
 
+/* The hosts of the joined container of nq queries and their postings (yrwi_host_facets_batch).
+ * The queries are given as for termSearchBatch.  order: YRWI_FACETS_BY_*; maxHosts: the most
+ * hosts per query (0: all); wantUrls: each host's smallest url hash as well.  Sized by a counting
+ * call.  Returns Object[3] {byte[] hosts (n * 6), long[] counts (n), byte[] urls (n * 12) or
+ * null}, n = hostOff[nq], and fills hostOff (nq + 1), nhosts and nrows (nq each, or null) and
+ * stats (long[11] or null: the fields of yrwi_facet_stats in their order); NULL on error. */
+JNIEXPORT jobjectArray JNICALL Java_net_yacy_kelondro_rwi_GpuRWI_hostFacets(
+    JNIEnv* env, jclass c, jlong ctx, jint nq, jbyteArray incl, jintArray nincl, jbyteArray excl, jintArray nexcl,
+    jbyteArray sel, jintArray nsel, jintArray maxd, jlongArray now, jint order, jint maxHosts, jboolean wantUrls,
+    jlongArray hostOff, jlongArray nhosts, jlongArray nrows, jlongArray stats) {
+  yrwi_ctx* x = (yrwi_ctx*)(intptr_t)ctx;
+  if (nq < 0 || !incl || !nincl || !excl || !nexcl || !maxd || !now || !hostOff || (sel && !nsel) ||
+      (*env)->GetArrayLength(env, nincl) < nq || (*env)->GetArrayLength(env, nexcl) < nq ||
+      (*env)->GetArrayLength(env, maxd) < nq || (*env)->GetArrayLength(env, now) < nq ||
+      (*env)->GetArrayLength(env, hostOff) < nq + 1 || (sel && (*env)->GetArrayLength(env, nsel) < nq) ||
+      (nhosts && (*env)->GetArrayLength(env, nhosts) < nq) || (nrows && (*env)->GetArrayLength(env, nrows) < nq))
+    return NULL;
+  jint* ni = (*env)->GetIntArrayElements(env, nincl, NULL);
+  jint* ne = (*env)->GetIntArrayElements(env, nexcl, NULL);
+  jint* ns = sel ? (*env)->GetIntArrayElements(env, nsel, NULL) : NULL;
+  jint* md = (*env)->GetIntArrayElements(env, maxd, NULL);
+  jlong* nw = (*env)->GetLongArrayElements(env, now, NULL);
+  int64_t ti = 0, te = 0, ts = 0;
+  int ok = 1;
+  for (jint i = 0; i < nq; i++) {
+    if (ni[i] < 0 || ne[i] < 0 || (ns && ns[i] < 0)) ok = 0;
+    ti += ni[i];
+    te += ne[i];
+    ts += ns ? ns[i] : 0;
+  }
+  uint8_t* ib = ok ? copy_in(env, incl, ti * 12) : NULL;
+  uint8_t* eb = ib ? copy_in(env, excl, te * 12) : NULL;
+  uint8_t* sb = eb && sel ? copy_in(env, sel, ts * 12) : NULL;
+  yrwi_query_desc* q = (yrwi_query_desc*)calloc((size_t)nq + 1, sizeof(yrwi_query_desc));
+  int64_t* off = (int64_t*)calloc(3 * (size_t)nq + 3, sizeof(int64_t)); /* hostOff, nhosts, nrows */
+  int64_t *nh = off ? off + nq + 1 : NULL, *nr = off ? off + 2 * (size_t)nq + 2 : NULL;
+  uint8_t *h6 = NULL, *u12 = NULL;
+  int64_t* cnt = NULL;
+  yrwi_facet_stats st;
+  memset(&st, 0, sizeof(st));
+  int rc = ib && eb && (!sel || sb) && q && off ? 0 : YRWI_E_NOMEM;
+  if (rc == 0) {
+    int64_t oi = 0, oe = 0, os = 0;
+    for (jint i = 0; i < nq; i++) {
+      q[i].incl = ib + 12 * oi; q[i].nincl = ni[i];
+      q[i].excl = eb + 12 * oe; q[i].nexcl = ne[i];
+      q[i].max_distance = md[i]; q[i].k = 1; q[i].now_ms = nw[i];
+      if (ns && ns[i] > 0) { q[i].urlselection = sb + 12 * os; q[i].nurlselection = ns[i]; }
+      oi += ni[i]; oe += ne[i]; os += ns ? ns[i] : 0;
+    }
+    rc = yrwi_host_facets_batch(x, q, nq, order, maxHosts, NULL, NULL, NULL, 0, off, NULL, NULL, NULL); /* counts only */
+  }
+  (*env)->ReleaseIntArrayElements(env, nincl, ni, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, nexcl, ne, JNI_ABORT);
+  if (ns) (*env)->ReleaseIntArrayElements(env, nsel, ns, JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, maxd, md, JNI_ABORT);
+  (*env)->ReleaseLongArrayElements(env, now, nw, JNI_ABORT);
+  const int64_t n = rc == 0 ? off[nq] : 0;
+  if (rc == 0 && n * 12 > 2147483647LL) rc = YRWI_E_LIMIT; /* a Java array holds at most 2^31 - 1 elements */
+  if (rc == 0) {
+    h6 = (uint8_t*)malloc((size_t)(n > 0 ? n * 6 : 1));
+    cnt = (int64_t*)malloc((size_t)(n > 0 ? n : 1) * sizeof(int64_t));
+    u12 = wantUrls ? (uint8_t*)malloc((size_t)(n > 0 ? n * 12 : 1)) : NULL;
+    rc = h6 && cnt && (!wantUrls || u12)
+             ? yrwi_host_facets_batch(x, q, nq, order, maxHosts, h6, cnt, u12, n, off, nh, nr, &st)
+             : YRWI_E_NOMEM;
+  }
+  jobjectArray res = NULL;
+  if (rc == 0) {
+    jclass oc = (*env)->FindClass(env, "java/lang/Object");
+    jbyteArray jh = (*env)->NewByteArray(env, (jsize)(n * 6));
+    jlongArray jc = (*env)->NewLongArray(env, (jsize)n);
+    jbyteArray ju = wantUrls ? (*env)->NewByteArray(env, (jsize)(n * 12)) : NULL;
+    if (oc && jh && jc && (!wantUrls || ju)) res = (*env)->NewObjectArray(env, 3, oc, NULL);
+    if (res) {
+      (*env)->SetByteArrayRegion(env, jh, 0, (jsize)(n * 6), (const jbyte*)h6);
+      (*env)->SetLongArrayRegion(env, jc, 0, (jsize)n, (const jlong*)cnt);
+      if (ju) (*env)->SetByteArrayRegion(env, ju, 0, (jsize)(n * 12), (const jbyte*)u12);
+      (*env)->SetObjectArrayElement(env, res, 0, jh);
+      (*env)->SetObjectArrayElement(env, res, 1, jc);
+      (*env)->SetObjectArrayElement(env, res, 2, ju);
+      (*env)->SetLongArrayRegion(env, hostOff, 0, nq + 1, (const jlong*)off);
+      if (nhosts) (*env)->SetLongArrayRegion(env, nhosts, 0, nq, (const jlong*)nh);
+      if (nrows) (*env)->SetLongArrayRegion(env, nrows, 0, nq, (const jlong*)nr);
+      if (stats && (*env)->GetArrayLength(env, stats) >= 11) {
+        const jlong v[11] = {st.rows_joined, st.rows_kept, st.hosts, st.hosts_out, st.bytes_h2d, st.bytes_d2h,
+                             st.launches_tail, st.syncs, st.device_allocs, st.t_group_ns, st.t_total_ns};
+        (*env)->SetLongArrayRegion(env, stats, 0, 11, v);
+      }
+    }
+  }
+  free(ib);
+  free(eb);
+  free(sb);
+  free(q);
+  free(off);
+  free(h6);
+  free(cnt);
+  free(u12);
+  return res;
+}
+
 /* joinExclude into a direct ByteBuffer the caller owns and reuses (no JNI array copy
  * of the joined container): returns m (rows written, 40 bytes each) or the (negative)
  * error code -- YRWI_E_ARG when the container holds more rows than capacity / 40. */

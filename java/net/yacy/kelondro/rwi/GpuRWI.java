@@ -342,6 +342,65 @@ public final class GpuRWI implements AutoCloseable {
         return rows;
     }
 
+    /** yrwi_host_facets_batch orders. */
+    public static final int FACETS_BY_HOST = 0, FACETS_BY_COUNT = 1;
+
+    /** What hostFacets returns: per query the hosts of its joined container.  Query i owns the
+     *  entries hostOff[i] .. hostOff[i + 1] of hosts (6 bytes each), counts and urls (12 bytes
+     *  each, or null when not asked for). */
+    public static final class HostFacets {
+        public final byte[] hosts;    // host hashes (url-hash characters 6..11), 6 bytes each
+        public final long[] counts;   // postings of each host in its query's container
+        public final byte[] urls;     // the smallest url hash of each host in that container, or null
+        public final long[] hostOff;  // nq + 1 entry offsets
+        public final long[] nhosts;   // distinct hosts of every query (before the maxHosts cut)
+        public final long[] nrows;    // rows of every query's container
+        /** the fields of yrwi_facet_stats in their order */
+        public final long[] stats;
+
+        HostFacets(final byte[] hosts, final long[] counts, final byte[] urls, final long[] hostOff,
+                   final long[] nhosts, final long[] nrows, final long[] stats) {
+            this.hosts = hosts;
+            this.counts = counts;
+            this.urls = urls;
+            this.hostOff = hostOff;
+            this.nhosts = nhosts;
+            this.nrows = nrows;
+            this.stats = stats;
+        }
+
+        /** the host hash of entry j */
+        public byte[] host(final int j) {
+            return java.util.Arrays.copyOfRange(this.hosts, 6 * j, 6 * j + 6);
+        }
+    }
+
+    /** The "results by domain" navigator of many queries in one pass (yrwi_host_facets_batch):
+     *  per query the hosts of its joined container (the rows termSearchBatch returns for it),
+     *  the postings of each and, with wantUrls, each host's smallest url hash -- a host name is
+     *  resolved through a url.  order: FACETS_BY_HOST or FACETS_BY_COUNT (postings descending,
+     *  equal counts by ascending host hash); maxHosts: the most hosts per query, 0: all.  The
+     *  queries are given as for termSearchBatch.  Only the triples leave the device. */
+    public synchronized HostFacets hostFacets(final byte[][][] include, final byte[][][] exclude,
+                                              final byte[][][] urlselection, final int[] maxDistance,
+                                              final long[] nowMillis, final int order, final int maxHosts,
+                                              final boolean wantUrls) {
+        final int nq = include.length;
+        final int[] ni = new int[nq], ne = new int[nq], ns = new int[nq];
+        for (int i = 0; i < nq; i++) {
+            ni[i] = include[i].length;
+            ne[i] = exclude[i] == null ? 0 : exclude[i].length;
+            ns[i] = urlselection == null || urlselection[i] == null ? 0 : urlselection[i].length;
+        }
+        final long[] hostOff = new long[nq + 1], nhosts = new long[nq], nrows = new long[nq], stats = new long[11];
+        final Object[] r = hostFacets(this.ctx, nq, flatten3(include), ni, flatten3(exclude), ne,
+                                      urlselection == null ? null : flatten3(urlselection),
+                                      urlselection == null ? null : ns, maxDistance, nowMillis, order, maxHosts,
+                                      wantUrls, hostOff, nhosts, nrows, stats);
+        if (r == null) throw new IllegalStateException("yrwi_host_facets_batch failed");
+        return new HostFacets((byte[]) r[0], (long[]) r[1], (byte[]) r[2], hostOff, nhosts, nrows, stats);
+    }
+
     /** joinExclude into a caller-owned direct buffer (ByteBuffer.allocateDirect, reused
      *  across queries): no copy of the joined container through a Java array.  Returns
      *  the number of 40-byte rows written; throws when the container does not fit. */
@@ -712,6 +771,10 @@ public final class GpuRWI implements AutoCloseable {
     private static native byte[] termSearchBatch(long ctx, int nq, byte[] incl, int[] nincl, byte[] excl, int[] nexcl,
                                                  byte[] sel, int[] nsel, int[] maxDistance, long[] nowMillis,
                                                  long[] rowOff);
+    private static native Object[] hostFacets(long ctx, int nq, byte[] incl, int[] nincl, byte[] excl, int[] nexcl,
+                                              byte[] sel, int[] nsel, int[] maxDistance, long[] nowMillis, int order,
+                                              int maxHosts, boolean wantUrls, long[] hostOff, long[] nhosts,
+                                              long[] nrows, long[] stats);
     private static native long joinExcludeInto(long ctx, byte[] incl, int nincl, byte[] excl, int nexcl,
                                                int maxDistance, long nowMillis, java.nio.ByteBuffer out);
     private static native byte[] query(long ctx, byte[] incl, int nincl, byte[] excl, int nexcl, int maxDistance,

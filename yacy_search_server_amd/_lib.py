@@ -106,6 +106,17 @@ class CTsbStats(ctypes.Structure):
                 ("t_total_ns", ctypes.c_int64)]
 
 
+class CFacetStats(ctypes.Structure):
+    _fields_ = [("rows_joined", ctypes.c_int64), ("rows_kept", ctypes.c_int64), ("hosts", ctypes.c_int64),
+                ("hosts_out", ctypes.c_int64), ("bytes_h2d", ctypes.c_int64), ("bytes_d2h", ctypes.c_int64),
+                ("launches_tail", ctypes.c_int32), ("syncs", ctypes.c_int32), ("device_allocs", ctypes.c_int64),
+                ("t_group_ns", ctypes.c_int64), ("t_total_ns", ctypes.c_int64)]
+
+
+FACETS_BY_HOST, FACETS_BY_COUNT = 0, 1  # YRWI_FACETS_BY_*: the orders of yrwi_host_facets_batch
+FACETS_ORDERS = {"host": FACETS_BY_HOST, "count": FACETS_BY_COUNT}
+
+
 class CEventInfo(ctypes.Structure):
     _fields_ = [("flagcount", ctypes.c_int32 * 32), ("postings_in", ctypes.c_int64),
                 ("admitted_local", ctypes.c_int64), ("admitted_remote", ctypes.c_int64),
@@ -329,6 +340,9 @@ SIGNATURES = {
                                         ctypes.POINTER(ctypes.c_int64)]),
     "yrwi_term_search_batch": (ctypes.c_int, [_VP, ctypes.POINTER(CQuery), ctypes.c_int32, _VP, ctypes.c_int64, _VP,
                                               ctypes.POINTER(CTsbStats)]),
+    "yrwi_host_facets_batch": (ctypes.c_int, [_VP, ctypes.POINTER(CQuery), ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.c_int32, _VP, _VP, _VP, ctypes.c_int64, _VP, _VP, _VP,
+                                              ctypes.POINTER(CFacetStats)]),
     "yrwi_normalize_score": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.POINTER(CProfile), ctypes.c_char_p,
                                             ctypes.c_int64, _VP]),
 }

@@ -1,7 +1,8 @@
 // yrwi_device.h -- device helpers of the index-maintenance sources (yrwi_update.hip,
-// yrwi_load.hip, yrwi_dict.hip, yrwi_dump.hip, yrwi_dht.hip): the searches and copies of the
-// code that reads or rewrites the index in place, each defined once.  The query path
-// (yrwi_kernels.hip) has its own and does not include this.
+// yrwi_load.hip, yrwi_dict.hip, yrwi_dump.hip, yrwi_dht.hip) and of the host facets
+// (yrwi_facets.hip): the searches and copies of the code that reads or rewrites the index in
+// place, each defined once.  The query path (yrwi_kernels.hip) has its own and does not
+// include this.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -18,10 +19,14 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef u32x4 __attribute__((address_space(1))) gmem_u4;
 typedef u32x2 __attribute__((address_space(1))) gmem_u2;
 typedef uint64_t __attribute__((address_space(1))) gmem_u64;
+typedef uint32_t __attribute__((address_space(1))) gmem_u32;
+typedef uint8_t __attribute__((address_space(1))) gmem_u8;
 #else
 typedef u32x4 gmem_u4;
 typedef u32x2 gmem_u2;
 typedef uint64_t gmem_u64;
+typedef uint32_t gmem_u32;
+typedef uint8_t gmem_u8;
 #endif
 
 // last j in [lo, hi] with off[j] <= x (off[lo] <= x): the segment, record or cell that holds
@@ -59,5 +64,10 @@ __device__ __forceinline__ void copy_row(uint8_t* __restrict__ dst, const uint8_
 
 // url-hash chars 6..11 (the host hash) = the key's low 36 bits (key_host36, yrwi_kernels.hip)
 __device__ __forceinline__ uint64_t host36(uint64_t hi, uint32_t lo) { return ((hi & 0xFFFFFFFull) << 8) | (lo & 0xFFu); }
+
+// character v of Base64Order.enhancedCoder's alphabet (ALPHA, yrwi_host.h)
+__device__ __forceinline__ uint32_t b64_char(uint32_t v) {
+  return v < 26 ? 'A' + v : v < 52 ? 'a' + (v - 26) : v < 62 ? '0' + (v - 52) : v == 62 ? '-' : '_';
+}
 
 }  // namespace yrwi

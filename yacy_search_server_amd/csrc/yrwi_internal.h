@@ -697,6 +697,43 @@ int launch_local_rows(const LocalJob* d_jobs, const int64_t* d_tile_base, int32_
 int launch_tsb_rows(const LocalJob* d_jobs, const int64_t* d_tile_base, int32_t njobs, int64_t tiles,
                     const uint64_t* dkhi, const uint8_t* dklo, const int64_t* d_qtile, int32_t nq, int32_t* d_tile_cnt,
                     int64_t* d_tile_start, int64_t* d_row_off, int64_t cap_rows, uint8_t* out, void* stream);
+// ---- host facets of a query batch (yrwi_host_facets_batch; kernels in yrwi_facets.hip)
+// The device buffers of one call.  jobs / tile_base / tiles as launch_tsb_rows takes them (LocalJob::evjob
+// = the query); row_base[j] = container rows of the jobs before job j; n = their sum, the sorted items.
+struct FacetDev {
+  const LocalJob* jobs = nullptr;
+  const int64_t* tile_base = nullptr;
+  const int64_t* row_base = nullptr;
+  int32_t njobs = 0, nq = 0, max_hosts = 0;
+  int64_t tiles = 0, n = 0;
+  const uint64_t* dkhi = nullptr;
+  const uint8_t* dklo = nullptr;
+  uint64_t *key = nullptr, *skey = nullptr;  // n each: (query << 36 | host36) as written and sorted
+  uint32_t *val = nullptr, *sval = nullptr;  // n each: the url ids beside them
+  int32_t* flag = nullptr;                   // n + 1: run heads and the terminal
+  int64_t* hx = nullptr;                     // n + 1: their exclusive sum
+  uint64_t* rkey = nullptr;                  // n + 1 each: per run its key, first position, first url id
+  uint32_t *rpos = nullptr, *ruid = nullptr;
+  int64_t* qstart = nullptr;                 // nq + 1: the first run of every query
+  int64_t* nwrite = nullptr;                 // nq + 1: hosts written per query, then 0
+  int64_t* host_off = nullptr;               // nq + 1: their exclusive sum
+  int64_t* nhosts = nullptr;                 // nq: distinct hosts per query
+  void* tmp = nullptr;                       // facet_tmp_bytes(n, nq) of sort / scan scratch (launch_facet_group)
+  size_t tmp_bytes = 0;
+};
+int facet_key_bits(int32_t nq);  // bits of the query part of a key (values 0 .. nq)
+size_t facet_tmp_bytes(int64_t n, int32_t nq);  // 0: the size query failed
+// keys, sort, heads, scan, runs, per-query counts, scan: FACET_GROUP_LAUNCHES launches, no host wait
+constexpr int FACET_GROUP_LAUNCHES = 7;
+int launch_facet_group(const FacetDev& F, void* stream);
+// YRWI_FACETS_BY_COUNT: the nruns runs in (query, count descending, host) order, F.sval = their indices; 2 launches.
+// tmp: facet_order_tmp_bytes(nruns, nq) of sort scratch (the number of runs is known after the first wait).
+size_t facet_order_tmp_bytes(int64_t nruns, int32_t nq);
+int launch_facet_order(const FacetDev& F, int64_t nruns, void* tmp, size_t tmp_bytes, void* stream);
+// the `total` written hosts into device scratch (6, 8 and 12 bytes each; d_urls12 may be nullptr); 1 launch
+int launch_facet_pack(const FacetDev& F, int64_t total, bool by_count, uint8_t* d_hosts6, int64_t* d_counts,
+                      uint8_t* d_urls12, void* stream);
+
 // what the host reads back after k_event_add, in one buffer of 2 njobs + nev words: out[j] =
 // d_evjobs[j].n and out[njobs + j] = d_status[j] of the njobs arrivals, out[2 njobs + e] = the
 // epoch event e has reached

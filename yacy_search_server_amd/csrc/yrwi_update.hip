@@ -1566,11 +1566,6 @@ __global__ __launch_bounds__(256) void k_uc_compact(UcCand C, const int32_t* __r
   oref[px[i]] = refs;
 }
 
-// character v of Base64Order.enhancedCoder's alphabet (ALPHA, yrwi_host.h)
-__device__ __forceinline__ uint32_t b64_char(uint32_t v) {
-  return v < 26 ? 'A' + v : v < 52 ? 'a' + (v - 26) : v < 62 ? '0' + (v - 52) : v == 62 ? '-' : '_';
-}
-
 // result i < n: the 12 characters of the dictionary key of id[i] (key_chars' rule; three words) and its references
 __global__ __launch_bounds__(256) void k_uc_place(const uint32_t* __restrict__ id, const uint32_t* __restrict__ refs,
                                                   int64_t n, const uint64_t* __restrict__ dkhi,

@@ -765,6 +765,52 @@ class RWIIndex:
         rows = buf[:40 * int(row_off[-1])].reshape(-1, 40)
         return [rows[row_off[i]:row_off[i + 1]] for i in range(len(queries))], st
 
+    def host_facets_batch_raw(self, queries: Sequence[Query], order: int, max_hosts: int, hosts6_out, counts_out,
+                              urls12_out, cap: int, host_off, nhosts=None,
+                              nrows=None) -> Tuple[int, "_lib.CFacetStats"]:
+        """yrwi_host_facets_batch as it is: the buffers are ctypes arrays, numpy arrays, addresses
+        or None (hosts6_out and counts_out None: the count-only form).  Returns (rc, the call's
+        yrwi_facet_stats) and raises nothing."""
+        st = _lib.CFacetStats()
+        cq, keep = (self._marshal(queries, 1)[:2]) if len(queries) else (None, None)
+        rc = _lib.lib().yrwi_host_facets_batch(self._h, cq, len(queries), order, max_hosts, _address(hosts6_out),
+                                               _address(counts_out), _address(urls12_out), cap, _address(host_off),
+                                               _address(nhosts), _address(nrows), ctypes.byref(st))
+        return rc, st
+
+    def host_facets_batch(self, queries: Sequence[Query], order: str = "count", max_hosts: int = 0,
+                          urls: bool = True):
+        """The hosts of every query's joined container (yrwi_host_facets_batch): per query
+        (hosts, counts, urls) -- the six-character host hashes as a list of bytes, their postings
+        as an int64 array and, with urls=True, each host's smallest url hash as a list of bytes
+        (else None) -- in `order` ("count": postings descending, ties by host; "host": ascending
+        host hash), the first max_hosts of them (0: all).  Returns (facets, nhosts, nrows, stats):
+        nhosts[i] the distinct hosts and nrows[i] the rows of query i's container, and the
+        call's yrwi_facet_stats.  The buffers are sized by the sum of each query's smallest
+        include list (no counting call first)."""
+        nq = len(queries)
+        cap = 0
+        for q in queries:
+            m = min((self.get_size(t) for t in q.include), default=0)
+            cap += min(m, max_hosts) if max_hosts > 0 else m
+        h6 = np.zeros(6 * max(cap, 1), dtype=np.uint8)
+        cnt = np.zeros(max(cap, 1), dtype=np.int64)
+        u12 = np.zeros(12 * max(cap, 1), dtype=np.uint8) if urls else None
+        off = np.zeros(nq + 1, dtype=np.int64)
+        nhosts = np.zeros(max(nq, 1), dtype=np.int64)
+        nrows = np.zeros(max(nq, 1), dtype=np.int64)
+        rc, st = self.host_facets_batch_raw(queries, _lib.FACETS_ORDERS[order], max_hosts, h6, cnt, u12, cap, off,
+                                            nhosts, nrows)
+        _check(self._h, rc)
+        hb = h6.tobytes()
+        ub = u12.tobytes() if urls else b""
+        out = []
+        for i in range(nq):
+            a, b = int(off[i]), int(off[i + 1])
+            out.append(([hb[6 * j:6 * j + 6] for j in range(a, b)], cnt[a:b],
+                        [ub[12 * j:12 * j + 12] for j in range(a, b)] if urls else None))
+        return out, nhosts[:nq], nrows[:nq], st
+
     # ---- ReferenceOrder.normalizeWith + cardinal ----
     def normalize_score(self, rows: np.ndarray, profile: Optional[RankingProfile] = None, language: str = "en",
                         now_ms: int = 0) -> np.ndarray:
