@@ -539,6 +539,37 @@ typedef struct yrwi_index_info {
   int64_t bitmap_lists;         /* lists with a url-id bitmap */
 } yrwi_index_info;
 int yrwi_index_info_get(yrwi_ctx* ctx, yrwi_index_info* info);
+/* The pair cache: the joined containers of two-term queries (two distinct include
+ * terms, no exclude term, no filter, no url selection, max_distance
+ * YRWI_MAX_DISTANCE_ANY, no authority profile; yrwi_query / yrwi_query_batch and
+ * their rows and submit forms on an unsharded context) are kept in device memory
+ * across calls, keyed by the two terms and the day now_ms falls on.  A later query
+ * of the pair skips its join and is normalised, scored and cut from the kept
+ * container: results do not change.  Every index change drops all entries.
+ * Environment, read per call: YRWI_PAIR_CACHE=0 turns it off; YRWI_PAIR_CACHE_MB
+ * (default 2048) is the byte budget -- the device block itself is reserved when the
+ * url ids are next built (after an index change; a context whose ids were built
+ * with the cache off, or with a smaller value, has no or a smaller block until
+ * then), later calls may only lower the budget within it;
+ * YRWI_PAIR_CACHE_MIN_ROWS (default 16384) is the joined size from which a
+ * container is kept.  The counters run from yrwi_open. */
+typedef struct yrwi_pair_cache_info {
+  int64_t enabled;         /* 1: query batches use it (0: switched off, a sharded context, or no block reserved yet) */
+  int64_t capacity_bytes;  /* the device block */
+  int64_t budget_bytes;    /* of which entries may take now */
+  int64_t min_rows;        /* admission minimum now */
+  int64_t entries;         /* containers a query can find */
+  int64_t pieces;          /* their normalisation pieces (one per tile of the join that wrote them), summed */
+  int64_t bytes;           /* of the block in use */
+  int64_t hits;            /* queries served from an entry */
+  int64_t misses;          /* queries the cache serves that found none (lists shorter than min_rows are not looked up) */
+  int64_t fills;           /* entries written */
+  int64_t dropped;         /* fills given up: another lane had filled the key meanwhile */
+  int64_t evictions;       /* entries displaced by a fill, least recently used first */
+  int64_t invalidations;   /* times an index change dropped every entry (a change that finds none is not counted) */
+  int64_t rows_served;     /* joined rows of all hits */
+} yrwi_pair_cache_info;
+int yrwi_pair_cache_info_get(yrwi_ctx* ctx, yrwi_pair_cache_info* info);
 /* Device-wide allocation events of the process so far (scratch arena growth,
  * pinned staging growth: each one stalls every lane of the device while it
  * runs).  A caller counts them around a timed region without per-batch

@@ -152,6 +152,12 @@ class CLoadStats(ctypes.Structure):
                                               "dropped_terms")]
 
 
+class CPairCacheInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("enabled", "capacity_bytes", "budget_bytes", "min_rows", "entries",
+                                              "pieces", "bytes", "hits", "misses", "fills", "dropped", "evictions",
+                                              "invalidations", "rows_served")]
+
+
 class CUpdateStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int64) for n in ("terms", "new_terms", "emptied_terms", "added", "replaced", "dropped",
                                               "removed")] + [("launches", ctypes.c_int32), ("syncs", ctypes.c_int32)]
@@ -276,6 +282,7 @@ SIGNATURES = {
                                         ctypes.POINTER(ctypes.c_int64)]),
     "yrwi_realloc_events": (ctypes.c_int64, []),
     "yrwi_index_info_get": (ctypes.c_int, [_VP, ctypes.POINTER(CIndexInfo)]),
+    "yrwi_pair_cache_info_get": (ctypes.c_int, [_VP, ctypes.POINTER(CPairCacheInfo)]),
     "yrwi_query": (ctypes.c_int, [_VP, ctypes.POINTER(CQuery), ctypes.POINTER(CHit),
                                   ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(CStats)]),
     "yrwi_query_batch": (ctypes.c_int, [_VP, ctypes.POINTER(CQuery), ctypes.c_int32, ctypes.c_int32,

@@ -723,6 +723,7 @@ int repack_index(CtxBase* ctx, bool force) {
   ctx->index_repacks++;
   // the line heads and bitmaps point at url ids that may have moved: rebuilt next
   ctx->uid_dirty = true;
+  pair_cache_invalidate(ctx);
   return 0;
 }
 
@@ -774,6 +775,7 @@ int ensure_host_ids(CtxBase* ctx) {
   hipStream_t st = ctx->stream;
   const int64_t n = ctx->nurls;
   if (n > (int64_t)INT32_MAX) return 0;  // (the key path serves)
+  pair_cache_invalidate(ctx);  // word 3 of every record is stamped below: cached containers carry copies of it
   DevBuf bhk, bhk2, bidx, bidx2, bflag, brank, bhid, btmp;
   uint64_t* hk = bhk.get<uint64_t>((size_t)n);
   uint64_t* hk2 = bhk2.get<uint64_t>((size_t)n);
@@ -838,6 +840,7 @@ int ensure_host_ids(CtxBase* ctx) {
 
 void index_changed(CtxBase* ctx, const KeyT& term, int64_t old_n, bool added) {
   ctx->uid_dirty = true;
+  pair_cache_invalidate(ctx);  // url ids are ranks: any list change may shift them
   ctx->host_ids = false;  // a new list's records carry no host ids; new urls may bring new hosts
   for (Lane* L : ctx->lanes) L->host_ids = false;
   ctx->dict_churn += old_n;
@@ -847,6 +850,9 @@ void index_changed(CtxBase* ctx, const KeyT& term, int64_t old_n, bool added) {
 
 int ensure_url_ids(CtxBase* ctx) {
   if (!ctx->uid_dirty) return 0;
+  // url ids, line heads, bitmaps and J5 arrays are rebuilt below: whatever marked them stale
+  // (index_changed, a repack, a failed rebuild) made the cached containers stale too
+  pair_cache_invalidate(ctx);
   if (int rc = repack_index(ctx, false)) return rc;
   hipStream_t st = ctx->stream;
   std::vector<ListRec*> lists, changed, others;
@@ -893,6 +899,7 @@ int ensure_url_ids(CtxBase* ctx) {
   }
   ctx->dict_pending.clear();
   ctx->uid_dirty = false;
+  pair_cache_reserve(ctx);  // before the lanes' scratch is derived from the memory left
   measure_scratch(ctx);  // what the index leaves for the lanes' scratch
   return 0;
 }

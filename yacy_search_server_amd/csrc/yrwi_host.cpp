@@ -405,6 +405,7 @@ extern "C" void yrwi_close(yrwi_ctx* ctx) {
   if (ctx->win_dev) hipFree(ctx->win_dev);
   if (ctx->win_host) hipHostFree(ctx->win_host);
   if (ctx->host_key) hipFree(ctx->host_key);
+  pair_cache_release(ctx);
   ctx->index_mem.release();
   if (ctx->uid_all) hipFree(ctx->uid_all);
   if (ctx->head_all) hipFree(ctx->head_all);
@@ -921,6 +922,206 @@ void yrwi::measure_scratch(CtxBase* ctx) {
   ctx->scratch_total = std::max<int64_t>((int64_t)fr + arenas - ((int64_t)8 << 30), (int64_t)1 << 30);
 }
 
+// ================================================================ pair cache
+void yrwi::pair_cache_invalidate(CtxBase* ctx) {
+  std::lock_guard<std::mutex> lk(ctx->pcache.mu);
+  ctx->pcache.tab.invalidate();
+}
+
+void yrwi::pair_cache_release(CtxBase* ctx) {
+  PairCache& C = ctx->pcache;
+  std::lock_guard<std::mutex> lk(C.mu);
+  C.tab.reset(0);
+  if (C.block) hipFree(C.block);
+  C.block = nullptr;
+  for (hipEvent_t e : C.ev)
+    if (e) hipEventDestroy(e);
+  C.ev.clear();
+  C.ready.clear();
+}
+
+void yrwi::pair_cache_reserve(CtxBase* ctx) {
+  PairCache& C = ctx->pcache;
+  std::lock_guard<std::mutex> lk(C.mu);
+  const size_t want = ctx->sharded || !pair_cache_enabled() ? 0 : pair_cache_budget();
+  if (want == C.tab.capacity()) return;
+  C.tab.reset(0);  // (nothing is in flight: no entry is pinned)
+  if (C.block) hipFree(C.block);
+  C.block = nullptr;
+  if (want == 0) return;
+  note_realloc("pair cache", want);
+  void* p = nullptr;
+  if (hipMalloc(&p, want) != hipSuccess) {
+    (void)hipGetLastError();  // no block: the cache stays off (yrwi_pair_cache_info_get reports it)
+    return;
+  }
+  C.block = static_cast<uint8_t*>(p);
+  C.tab.reset(want);
+}
+
+static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+// an entry's block: the records, the url ids, the pieces, each from a 256-B boundary
+static size_t pair_entry_bytes(int64_t rows, int64_t ntiles) {
+  return al256((size_t)rows * FEAT_BYTES) + al256((size_t)rows * 4) + al256((size_t)ntiles * sizeof(ChunkSum));
+}
+
+int yrwi::pair_cache_lookup(Lane* L, std::vector<Plan>& plans) {
+  PairCache* C = L->pcache;
+  if (!C) return 0;
+  const int64_t min_rows = pair_cache_min_rows();
+  // hits whose fill is not known to be complete: (slot, its event); looked at outside the lock
+  std::vector<std::pair<int32_t, hipEvent_t>> fresh;
+  std::unique_lock<std::mutex> lk(C->mu);
+  if (!C->block) return 0;
+  for (Plan& P : plans) {
+    P.pc_slot = -1;
+    P.pc_fill = false;
+    // two distinct include terms and nothing else; a last step that gets pieces (no authority counts)
+    if (P.empty || P.rep >= 0 || P.chain || P.seq.size() != 2 || P.ninc != 2 || P.nexc != 0 || P.filter ||
+        P.has_sel || P.maxd != YRWI_MAX_DISTANCE_ANY || P.prof.coeff_authority > 12 || P.now_ms < 0)
+      continue;
+    if (std::min(P.seq[0]->n, P.seq[1]->n) < min_rows) continue;  // its container cannot reach the minimum
+    P.pc_key = pair_key(P.inc[0].hi, P.inc[0].lo, P.inc[1].hi, P.inc[1].lo, P.now_ms / DAY_MS);
+    const int32_t s = C->tab.lookup(P.pc_key);
+    if (s < 0) {
+      P.pc_fill = true;
+      continue;
+    }
+    L->pc_pins.push_back(s);
+    if (!C->ready[(size_t)s]) fresh.push_back({s, C->ev[(size_t)s]});
+    const PairEntry& e = C->tab.at(s);
+    uint8_t* base = C->block + e.off;
+    uint64_t* feat = reinterpret_cast<uint64_t*>(base);
+    uint32_t* uid = reinterpret_cast<uint32_t*>(base + al256((size_t)e.rows * FEAT_BYTES));
+    const ChunkSum* ps = reinterpret_cast<const ChunkSum*>(base + al256((size_t)e.rows * FEAT_BYTES) +
+                                                           al256((size_t)e.rows * 4));
+    P.cont = DList{nullptr, nullptr, nullptr, e.rows, uid, feat, nullptr, nullptr, 0};
+    P.pieces = ps;
+    P.npieces = e.ntiles;
+    P.pc_slot = s;
+  }
+  lk.unlock();
+  // Filled a moment ago, maybe by another lane: this lane's stream goes behind the fill's event
+  // (the pin keeps slot and event this entry's).  The table's lock is held for table calls only.
+  std::vector<int32_t> done;
+  for (auto& f : fresh) {
+    if (hipEventQuery(f.second) == hipSuccess) {
+      done.push_back(f.first);
+    } else {
+      (void)hipGetLastError();
+      HIPCHK(L, hipStreamWaitEvent(L->stream, f.second, 0));
+    }
+  }
+  if (!done.empty()) {
+    lk.lock();
+    for (int32_t s : done) C->ready[(size_t)s] = 1;
+  }
+  return 0;
+}
+
+int yrwi::pair_cache_fill(Lane* L, std::vector<Plan>& plans, const std::vector<JoinQ>& jobs,
+                          const std::vector<int>& owner, const std::vector<int64_t>& mh) {
+  PairCache* C = L->pcache;
+  if (!C) return 0;
+  bool any = false;
+  for (size_t j = 0; j < jobs.size(); j++) any |= plans[(size_t)owner[j]].pc_fill;
+  if (!any) return 0;
+  const int64_t min_rows = pair_cache_min_rows();
+  std::lock_guard<std::mutex> lk(C->mu);
+  if (!C->block) return 0;
+  const size_t budget = std::min(pair_cache_budget(), C->tab.capacity());
+  PairFill f{};
+  std::vector<int32_t> filled;
+  // an error: the entries reserved here and not yet published go (PairTable::abort), so that their
+  // keys can be filled again; their pins go with them
+  auto give_up = [&](const char* what) {
+    for (int32_t s : filled) {
+      if (C->tab.at(s).published) continue;
+      C->tab.abort(s);
+      L->pc_pins.erase(std::find(L->pc_pins.begin(), L->pc_pins.end(), s));
+    }
+    return L->fail(YRWI_E_HIP, what);
+  };
+  for (size_t j = 0; j < jobs.size(); j++) {
+    const JoinQ& J = jobs[j];
+    Plan& P = plans[(size_t)owner[j]];
+    if (!P.pc_fill || J.count_only || J.chained || !J.psum || !J.out_uid || !J.out_feat || J.out_tup ||
+        mh[j] < min_rows)
+      continue;
+    P.pc_fill = false;
+    const int64_t rows = mh[j];
+    // (a key another lane filled meanwhile: the insert is dropped)
+    const int32_t s = C->tab.insert(P.pc_key, rows, J.ntiles, pair_entry_bytes(rows, J.ntiles), budget);
+    if (s < 0) continue;
+    if ((size_t)s >= C->ev.size()) {
+      C->ev.resize((size_t)s + 1, nullptr);
+      C->ready.resize((size_t)s + 1, 0);
+    }
+    if (!C->ev[(size_t)s] && hipEventCreateWithFlags(&C->ev[(size_t)s], hipEventDisableTiming) != hipSuccess) {
+      C->ev[(size_t)s] = nullptr;
+      C->tab.abort(s);
+      return give_up("pair cache event");
+    }
+    L->pc_pins.push_back(s);  // until this pass ends: the copy below is complete by then
+    filled.push_back(s);
+    C->ready[(size_t)s] = 0;
+    uint8_t* base = C->block + C->tab.at(s).off;
+    const size_t fb = (size_t)rows * FEAT_BYTES, ub = (size_t)rows * 4, pb = (size_t)J.ntiles * sizeof(ChunkSum);
+    const uint8_t* src[3] = {reinterpret_cast<const uint8_t*>(J.out_feat), reinterpret_cast<const uint8_t*>(J.out_uid),
+                             reinterpret_cast<const uint8_t*>(J.psum)};
+    uint8_t* dst[3] = {base, base + al256(fb), base + al256(fb) + al256(ub)};
+    const size_t nb[3] = {fb, ub, pb};
+    if (f.n + 3 > PAIR_FILL_MAX) {
+      if (launch_pair_fill(f, L->stream)) return give_up("pair cache fill launch");
+      f = PairFill{};
+    }
+    for (int k = 0; k < 3; k++) {
+      f.src[f.n] = src[k];
+      f.dst[f.n] = dst[k];
+      f.bytes[f.n] = nb[k];
+      f.n++;
+    }
+  }
+  if (f.n && launch_pair_fill(f, L->stream)) return give_up("pair cache fill launch");
+  // visible to the other lanes only now, behind an event on this lane's stream
+  for (int32_t s : filled) {
+    if (hipEventRecord(C->ev[(size_t)s], L->stream) != hipSuccess) return give_up("pair cache event record");
+    C->tab.publish(s);
+  }
+  return 0;
+}
+
+void yrwi::pair_cache_unpin(Lane* L) {
+  if (L->pcache && !L->pc_pins.empty()) {
+    std::lock_guard<std::mutex> lk(L->pcache->mu);
+    for (int32_t s : L->pc_pins) L->pcache->tab.unpin(s);
+  }
+  L->pc_pins.clear();
+}
+
+extern "C" int yrwi_pair_cache_info_get(yrwi_ctx* ctx, yrwi_pair_cache_info* out) {
+  if (!ctx || !out) return YRWI_E_ARG;
+  std::memset(out, 0, sizeof(*out));
+  PairCache& C = ctx->pcache;
+  std::lock_guard<std::mutex> lk(C.mu);
+  const PairCounters& c = C.tab.counters();
+  out->enabled = !ctx->sharded && pair_cache_enabled() && C.block != nullptr ? 1 : 0;
+  out->capacity_bytes = (int64_t)C.tab.capacity();
+  out->budget_bytes = (int64_t)std::min(pair_cache_budget(), C.tab.capacity());
+  out->min_rows = pair_cache_min_rows();
+  out->entries = C.tab.entries();
+  out->pieces = C.tab.pieces();
+  out->bytes = (int64_t)C.tab.bytes_used();
+  out->hits = c.hits;
+  out->misses = c.misses;
+  out->fills = c.fills;
+  out->dropped = c.dropped;
+  out->evictions = c.evictions;
+  out->invalidations = c.invalidations;
+  out->rows_served = c.rows_served;
+  return 0;
+}
+
 static int run_batch_part_(const yrwi_ctx* ix, Lane* L, const yrwi_query_desc* q, int32_t nq, int32_t kmax,
                            yrwi_hit* out, uint8_t* rows, int32_t* nout, yrwi_stats* st);
 
@@ -930,6 +1131,9 @@ static int run_batch_part(const yrwi_ctx* ix, Lane* L, const yrwi_query_desc* q,
   L->enter();
   const int64_t seq = L->seq;  // (passing the turn after the final collective clears L->seq)
   const int rc = run_batch_part_(ix, L, q, nq, kmax, out, rows, nout, st);
+  if (rc && !L->pc_pins.empty()) (void)lane_sync(L);  // a failed pass: nothing of it reads a cached entry any more
+  pair_cache_unpin(L);
+  L->pcache = nullptr;
   // peers waiting on this part's exchanges fail fast; later parts are unaffected
   if (rc && L->hostx) hostx_abort(L->hostx, seq);
   turn_release(L);  // error paths, parts without collectives: the turn still passes in order
@@ -991,6 +1195,8 @@ static int run_batch_part_(const yrwi_ctx* ix, Lane* L, const yrwi_query_desc* q
     std::vector<Plan> plans(std::make_move_iterator(all.begin() + g0), std::make_move_iterator(all.begin() + g1));
     L->release_after_final = g1 >= nq;
     if (begin_pass(L)) return YRWI_E_HIP;
+    // the pair cache serves query batches on one context (knobs read per pass)
+    L->pcache = !L->sharded && pair_cache_enabled() ? &const_cast<yrwi_ctx*>(ix)->pcache : nullptr;
     // HIP events (per-kernel timing) only when the caller asked for statistics
     Timing tm;
     Timing* tmp = st ? &tm : nullptr;
@@ -1012,6 +1218,7 @@ static int run_batch_part_(const yrwi_ctx* ix, Lane* L, const yrwi_query_desc* q
     rc = run_rank_phase(L, plans, kmax, out + (size_t)g0 * kmax, nout + g0, nullptr, st, tmp, /*collective=*/true,
                         rows ? rows + (size_t)YRWI_ROW_BYTES * (size_t)g0 * kmax : nullptr);
     if (rc) return rc;
+    pair_cache_unpin(L);  // the pass's results are complete (run_rank_phase waited for them)
     tr += now_ns() - tr0;
     if (st) {
       if (g1 < nq) HIPCHK(L, lane_sync(L));  // the pass's events must be complete before they are reused

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "yrwi_internal.h"
+#include "yrwi_pair_cache.h"
 
 namespace yrwi {
 
@@ -219,6 +220,12 @@ struct Plan {
   // an identical query earlier in the same pass (yrwi_share.h: its index among the pass's plans) or
   // -1: this query joins nothing and ranks nothing, its hits and rows are the representative's
   int32_t rep = -1;
+  // pair cache (PairCache): the entry this query's container and pieces were taken from (a hit:
+  // no join job), or -1; pc_fill: a miss of a query the cache serves, whose joined container
+  // becomes an entry (pc_key) if it is large enough
+  int32_t pc_slot = -1;
+  bool pc_fill = false;
+  PairKey pc_key;
 };
 
 
@@ -264,6 +271,35 @@ struct CollTurn {
   std::condition_variable cv;
   int64_t next = 0;
 };
+
+// The pair cache of a context: the joined containers of two-term queries, with
+// their normalisation pieces, kept across query calls and handed to the rank phase in place of a
+// join.  One device block, reserved with the index (ensure_url_ids) and allocated from by the
+// table (yrwi_pair_cache.h); one event per table slot, recorded on the filling lane's stream
+// after the copy into the entry: a reader on another stream waits on it, never on the host.
+// Every member is used under mu.
+struct PairCache {
+  std::mutex mu;
+  PairTable tab;
+  uint8_t* block = nullptr;
+  std::vector<hipEvent_t> ev;  // by slot
+  std::vector<char> ready;     // by slot: the fill is known to be complete (no wait any more)
+};
+// the knobs, read per call: YRWI_PAIR_CACHE=0 turns the cache off, YRWI_PAIR_CACHE_MB is its
+// byte budget (default 2048), YRWI_PAIR_CACHE_MIN_ROWS the joined rows from which a container
+// is admitted (default 16384: eight rank chunks)
+inline bool pair_cache_enabled() {
+  const char* e = getenv("YRWI_PAIR_CACHE");
+  return !(e && e[0] == '0');
+}
+inline size_t pair_cache_budget() {
+  const char* e = getenv("YRWI_PAIR_CACHE_MB");
+  return (size_t)(e ? std::max<long long>(0, atoll(e)) : 2048) << 20;
+}
+inline int64_t pair_cache_min_rows() {
+  const char* e = getenv("YRWI_PAIR_CACHE_MIN_ROWS");
+  return e ? std::max<int64_t>(1, atoll(e)) : (int64_t)16384;
+}
 
 // One execution lane: a HIP stream with its own scratch arena, pinned staging,
 // events and (sharded) communicator.  A batch is split over the lanes and each
@@ -339,6 +375,10 @@ struct Lane {
   HostX* hostx = nullptr;  // host exchange of the batch part's list sizes (shared by the lanes)
   int32_t xcall = 0;       // exchanges made by the running part
   bool turn_held = false, release_after_final = false;
+  // the context's pair cache while a query batch's pass runs on this lane (nullptr: off, a
+  // sharded context, or another entry point's join), and the entries the pass has pinned
+  PairCache* pcache = nullptr;
+  std::vector<int32_t> pc_pins;
 
   int fail(int code, const std::string& m) {
     err = m;
@@ -478,6 +518,7 @@ struct CtxBase {
   };
   std::vector<LocalBlock*> local_blocks;
   size_t local_bytes = 0;  // of local_blocks
+  PairCache pcache;
   // run_windows (yrwi_dump_heap, yrwi_dht_select): two device and two pinned windows of win_cap
   // bytes each, allocated on first use and kept
   uint8_t* win_dev = nullptr;
@@ -797,6 +838,24 @@ int join_containers(yrwi_ctx* ctx, Lane* L, const yrwi_query_desc* const* q, int
 void measure_scratch(CtxBase* ctx);
 // dense host ids in every index record (after ensure_url_ids; no batch in flight)
 int ensure_host_ids(CtxBase* ctx);
+// ---- pair cache (yrwi_host.cpp)
+// An array a cached container was derived from is about to be rewritten or renumbered (lists, url
+// ids, bitmaps, records): every entry is stale.  No batch is in flight.
+void pair_cache_invalidate(CtxBase* ctx);
+// The cache's device block, sized by YRWI_PAIR_CACHE_MB, before the lanes' scratch is measured
+// (ensure_url_ids; no batch in flight).  A sharded context has none.
+void pair_cache_reserve(CtxBase* ctx);
+void pair_cache_release(CtxBase* ctx);  // yrwi_close
+// Planning: every plan the cache serves (two include lists, nothing else; one context) is looked
+// up.  A hit takes the entry's container and pieces (P.cont, P.pieces, P.pc_slot; pinned; the
+// lane's stream waits for a fill still in flight) and joins nothing; a miss is marked (P.pc_fill).
+int pair_cache_lookup(Lane* L, std::vector<Plan>& plans);
+// After a step's compaction, its joined sizes known (mh, by job): the marked plans' containers of
+// at least the admission minimum are copied into new entries on the lane's stream.
+int pair_cache_fill(Lane* L, std::vector<Plan>& plans, const std::vector<JoinQ>& jobs, const std::vector<int>& owner,
+                    const std::vector<int64_t>& mh);
+// The pass's results are complete (or it failed and the lane is drained): its pins go.
+void pair_cache_unpin(Lane* L);
 // the list of `term` was added / replaced (added = true) or removed: url ids are due.  old_n is
 // charged to dict_churn: the postings whose keys may have left the dictionary's lists (put_list:
 // the whole old list; yrwi_update.hip: the postings really removed, 0 for an add)

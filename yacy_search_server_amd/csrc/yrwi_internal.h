@@ -370,6 +370,17 @@ struct CopyIn {
   int32_t n;
 };
 int launch_copy_in(const CopyIn& c, void* stream);
+// device -> device copies of up to PAIR_FILL_MAX ranges in one launch: joined containers and their
+// pieces into their pair-cache entries (yrwi_host.h PairCache).  dst ranges start 256-B aligned,
+// src ranges 4-B aligned at least; bytes: multiples of 4
+constexpr int PAIR_FILL_MAX = 12;
+struct PairFill {
+  const uint8_t* src[PAIR_FILL_MAX];
+  uint8_t* dst[PAIR_FILL_MAX];
+  uint64_t bytes[PAIR_FILL_MAX];
+  int32_t n;
+};
+int launch_pair_fill(const PairFill& f, void* stream);
 // device -> pinned host readback (dst: device address of pinned host memory): n
 // elements of `elem` bytes, the source's `stride` bytes apart (4-B words when aligned)
 int launch_gather_out(uint8_t* dst, const uint8_t* src, int64_t n, int32_t elem, int64_t stride, void* stream);

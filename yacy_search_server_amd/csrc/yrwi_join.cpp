@@ -336,6 +336,7 @@ struct PendingCompact {
   bool active = false;
   JoinStep step;
   std::vector<std::array<int64_t, CHAIN_LVL>> level;  // per job (layout order): k_chain's level counts
+  std::vector<int64_t> mh;  // per job: its joined rows (the pair cache fills from them after the compaction)
 };
 
 // One fold step's join jobs: layout, launch, joined sizes back to the plans.
@@ -426,9 +427,14 @@ static int run_join_jobs(Lane* ctx, std::vector<Plan>& plans, std::vector<JoinQ>
     P.pieces = J.psum;
     P.npieces = J.psum ? J.ntiles : 0;
   }
+  // the containers of the queries the pair cache missed become its entries (a chained step's
+  // jobs are compacted later: finish_chained_step fills then)
+  if (!S.chain)
+    if (int rc = pair_cache_fill(ctx, plans, jobs, owner, mh)) return rc;
   if (S.chain && pend) {
     pend->active = true;
     pend->step = S;
+    pend->mh = mh;
     pend->level.assign((size_t)nj, {0, 0, 0, 0, 0});
     const int64_t* hl = reinterpret_cast<const int64_t*>(land) + nj;
     for (int j = 0; j < nj; j++)
@@ -478,8 +484,9 @@ static int run_exclusion(Lane* ctx, std::vector<Plan>& plans, yrwi_stats* st, Ti
 }
 
 // a query steps at s while it has a list left and its global container (acc_g) is not empty
+// (a pair-cache hit has its container already: it never steps)
 static bool steps_at(const Plan& P, int64_t acc_g, size_t s) {
-  return !P.empty && P.seq.size() > s + 1 && acc_g > 0 && !(P.chain && s > 0);
+  return !P.empty && P.pc_slot < 0 && P.seq.size() > s + 1 && acc_g > 0 && !(P.chain && s > 0);
 }
 
 // url selections (resolve_selections): their ids for this pass's kernels (dsel,
@@ -770,6 +777,7 @@ static int finish_chained_step(Lane* ctx, std::vector<Plan>& plans, const std::v
       tm->kcompact.push_back({c0, c1});
       tm->spans.push_back({c0, c1});
     }
+    if (int rc = pair_cache_fill(ctx, plans, J.jobs, J.owner, pend.mh)) return rc;
   }
   if (st)
     for (size_t k = 0; k < cqs.size(); k++) {
@@ -809,6 +817,16 @@ int yrwi::run_join_phase(Lane* ctx, std::vector<Plan>& plans, yrwi_stats* st, Ti
   std::vector<ChainQ> chq(nq);
   bool any_chain = false;
   if (int rc = plan_chains(ctx, plans, acc_g, dsel, st, chq, &any_chain)) return rc;
+  // two-term queries whose joined container the pair cache holds take it and join nothing
+  if (int rc = pair_cache_lookup(ctx, plans)) return rc;
+  for (Plan& P : plans) {
+    if (P.pc_slot < 0) continue;
+    P.step_mode[0] = dispatch_mode(acc_g[(size_t)(&P - plans.data())], P.seq_ng[1]);
+    if (st) {  // the reference's work for the query, as a miss accounts it; no kernel loaded a byte
+      st->bytes_alg += step_bytes(P.step_mode[0], P.seq[0]->n, P.seq[1]->n);
+      if (P.step_mode[0] == JM_ENUM) st->n_enum_steps++; else st->n_test_steps++;
+    }
+  }
   for (size_t s = 0;; s++) {
     StepJobs J;
     if (int rc = build_step_jobs(ctx, plans, acc_g, chq, s, st, &J)) return rc;

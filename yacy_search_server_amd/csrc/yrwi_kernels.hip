@@ -270,6 +270,45 @@ int launch_copy_in(const CopyIn& c, void* stream) {
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// Pair-cache fills (yrwi_host.h PairCache): a joined container and its pieces copied from the
+// lane's scratch into the entry's block, COPY_IN_BLOCK bytes per workgroup.  The widest word the
+// source's alignment allows (a job's pieces start anywhere in the step's ChunkSum array); a range's
+// last bytes are copied bytewise.
+template <class T>
+__device__ __forceinline__ void copy_range(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint64_t lo,
+                                           uint64_t end) {
+  const uint64_t words = (end - lo) / sizeof(T);
+  for (uint64_t w = threadIdx.x; w < words; w += 256)
+    *reinterpret_cast<T*>(dst + lo + w * sizeof(T)) = *reinterpret_cast<const T*>(src + lo + w * sizeof(T));
+  for (uint64_t x = lo + words * sizeof(T) + threadIdx.x; x < end; x += 256) dst[x] = src[x];
+}
+__global__ __launch_bounds__(256) void k_pair_fill(PairFill f) {
+  uint32_t b = blockIdx.x;
+  int e = 0;
+  for (; e < f.n; e++) {
+    const uint32_t nb = (uint32_t)((f.bytes[e] + COPY_IN_BLOCK - 1) / COPY_IN_BLOCK);
+    if (b < nb) break;
+    b -= nb;
+  }
+  if (e >= f.n) return;
+  const uint8_t* __restrict__ src = f.src[e];
+  uint8_t* __restrict__ dst = f.dst[e];
+  const uint64_t lo = (uint64_t)b * COPY_IN_BLOCK, end = min<uint64_t>(f.bytes[e], lo + COPY_IN_BLOCK);
+  const uintptr_t a = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst);
+  if ((a & 15) == 0) copy_range<uint4>(dst, src, lo, end);
+  else if ((a & 7) == 0) copy_range<uint2>(dst, src, lo, end);
+  else if ((a & 3) == 0) copy_range<uint32_t>(dst, src, lo, end);
+  else copy_range<uint8_t>(dst, src, lo, end);
+}
+
+int launch_pair_fill(const PairFill& f, void* stream) {
+  uint32_t blocks = 0;
+  for (int e = 0; e < f.n; e++) blocks += (uint32_t)((f.bytes[e] + COPY_IN_BLOCK - 1) / COPY_IN_BLOCK);
+  if (blocks == 0) return 0;
+  hipLaunchKernelGGL(k_pair_fill, dim3(blocks), dim3(256), 0, (hipStream_t)stream, f);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 __global__ void k_gather_out(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, int64_t n, int32_t elem,
                              int64_t stride, int words) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -685,6 +685,14 @@ class RWIIndex:
         _check(self._h, _lib.lib().yrwi_index_info_get(self._h, ctypes.byref(info)))
         return {f: getattr(info, f) for f, _ in _lib.CIndexInfo._fields_}
 
+    def pair_cache_info(self) -> dict:
+        """The pair cache's state and counters (yrwi_pair_cache_info_get): enabled, block and
+        budget bytes, admission minimum, entries, their pieces, bytes, hits, misses, fills, dropped fills,
+        evictions, invalidations, rows served."""
+        info = _lib.CPairCacheInfo()
+        _check(self._h, _lib.lib().yrwi_pair_cache_info_get(self._h, ctypes.byref(info)))
+        return {f: getattr(info, f) for f, _ in _lib.CPairCacheInfo._fields_}
+
     def get_size(self, term: bytes) -> int:
         n = ctypes.c_int64()
         _check(self._h, _lib.lib().yrwi_list_size(self._h, bytes(term), ctypes.byref(n)))
